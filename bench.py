@@ -14,8 +14,12 @@ size must equal --gpus.  A box with fewer GPUs than ranks is an error, never a s
   --scaling strong --total-units T: BASELINE config 5 (T = 65536): one global list of T intervals, rank r
                    decodes the contiguous shard libmspack_amd.dist.shard_range(T, r, world) of it.
 
-At N=1 the line also carries (measured after the timed region, except host_inclusive's clean-process worker, which runs first):
+A plain run sets up, warms up, times --steps steps, checks the last step's per-unit results (no error, full length) and
+prints the line.  `--dump-outputs DIR` also writes what that last step handed back (rank 0) as DIR/<name>.npy.
+`--full` adds, after the timed region, every byte compared with the plaintext (config.bit_exact), the spread of single
+launches and
   roofline        the LZX kernel's duration from HIP events on the launch stream vs algorithmic bytes
+and at N=1 (host_inclusive's clean-process worker runs first):
   host_inclusive  SURVEY 8(d)'s metric as written: from compressed units in HOST memory to decoded bytes in
                   device memory (mspack_hip_decode_batch_to_device) and, separately, back in host memory
                   (mspack_hip_decode_batch) -- what a cabd/chmd extract() caller gets; measured in a process of its
@@ -224,6 +228,38 @@ def roofline(algo_bytes, ms, kernel, **extra):
          "algorithmic_bytes_per_launch": int(algo_bytes)}
     d.update(extra)
     return d
+
+
+DUMP_MAX_UNITS = 1 << 16        # per-unit arrays: 64 B a unit (float64) -> at most 4 MiB
+DUMP_SAMPLE_BYTES = 1 << 22     # decoded bytes kept as float32 -> 16 MiB
+
+
+def dump_outputs(d, batch, units):
+    """--dump-outputs DIR: what the timed path (mspack_hip_decode_batch_device) handed its caller in the last step, as .npy files --
+    result_<field>.npy: every field of the results array (float64; a seeded sample of DUMP_MAX_UNITS units beyond that many);
+    unit_checksums.npy: per unit of the same units, [sum of its decoded bytes, sum of byte x (1-based position)] (float64, exact);
+    output_sample.npy: a seeded sample of DUMP_SAMPLE_BYTES of all decoded bytes (float32), sorted by position.
+    The whole output (256 MiB at the defaults) is too large to keep; the checksums still see every byte."""
+    os.makedirs(d, exist_ok=True)
+    rng = np.random.default_rng(0x5EED)
+    n = len(units)
+    keep = np.arange(n) if n <= DUMP_MAX_UNITS else np.sort(rng.choice(n, DUMP_MAX_UNITS, replace=False))
+    res = batch.results()[keep]
+    for f in res.dtype.names:
+        np.save(os.path.join(d, "result_%s.npy" % f), res[f].astype(np.float64))
+    out = batch.output()
+    oo, ol = units["out_off"].astype(np.int64), units["out_len"].astype(np.int64)
+    pos = np.arange(1, int(ol.max()) + 1, dtype=np.float64)
+    sums = np.zeros((len(keep), 2))
+    for k, i in enumerate(keep):
+        seg = out[oo[i]:oo[i] + ol[i]]
+        sums[k] = seg.sum(dtype=np.float64), np.dot(seg, pos[:ol[i]])
+    np.save(os.path.join(d, "unit_checksums.npy"), sums)
+    total = int(ol.sum())
+    flat = np.sort(rng.integers(0, total, min(total, DUMP_SAMPLE_BYTES)))
+    starts = np.cumsum(ol) - ol
+    u = np.searchsorted(starts, flat, side="right") - 1
+    np.save(os.path.join(d, "output_sample.npy"), out[oo[u] + flat - starts[u]].astype(np.float32))
 
 
 def secondary_mszip(M, torch, dev, n=4096, ub=32768, iters=10, cpu=True):
@@ -543,7 +579,14 @@ def main():
     ap.add_argument("--host-path-worker", action="store_true", help="internal: the host_inclusive measurement in a process of its own")
     ap.add_argument("--no-api", action="store_true", help="skip through_api (containers through the object API) in the worker")
     ap.add_argument("--exp", action="store_true", help="kernel experiments: skip the parity gate and the CPU leg (the line is then NOT a valid result)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: every byte against the plaintext, the roofline and the spread of single launches, "
+                         "host_inclusive, the secondary configs and the CPU baseline (--no-extras / --no-cpu drop parts of it)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last step computed (rank 0) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.host_path_worker:
         return host_path_worker(args)
@@ -554,7 +597,7 @@ def main():
     # queues on the device the chunks' launches of the host path time-share hardware queues (measured: 8.2 ms instead of
     # 4.0 for the same call, profiles/round3_hostpath.txt).  The same calls made from this process are reported beside it.
     host_clean = None
-    if args.gpus == 1 and int(os.environ.get("WORLD_SIZE", "1")) == 1 and not args.exp and not args.no_extras \
+    if args.full and args.gpus == 1 and int(os.environ.get("WORLD_SIZE", "1")) == 1 and not args.exp and not args.no_extras \
             and args.scaling == "weak" and not args.no_frame_tables:
         host_clean = run_host_path_worker(args)
 
@@ -607,19 +650,24 @@ def main():
     my_elapsed = time.perf_counter() - t0
     elapsed, total_out = D.reduce_scalars(dist, dev, my_elapsed, float(n * ub))
     per_rank_ms = D.gather_scalar(dist, dev, my_elapsed / args.steps * 1e3)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, batch, units)
 
-    ms_kernel = batch.kernel_ms(max(3, min(args.steps, 10)))       # roofline numerator: HIP events on the launch stream
-    singles = sorted(batch.kernel_ms(1) for _ in range(7))          # spread of single launches (outside the timed region)
-    step_spread = [round(singles[0], 4), round(singles[len(singles) // 2], 4), round(singles[-1], 4)]
+    if args.full:
+        ms_kernel = batch.kernel_ms(max(3, min(args.steps, 10)))       # roofline numerator: HIP events on the launch stream
+        singles = sorted(batch.kernel_ms(1) for _ in range(7))          # spread of single launches (outside the timed region)
+        step_spread = [round(singles[0], 4), round(singles[len(singles) // 2], 4), round(singles[-1], 4)]
 
-    # ---- parity: every unit, every byte, outside the timed region ----
+    # ---- parity, outside the timed region: every unit's result; with --full every byte too ----
     res = batch.results()
-    out = batch.output()[:n * ub]
-    ok = bool((res["err"] == 0).all() and (res["out_len"] == ub).all() and np.array_equal(out, plain))
+    ok = bool((res["err"] == 0).all() and (res["out_len"] == ub).all())
+    if args.full:
+        ok = ok and np.array_equal(batch.output()[:n * ub], plain)
     adopted = float(((res["flags"] & M.F_FRAMES_ADOPTED) != 0).mean())
     all_ok = D.all_true(dist, dev, ok)
     if not all_ok and not args.exp:
-        raise SystemExit("rank %d: GPU output is NOT bit-exact on some rank; refusing to report a number" % rank)
+        raise SystemExit("rank %d: GPU output is NOT %s on some rank; refusing to report a number" %
+                         (rank, "bit-exact" if args.full else "free of unit errors"))
 
     comp_bytes = float(ln.sum())
     algo_bytes = comp_bytes + n * ub                      # in + out, per launch
@@ -649,17 +697,19 @@ def main():
             "ms_per_step": round(elapsed / args.steps * 1e3, 4),
             "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None,
             "dtype": "u8", "data": "synthetic",
-            "config": {"workload": wl, "units_per_gpu": n, "unit_bytes": ub, "bit_exact": all_ok,
+            "config": {"workload": wl, "units_per_gpu": n, "unit_bytes": ub,
                        "frame_tables": "off (serial kernel)" if args.no_frame_tables else "on (mspack_lzx_pipe)",
                        "residency": "value: compressed units and decoded bytes resident in HBM; host_inclusive: the same batch from host memory",
                        "units_on_frame_parallel_path": round(adopted, 4),
                        "corpus_gen_s": round(gen_s, 2), "per_rank_ms_per_step": [round(x, 4) for x in per_rank_ms],
-                       "step_ms_min_median_max": step_spread,
                        "launcher": "torchrun" if "TORCHELASTIC_RUN_ID" in os.environ else ("self-spawned" if world > 1 else "single")},
-            "roofline": roofline(algo_bytes, ms_kernel, LZX_KERNELS if adopted > 0.5 else "mspack_decode_lzx",
-                                 traffic=traffic, traffic_source=traffic_source),
         }
-        extras = world == 1 and not args.exp and not args.no_extras
+        if args.full:
+            line["config"]["bit_exact"] = all_ok
+            line["config"]["step_ms_min_median_max"] = step_spread
+            line["roofline"] = roofline(algo_bytes, ms_kernel, LZX_KERNELS if adopted > 0.5 else "mspack_decode_lzx",
+                                        traffic=traffic, traffic_source=traffic_source)
+        extras = args.full and world == 1 and not args.exp and not args.no_extras
         if extras:
             inproc = host_inclusive(M, units, comp, out_bytes, plain, n, ub, torch=torch, dev=dev)
             if host_clean and "MBps" in host_clean:
@@ -675,7 +725,7 @@ def main():
                     line["host_inclusive"]["clean_process_error"] = host_clean.get("error")
         del batch
         torch.cuda.empty_cache()
-        cpu = world == 1 and not args.no_cpu and not args.exp
+        cpu = args.full and world == 1 and not args.no_cpu and not args.exp
         if extras:
             lo5, hi5 = D.shard_range(65536, 0, 8)
             line["secondary"] = [

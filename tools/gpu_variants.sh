@@ -2,7 +2,7 @@
 # bench the headline launch (and 8192 units) with analysis / tuning builds from build/variants:  VARIANTS="a b c" bash tools/gpu_variants.sh
 R=${GRAFT_REPO_ROOT:-$(pwd)}; OUT=$R/gpurun_out/variants; mkdir -p $OUT; cd $R
 export TMPDIR=/tmp
-B="python bench.py --exp --no-cpu --no-extras --steps 15 --warmup 4"
+B="python bench.py --full --exp --no-cpu --no-extras --steps 15 --warmup 4"
 for rep in 1 ${REPS:+2}; do for v in base $VARIANTS; do
   so=$R/build/variants/libmspack_hip_$v.so; [ $v = base ] && so=$R/libmspack_amd/libmspack_hip.so
   for u in ${UNITS:-4096 8192}; do
