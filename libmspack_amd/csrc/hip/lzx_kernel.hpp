@@ -280,6 +280,15 @@ struct LzxState {
 #define LZX_BAD_SOURCE(off_, wp_, written_, ref_, wsize_)                                       \
   ((off_) > (wp_) && ((((off_) > (written_)) && (((off_) - (wp_)) > (ref_))) || (((off_) - (wp_)) > (wsize_))))
 
+// symbols the main table is built over: every index a pretree run can make non-zero (up to 4 past 256 + num_offsets,
+// lzxd.c:159-166), but never beyond LZX_MAINTREE_MAXSYMBOLS = 2576 (lzx.h:38, lzxd.c:96-104): at 2^25 a run from entry
+// 2575 writes 2576..2579, which the reference's table does not count
+__device__ __forceinline__ int lzx_main_build_syms(u32 num_offsets)
+{
+  const int n = 256 + (int) num_offsets + 64;
+  return n < 2576 ? n : 2576;
+}
+
 __device__ __forceinline__ void lzx_reset_state(LzxDec &d, LzxState &s) {      // lzxd.c:257-270
   s.R0 = s.R1 = s.R2 = 1;
   s.header_read = false; s.block_remaining = 0; s.block_type = 0;
@@ -337,7 +346,7 @@ __device__ __forceinline__ bool lzx_block_header(LzxDec &d, LzxState &s, const b
       if (!lzx_read_lens(d, lens, first, last)) return false;
       HT0();
       if (part == 1 && tables) {
-        if (huff_build<LZX_MAIN_P, LZX_MSH, LZX_MTAB_T>(sh->main_len, 256 + (int) s.num_offsets + 64, 12, sh->main_tab, sh->main_sorted,
+        if (huff_build<LZX_MAIN_P, LZX_MSH, LZX_MTAB_T>(sh->main_len, lzx_main_build_syms(s.num_offsets), 12, sh->main_tab, sh->main_sorted,
                                    sh->cnt, d.hr_main, d.lane, false)) {
           d.err = ERR_DECRUNCH; return false;
         }
@@ -2020,7 +2029,7 @@ __device__ __attribute__((noinline)) void lzx_pipe_parse_tail(const mspack_hip_u
     if (tables && btype == 2u) tables = !huff_build<LZX_ALI_P>(sh->ali_len, 8, 7, sh->ali_tab, sh->ali_sorted, sh->cnt, d.hr_ali, lane, false);
     if (tables) {
       u32 nsorted = 0;
-      tables = !huff_build<LZX_MAIN_P, LZX_MSH, LZX_MTAB_T>(sh->main_len, 256 + (int) s.num_offsets + 64, 12, sh->main_tab, sh->main_sorted,
+      tables = !huff_build<LZX_MAIN_P, LZX_MSH, LZX_MTAB_T>(sh->main_len, lzx_main_build_syms(s.num_offsets), 12, sh->main_tab, sh->main_sorted,
                                                             sh->cnt, d.hr_main, lane, false, &nsorted);
       if (tables && published) two_level = rfl(lzx_build_sub(sh, d.hr_main, nsorted, lane) ? 1u : 0u) != 0u;
     }
@@ -2260,7 +2269,7 @@ __device__ u32 lzx_pipe_parse(const mspack_hip_unit &u, const mspack_hip_unit *u
   if (tables && btype == 2u) tables = !huff_build<LZX_ALI_P>(sh->ali_len, 8, 7, sh->ali_tab, sh->ali_sorted, sh->cnt, d.hr_ali, lane, false);
   if (tables) {
     u32 nsorted = 0;
-    tables = !huff_build<LZX_MAIN_P, LZX_MSH, LZX_MTAB_T>(sh->main_len, 256 + (int) s.num_offsets + 64, 12, sh->main_tab, sh->main_sorted,
+    tables = !huff_build<LZX_MAIN_P, LZX_MSH, LZX_MTAB_T>(sh->main_len, lzx_main_build_syms(s.num_offsets), 12, sh->main_tab, sh->main_sorted,
                                                           sh->cnt, d.hr_main, lane, false, &nsorted);
     if (tables && published) two_level = rfl(lzx_build_sub(sh, d.hr_main, nsorted, lane) ? 1u : 0u) != 0u;
   }
@@ -2325,7 +2334,7 @@ __device__ __forceinline__ void lzx_restore_lens(LzxDec &d, const LzxFrameRec *r
 __device__ __forceinline__ void lzx_restore_tables(LzxDec &d, LzxState &s)
 {
   LzxShared *sh = d.sh;
-  huff_build<LZX_MAIN_P, LZX_MSH, LZX_MTAB_T>(sh->main_len, 256 + (int) s.num_offsets + 64, 12, sh->main_tab, sh->main_sorted,
+  huff_build<LZX_MAIN_P, LZX_MSH, LZX_MTAB_T>(sh->main_len, lzx_main_build_syms(s.num_offsets), 12, sh->main_tab, sh->main_sorted,
                                                sh->cnt, d.hr_main, d.lane, false);
   const int r = huff_build<LZX_LEN_P>(sh->len_len, LZX_LEN_SYMS, 12, sh->len_tab, sh->len_sorted, sh->cnt, d.hr_len, d.lane, false);
   s.length_empty = (r == 2);

@@ -31,6 +31,19 @@ def _build_oracle():
     return so
 
 
+def emu_so():
+    """tests/_build/libmspack_emu.so (the kernel sources on the wavefront emulator, tests/emu/), rebuilt whenever a kernel
+    source or the emulator itself is newer than it"""
+    so = os.path.join(ROOT, "tests", "_build", "libmspack_emu.so")
+    srcs = [os.path.join(ROOT, "tests", "emu", f) for f in ("emu_runtime.cpp", "build_emu.sh", "include/hip/hip_runtime.h")]
+    hip = os.path.join(ROOT, "libmspack_amd", "csrc", "hip")
+    srcs += [os.path.join(hip, f) for f in os.listdir(hip) if f.endswith((".hpp", ".hip"))]
+    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
+        subprocess.check_call(["bash", os.path.join(ROOT, "tests", "emu", "build_emu.sh")], stdout=subprocess.DEVNULL,
+                              stderr=subprocess.DEVNULL)
+    return so
+
+
 _oracle = None
 
 

@@ -1,0 +1,155 @@
+"""The hand-built streams of tests/crafted_streams.py without a GPU: the helper's own plaintext against the oracle, the oracle
+against the compiled reference (where it exists), each case's named property, and the whole set through the kernels on the
+wavefront emulator (tests/test_emu_kernels.py builds it)."""
+import os
+import subprocess
+import sys
+
+import pytest
+
+import crafted_streams as CS
+from helpers import emu_so, have_ref, oracle_lzx, oracle_lzxd, oracle_mszip, ref_lzx, ref_lzxd, ref_mszip
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CASES = CS.all_cases()
+
+
+def run_oracle(c):
+    if c.codec == "lzx":
+        e, o, r = oracle_lzx(c.stream, c.out_len, c.wb, c.reset)
+    elif c.codec == "lzxd":
+        e, o, r = oracle_lzxd(c.stream, c.out_len, c.wb, c.ref)
+    else:
+        e, o, r, _ = oracle_mszip(c.stream, c.out_len)
+    return e, o, r
+
+
+def test_case_names_are_unique():
+    assert len({c.name for c in CASES}) == len(CASES) >= 40
+
+
+@pytest.mark.parametrize("c", CASES, ids=[c.name for c in CASES])
+def test_helper_plaintext_equals_the_oracle(built, c):
+    e, o, r = run_oracle(c)
+    assert e == c.err, (e, c.err)
+    if c.plain is not None:
+        assert r.out_len == c.out_len == len(c.plain)
+        assert o == c.plain, "differs at byte %d" % next(k for k in range(len(o)) if o[k] != c.plain[k])
+
+
+@pytest.mark.skipif(not have_ref(), reason="the compiled reference is not built")
+@pytest.mark.parametrize("c", CASES, ids=[c.name for c in CASES])
+def test_oracle_equals_the_reference(built, c):
+    e, o, r = run_oracle(c)
+    if c.codec == "lzx":
+        re, ro, rw = ref_lzx(c.stream, c.out_len, c.wb, c.reset)
+    elif c.codec == "lzxd":
+        re, ro, rw = ref_lzxd(c.stream, c.out_len, c.wb, c.ref)
+    else:
+        re, ro, rw = ref_mszip(c.stream, c.out_len)
+    assert re == e and rw == r.out_len and ro == o[:rw], (re, e, rw, r.out_len)
+
+
+def by_name(name):
+    return next(c for c in CASES if c.name == name)
+
+
+def test_cases_have_the_property_they_name():
+    """measured on what the builders wrote, not declared"""
+    # pretree runs past the end of the table: non-zero lengths at and beyond `last`
+    p = by_name("lzx_pretree_run_past_main_tree_end").props
+    assert (512, 515) in p["overshoot"] and all(p["main_lens"][512:515])
+    assert (256, 258) in by_name("lzx_pretree_run_past_literals_changes_delta_base").props["overshoot"]
+    # window 2^25: entries 2576..2579 non-zero; the code is complete over 2576 symbols and over-subscribed over 2580
+    p = by_name("lzxd_w25_main_tree_run_into_entries_2576_2579").props
+    m = p["main_lens"]
+    assert all(m[2576:2580]) and CS.kraft(m[:2576]) == 65536 < CS.kraft(m[:2580])
+    # length symbol 249 has a code, and 258-byte matches were written (DELTA: and extended lengths)
+    for name in ("lzx_258_byte_match_type1", "lzx_258_byte_match_type2", "lzx_258_byte_matches_over_three_frames",
+                 "lzxd_extended_lengths_and_symbol_249"):
+        p = by_name(name).props
+        assert p["len_lens"][249] and 258 in p["lengths"], name
+    assert max(by_name("lzxd_extended_lengths_and_symbol_249").props["lengths"]) >= 257 + 0x1500
+    # main codes of every length; short codes that fill the table beside lengths that get no code
+    assert by_name("lzx_main_codes_of_every_length_1_to_16").props["max_code_len"] == 16
+    for name, longest in (("8_bit", 8), ("9_bit", 9), ("11_12_bit", 12)):
+        p = by_name("lzx_short_codes_fill_longer_unreachable_" + name).props
+        lens = p["main_lens"][:CS.MAIN_MAX]
+        codes = CS.canon(lens, 12)
+        assert p["max_code_len"] == longest and any(l > 12 and codes[s] is None for s, l in enumerate(lens)), name
+    # fixed-width literals: every literal at 8 bits, nothing else in the tree, no match
+    for name in ("lzx_fixed_8_bit_literals_w21", "lzx_fixed_8_bit_literals_w15"):
+        p = by_name(name).props
+        assert set(p["main_lens"][:256]) == {8} and not any(p["main_lens"][256:]) and "lengths" not in p
+    # blocks of length 0 and odd uncompressed blocks
+    bl = by_name("lzx_zero_length_and_odd_uncompressed_blocks").props["blocks"]
+    assert (1, 0) in bl and (3, 0) in bl and (3, 1001) in bl and (3, 3) in bl
+    # every slot behind the first frame (all of them at 2^15), verbatim and aligned
+    for wb in (15, 17, 21):
+        want = {s for s in range(3, CS.SLOTS[wb]) if CS.BASE[s] - 2 + (1 << CS.EXTRA[s]) - 1 <= CS.FRAME}
+        assert wb != 15 or want == set(range(3, 30))
+        for t in (1, 2):
+            assert by_name("lzx_every_slot_w%d_type%d" % (wb, t)).props["slots"] >= want, (wb, t)
+    # R1 / R2 swaps at the very start of every reset interval, while R0 = R1 = R2 = 1
+    reps = by_name("lzx_repeats_right_after_resets").props["reps"]
+    assert {(f * CS.FRAME + 1, 1, 1) for f in range(3)} <= set(reps)
+    # E8: translation from frame 1 on only; the edges translate; filesize 0 translates nothing
+    assert by_name("lzx_e8_switched_on_by_a_later_block").props["e8_translated"][0] == 0
+    assert all(by_name("lzx_e8_switched_on_by_a_later_block").props["e8_translated"][1:])
+    for name in ("lzx_e8_edges_last_frame_32768", "lzx_e8_edges_last_frame_5000"):
+        assert all(by_name(name).props["e8_translated"])
+    assert not any(by_name("lzx_uncompressed_e8_without_filesize").props["e8_translated"])
+    # the parse waves' second-level table: beyond LZX_SUB_CAP (the fallback) in one case, within it in another
+    p = by_name("lzx_parse_wave_sub_tables_beyond_their_cap").props
+    assert CS.sub_table_total(p["main_lens"][:CS.main_syms(21)]) > CS.LZX_SUB_CAP and p["max_code_len"] == 16
+    assert len(p["blocks"]) == 4 and len(by_name("lzx_parse_wave_sub_tables_beyond_their_cap").tab) == 4
+    p = by_name("lzx_258_byte_matches_over_three_frames").props
+    assert 256 < CS.sub_table_total(p["main_lens"][:CS.main_syms(21)]) <= CS.LZX_SUB_CAP
+    # runs past the end: a zero run; and DELTA at 2^22..2^24, where the entries past the end count in the reference's table
+    assert (CS.main_syms(16), CS.main_syms(16) + 17) in by_name("lzx_zero_run_18_past_main_tree_end").props["ran_past"]
+    for wb in (22, 23, 24):
+        p = by_name("lzxd_w%d_main_tree_run_past_its_end" % wb).props
+        nm = CS.main_syms(wb)
+        assert (nm, nm + 3) in p["overshoot"] and CS.kraft(p["main_lens"][:nm + 3]) == 65536 and (1 << (wb - 1)) in \
+            {o for o, _pos in p["offsets"]}
+    assert by_name("lzx_last_block_longer_than_the_output").props["blocks"] == [(1, 100000)]
+    assert by_name("lzx_e8_in_a_last_frame_of_10_bytes").props["e8_translated"][1] == 0
+    assert by_name("lzx_e8_in_a_last_frame_of_11_bytes").props["e8_translated"][1] == 1
+    # MSZIP
+    p = by_name("mszip_hlit_257_hdist_2").props
+    assert p["max_hlit"] == 257 and p["max_hdist"] == 2
+    p = by_name("mszip_stored_32768_empty_frame_distance_32768_code_284").props
+    assert p["stored_lens"] == [32768, 0] and 257 + 27 in p["len_codes"] and p["max_dist"] == 32768
+    c = by_name("mszip_bytes_before_the_ck_signature")
+    assert [c.stream[t - 1:t] for t in c.tab[1:]] == [b"K", b"Q"]
+    p = by_name("mszip_hlit_288_hdist_32").props
+    assert p["max_hlit"] == 288 and p["max_hdist"] == 32
+    assert by_name("mszip_repeat_code_16_at_position_0").props["repeat_at_0"]
+    assert by_name("mszip_zero_run_18_across_the_literal_distance_boundary").props["runs_across"] == {18}
+    assert by_name("mszip_zero_run_17_across_the_literal_distance_boundary").props["runs_across"] == {17}
+    assert by_name("mszip_repeat_run_overruns_the_tables").props["run_overruns"]
+    p = by_name("mszip_stored_blocks_zero_and_after_huffman_blocks").props
+    assert p["stored_after_huffman"] >= 2 and 0 in p["stored_lens"]
+    p = by_name("mszip_several_blocks_per_frame_distance_32768_code_284").props
+    assert 257 + 27 in p["len_codes"] and p["max_dist"] == 32768
+
+
+EMU_WORKER = r'''
+import sys
+sys.path.insert(0, %r); sys.path.insert(0, %r + "/tests")
+import libmspack_amd as M
+import test_gpu_crafted as G
+assert "emu" in M.HIP_SO
+G.check_all(G.CS.all_cases())
+print("EMU_CRAFTED_OK")
+'''
+
+
+@pytest.mark.skipif(not os.path.exists("/opt/rocm/lib/llvm/bin/clang++"), reason="the emulator build needs ROCm's clang++")
+def test_crafted_streams_on_the_wavefront_emulator(built, tmp_path):
+    so = emu_so()                  # (rebuilt when a kernel source is newer: the run must see the kernels as they are)
+    script = tmp_path / "w.py"
+    script.write_text(EMU_WORKER % (ROOT, ROOT))
+    env = dict(os.environ, MSPACK_HIP_SO=so)
+    p = subprocess.run([sys.executable, str(script)], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=1500)
+    assert p.returncode == 0 and b"EMU_CRAFTED_OK" in p.stdout, p.stdout.decode()[-3000:]

@@ -13,6 +13,8 @@ import sys
 
 import pytest
 
+from helpers import emu_so
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CLANG = "/opt/rocm/lib/llvm/bin/clang++"
 SO = os.path.join(ROOT, "tests", "_build", "libmspack_emu.so")
@@ -73,11 +75,7 @@ print("EMU_OK")
 
 @pytest.mark.skipif(not os.path.exists(CLANG), reason="the emulator build needs ROCm's clang++")
 def test_kernels_on_the_wavefront_emulator(built, tmp_path):
-    srcs = [os.path.join(ROOT, "tests", "emu", f) for f in ("emu_runtime.cpp", "build_emu.sh", "include/hip/hip_runtime.h")]
-    hip = os.path.join(ROOT, "libmspack_amd", "csrc", "hip")
-    srcs += [os.path.join(hip, f) for f in os.listdir(hip) if f.endswith((".hpp", ".hip"))]
-    if not os.path.exists(SO) or any(os.path.getmtime(s) > os.path.getmtime(SO) for s in srcs):
-        subprocess.check_call(["bash", os.path.join(ROOT, "tests", "emu", "build_emu.sh")], stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+    emu_so()
     script = tmp_path / "w.py"
     script.write_text(WORKER % (ROOT, ROOT))
     # (parse waves pause after publishing partial progress: the commit tasks' path for frames still being parsed runs)
