@@ -11,9 +11,7 @@
 
 #define FOLD_FRAME 32768u
 #define FOLD_TAG 0x80000000u                      /* a map entry that waits for a value (LZX: a placeholder R0 / R1 / R2): TAG | which */
-#ifndef FOLD_DEPTH
 #define FOLD_DEPTH 48                             /* gathers in flight in the chain's passes (x 64 lanes; a wave can have 63 memory instructions outstanding) */
-#endif
 
 // A fold task is run by FOLD_WAVES waves (one workgroup) that share the map: what costs time in the chain's passes is the round trip
 // of scattered byte gathers to memory another XCD has just written (~8 us per batch of 48 x 64, measured), and a wave cannot have
@@ -24,18 +22,12 @@
 #define FOLD_WAVES 1u
 #define fold_barrier() __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront")
 #else
-#ifndef FOLD_WAVES
 #define FOLD_WAVES 8u
-#endif
 #define fold_barrier() __syncthreads()
 #endif
 #define FOLD_THREADS (64u * FOLD_WAVES)
 
-#if defined(FOLD_NT_STORES) && !defined(MSPACK_WAVE_EMU)      /* analysis builds: the fold tasks' byte stores marked non-temporal */
-__device__ __forceinline__ void fold_st(u8 *p, u8 v) { __builtin_nontemporal_store(v, p); }
-#else
 __device__ __forceinline__ void fold_st(u8 *p, u8 v) { gst(p, v); }
-#endif
 
 #ifdef FOLD_TRACE      /* analysis builds: ticks (s_memrealtime, 100 MHz) per phase of the fold tasks, summed over all tasks:
                           0 records -> map, 1 jumps, 2 own bytes, 3 wait for the frame two below, 4 early gather + list, 5 wait for

@@ -1,5 +1,5 @@
 // lzx_fold.hpp -- the per-FOLDER chain of LZ77 copies cut down to one gather pass per frame (mspack_lzx_fold, shim.hip).
-// Included by lzx_kernel.hpp (plain LZX build only); reference loops it replaces: lzxd.c:613-646 (the match copy), :565-586 (R0-R2).
+// Included by lzx_pipe_resolve.hpp (plain LZX build, namespace lzxn, only); reference loops it replaces: lzxd.c:613-646 (the match copy), :565-586 (R0-R2).
 //
 // What a folder of ordinary data is bound by: frame f's matches copy bytes of frames < f, so the
 // frames' resolve tasks (lzx_pipe_resolve) run one after the other, and one of them is ~250 us of dependent steps -- which

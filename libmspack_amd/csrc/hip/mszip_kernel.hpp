@@ -485,7 +485,7 @@ __device__ __forceinline__ int zip_run_spec(ZipDec &d)
 // adopts a record only if it was parsed from exactly its bit position, and decodes everything else as before.
 // ---------------------------------------------------------------------------------------------------
 // ---------------------------------------------------------------------------------------------------
-// zip_parse_lanes -- the lane-stretch parser of the LZX path (lzx_kernel.hpp, lzx_parse_emit) for deflate: same
+// zip_parse_lanes -- the lane-stretch parser of the LZX path (lzx_pipe_parse.hpp, lzx_parse_emit) for deflate: same
 // tokens of the current deflate block from the reader's bit position on; returns 1 = the end-of-block symbol was
 // consumed (bit position and the reference's bits_left behind it are in the decoder), 0 = stopped in front of a token
 // this path does not take (scalar reader positioned there), -1 = the block cannot be parsed here.  A pass covers up to
@@ -709,7 +709,7 @@ __device__ __forceinline__ int zip_parse_lanes(ZipDec &d, u8 *const fout, RecWri
 // Hand-off of a block record between waves of ONE launch (mspack_mszip_pipe): what the parse wave stored (literals in the
 // output, match records, record fields) is published with an agent-scope release, a drained store queue and a relaxed
 // status store; the folder's wave polls the status relaxed and then takes one agent-scope acquire (the recipe of the
-// LZX path, lzx_kernel.hpp).  Status: 0 = not yet, 1 = the whole CFDATA block was parsed, 2 = the parse wave gave up.
+// LZX path, lzx_pipe.hpp).  Status: 0 = not yet, 1 = the whole CFDATA block was parsed, 2 = the parse wave gave up.
 __device__ __forceinline__ u32 zip_status_load(const u32 *p) {
   return rfl(__hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
 }
@@ -1006,13 +1006,11 @@ __device__ __forceinline__ int zip_inflate(ZipDec &d, u32 &bytes_output)
       if (huff_build<ZIP_DIST_P>(sh->dist_len, 32, 6, sh->dist_tab, sh->dist_sorted, sh->cnt, d.hr_dist, lane, true)) return ZIP_E_FORMAT;
       u32 cooldown = 0;                                // scalar tokens to take before the next speculative run
       for (;;) {
-#ifndef ZIP_NO_SPEC
         if (cooldown == 0u && !d.flushed) {
           if (zip_run_spec(d)) break;                    // consumed the end-of-block symbol
           cooldown = 8u;
         }
         else if (cooldown) cooldown--;
-#endif
         if (d.bl <= 32) d.refill();
         int sym = d.decode_sym<ZIP_LIT_P>(sh->lit_tab, sh->lit_sorted, d.hr_lit, true);
         if (sym < 0) return sym == -2 ? ERR_READ : ZIP_E_FORMAT;

@@ -478,14 +478,6 @@ __device__ __forceinline__ void qtm_decode_unit(const mspack_hip_unit &u, const 
   }
 #define QTM_MARKS() do { if (MARKS && P >= next_mark) next_mark = qtm_marks_passed(sh, P, 0u, lane); } while (0)
 #define QTM_MARKS_FAIL(below_) do { if (MARKS && next_mark < (below_)) next_mark = qtm_marks_passed(sh, P, (below_), lane); } while (0)
-#ifdef QTM_NO_OUTPUT     /* analysis builds, never shipped: the arithmetic decoder ALONE -- no literal buffer, no
-                            match queue, no copies, nothing written.  What a launch of this build takes is the floor of any split of a
-                            folder into a decoding wave and a writing wave (tools/bench_qtm_config4.py; profiles/round6_qtm.txt) */
-#define QTM_FLUSH() do { lit_n = 0; } while (0)
-#define QTM_COPY(P_, off_, len_) do { } while (0)
-#define QTM_LIT(v_, P_) do { } while (0)
-#define QTM_RESOLVE_DUE(P_) do { } while (0)
-#else
 #define QTM_LIT(v_, P_) do { lit_buf = wrl(lit_buf, (v_), lit_n); lit_pos = wrl(lit_pos, (P_), lit_n); if (++lit_n == WAVE) QTM_FLUSH(); } while (0)
 #define QTM_RESOLVE_DUE(P_) do { if (spq_due(Q, (P_))) { QTM_FLUSH(); spq_resolve(sh->spq, Q, out, (P_), false, lane, out_len); } } while (0)
 #define QTM_FLUSH()                                                                           \
@@ -504,7 +496,6 @@ __device__ __forceinline__ void qtm_decode_unit(const mspack_hip_unit &u, const 
       Q.Pf = (P_) + (len_);                                                                   \
     }                                                                                         \
   } while (0)
-#endif
 
   // The decode loop (qtmd.c:283-470).  Far from the end of the input -- a token reads fewer than 96 bytes -- no read can fail:
   // the lean decoder (FAST).  Round 5: the lean and the exact decoder are TWO copies of the whole loop, one run after the
@@ -514,9 +505,6 @@ __device__ __forceinline__ void qtm_decode_unit(const mspack_hip_unit &u, const 
   // from the state), so the exact copy just goes on.
   // (Two loops in a row inside the frame loop -- the first attempt -- made the compiler treat the coder's wave-uniform
   // state as divergent: the whole chain moved to the vector unit.  Checked in the ISA: build/isa/qtm_r5.txt.)
-#ifndef QTM_SPLIT_LOOPS
-#define QTM_SPLIT_LOOPS 1          /* 0: one loop, lean or exact decided per token (rounds 3-4) */
-#endif
 #define QTM_FAR_FROM_END() (d.w.origin + d.w.wi * 4u + 96u <= d.w.in_len)
 #define QTM_DECODE_LOOP(LEAVE_WHEN_NEAR_END_, TOKEN_, switch_)                                        \
   while ((long long)(o_end - o_ptr) < need) {                                                         \
@@ -586,13 +574,8 @@ __device__ __forceinline__ void qtm_decode_unit(const mspack_hip_unit &u, const 
   }
   {
     bool to_exact = false;
-#if QTM_SPLIT_LOOPS
     QTM_DECODE_LOOP(true, qtm_token<true>(d, M, moff, mlen), to_exact)
     if (to_exact) { bool never = false; QTM_DECODE_LOOP(false, qtm_token<false>(d, M, moff, mlen), never) (void) never; }
-#else
-    QTM_DECODE_LOOP(false, (QTM_FAR_FROM_END() ? qtm_token<true>(d, M, moff, mlen) : qtm_token<false>(d, M, moff, mlen)), to_exact)
-    (void) to_exact;
-#endif
   }
 #undef QTM_DECODE_LOOP
 #undef QTM_FAR_FROM_END

@@ -12,26 +12,36 @@
 #include "wave_common.hpp"
 #include "spec_queue.hpp"
 #include "fold_common.hpp"
-// lzx_kernel.hpp is compiled twice: plain LZX (CAB, CHM) and LZX DELTA (OAB) -- see its header
+// ---- the LZX decoder: the same role headers compiled under three configurations, each in its own namespace ----
+// lzxn: plain LZX (CAB folders, CHM sections).  mspack_decode_lzx (unit decoder + E8 pass), the resolve tasks of mspack_lzx_pipe,
+// mspack_lzx_fold; the frame record's layout everywhere in this file.
 namespace lzxn {
 #include "lzx_kernel.hpp"
+#include "lzx_run.hpp"
+#include "lzx_run_plain.hpp"
+#include "lzx_pipe.hpp"
+#include "lzx_pipe_resolve.hpp"
+#include "lzx_unit.hpp"
 }
+// lzxd: LZX DELTA (OAB blocks).  mspack_decode_lzxd (unit decoder + E8 pass).
 #define LZX_DELTA 1
 namespace lzxd {
 #include "lzx_kernel.hpp"
+#include "lzx_run.hpp"
+#include "lzx_run_delta.hpp"
+#include "lzx_unit.hpp"
 }
 #undef LZX_DELTA
+// lzxp: the parse tasks of mspack_lzx_pipe (no match queue, no token queue, an 8-bit main table: lzx_kernel.hpp).
 #define LZX_PARSE_ONLY 1
-#ifndef LZX_LIT_RING
 #define LZX_LIT_RING 1024u      /* bytes of literals a parse wave stages in LDS: they leave as whole 16-byte rows (a power of two) */
-#endif
-#ifndef LZX_STAGE_WORDS
 #define LZX_STAGE_WORDS 768u    /* 3 KiB of a frame's input per pass + the 1 KiB literal ring: the pipe's 10 KiB LDS block (16 waves per CU).
                                    Measured (profiles/round4_ring_variants.txt): 4 KiB stage + 2 KiB ring at 12 waves per CU 3.00 / 5.87 ms
                                    (4096 / 8192 intervals), 2 KiB + 2 KiB at 16 waves 3.06 / 5.92, this 2.89 / 5.58 */
-#endif
 namespace lzxp {
 #include "lzx_kernel.hpp"
+#include "lzx_pipe.hpp"
+#include "lzx_pipe_parse.hpp"
 }
 #undef LZX_PARSE_ONLY
 static_assert(sizeof(lzxp::LzxFrameRec) == sizeof(lzxn::LzxFrameRec), "one record layout");
@@ -56,7 +66,7 @@ __device__ __forceinline__ bool pick_unit(const mspack_hip_unit *units, const u3
 //   u32    frame_unit[n]  per frame slot: the unit it belongs to when a parse wave should take it, else ~0
 //   u32    hdr[256]       per launch (up to 32 concurrent ones) 8 words: [0] = most, [1] = fewest frames of a unit with a
 //                         frame table, [2] = ticket counter of mspack_lzx_pipe, [4] = chunks handed out of the launch's pool
-//   LzxFrameRec recs[n]   what the parse wave of that frame assumed and found (lzx_kernel.hpp), incl. its chunk list
+//   LzxFrameRec recs[n]   what the parse wave of that frame assumed and found (lzx_pipe.hpp), incl. its chunk list
 //   uint2  pool[n * REC_POOL_PER_SLOT * REC_CHUNK]   the frames' match records (wave_common.hpp: RecPool): 48 KiB per slot
 //                         on average instead of round 3's 128 KiB worst case per slot; a launch uses the part that
 //                         belongs to its slot range
@@ -199,7 +209,7 @@ void mspack_decode_lzx(const mspack_hip_unit *units, const u32 *order, u32 n_uni
 // are alike, a wave that took a long first frame takes a short second frame (launch order is longest first in every
 // section), and a unit of many frames has the parse of frame f + k running beside the copies of frame f.
 // Hand-off: payload by plain stores, agent-scope release, relaxed status store; the reader polls the status relaxed, then
-// one agent-scope acquire (lzx_kernel.hpp).  The first frame that is not a complete regular one ends its unit's chain and
+// one agent-scope acquire (lzx_pipe.hpp).  The first frame that is not a complete regular one ends its unit's chain and
 // says where serial decoding resumes; mspack_decode_lzx (launched behind the pipe) finishes every unit.
 // ---------------------------------------------------------------------------------------------------
 // ---- few units of many frames: the folder's chain as one gather pass per frame (lzx_fold.hpp) ----
@@ -207,19 +217,13 @@ void mspack_decode_lzx(const mspack_hip_unit *units, const u32 *order, u32 n_uni
 // some unit is too long for the map's positions): policy 0 never, 1 when it pays, 2 whenever it can (tests).  Where it pays: the
 // resolve tasks of lzx_pipe_resolve fill 16 waves per CU and cost ~0.25 ms per frame ON a unit's chain; the fold tasks fill ONE wave
 // per CU (128 KiB of LDS each) and leave ~15 us per frame on the chain -- so: long units, and too few of them to fill the chip.
-#ifndef LZX_FOLD_MIN_FRAMES
 #define LZX_FOLD_MIN_FRAMES 4u
-#endif
-#ifndef LZX_FOLD_MAX_UNITS
 #define LZX_FOLD_MAX_UNITS 128u
-#endif
 // (measured, tools/fold_policy_sweep.py, profiles/round6_fold_policy.txt: n folders of f frames, LZX, resolve tasks / fold tasks, ms:
 //  4 x 256: 68.5 / 13.4; 16 x 64: 20.9 / 8.3; 32 x 32: 12.2 / 6.5; 64 x 16: 8.1 / 6.0; 128 x 8: 6.2 / 5.8; 128 x 4: 2.7 / 3.1;
 //  256 x 8: 8.3 / 9.0 -- so: at most 128 units, and eight frames in the longest, or at least four when every frame gets a task of its
 //  own at once; MSZIP folders gain at 128 x 4 too (2.6 / 2.2): four blocks)
-#ifndef LZX_FOLD_LONG_FRAMES
 #define LZX_FOLD_LONG_FRAMES 8u
-#endif
 __device__ __forceinline__ bool lzx_fold_on(const u32 *ctl, const u32 policy, const u32 n_slots, const bool mszip)
 {
   if (policy == 0u || rfl(ctl[6]) != 0u || rfl(ctl[0]) == 0u) return false;
@@ -291,7 +295,7 @@ __device__ __attribute__((noinline)) void lzx_pipe_task_tail(const mspack_hip_un
   RecPool rp; rp.base = pool; rp.head = pool_head; rp.cap = pool_chunks;
   lzxp::lzx_pipe_parse_tail(up, f, in_arena, out_arena, (lzxp::LzxFrameRec *) &recs[rfl(up->frame_base)], rp, sh);
 }
-// (a frame's block header read ahead of the header chain, while the frame below is not that far: lzx_kernel.hpp)
+// (a frame's block header read ahead of the header chain, while the frame below is not that far: lzx_pipe_parse.hpp)
 __device__ __attribute__((noinline)) u32 lzx_pipe_task_spec(const mspack_hip_unit *up, const u32 f, const u8 *in_arena, const lzxn::LzxFrameRec *recs,
                                                             lzxp::LzxShared *sh)
 {
@@ -311,7 +315,7 @@ __device__ __attribute__((noinline)) void lzx_pipe_task_resolve(const mspack_hip
   const mspack_hip_unit u = *up;
   lzxn::lzx_pipe_resolve(u, f, out_arena, &recs[u.frame_base], toks, rl, merged);
 }
-// (the same where the launch has wave slots to spare: the frame's records taken up while it is parsed -- lzx_kernel.hpp)
+// (the same where the launch has wave slots to spare: the frame's records taken up while it is parsed -- lzx_pipe_resolve.hpp)
 __device__ __attribute__((noinline)) void lzx_pipe_task_resolve_stream(const mspack_hip_unit *up, const u32 f, u8 *out_arena, lzxn::LzxFrameRec *recs,
                                                                        uint2 *toks, lzxn::LzxResolveLds *rl)
 {
@@ -322,9 +326,7 @@ __device__ __attribute__((noinline)) void lzx_pipe_task_resolve_stream(const msp
 #ifdef LZX_PIPE_TRACE      /* analysis builds: one line per ticket = start, end (s_memrealtime, 100 MHz), task, time waited */
 __device__ unsigned long long g_pipe_trace[4 << 16];
 #endif
-#ifndef LZX_PIPE_WAVES_PER_EU
 #define LZX_PIPE_WAVES_PER_EU 4
-#endif
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(LZX_PIPE_WAVES_PER_EU)))
 void mspack_lzx_pipe(const mspack_hip_unit *units, const u32 *order, u32 n_units, u32 slot_lo, u32 n_slots,
                      const u8 *in_arena, u8 *out_arena, mspack_hip_result *results, int32_t *frame_meta,
@@ -406,11 +408,7 @@ void mspack_lzx_pipe(const mspack_hip_unit *units, const u32 *order, u32 n_units
     if (lane == 0) lzxn::g_pipe_wait[blockIdx.x & 0xFFFFu] = 0;
 #endif
     if (do_parse) {
-#ifndef LZX_NO_SPEC_HEADER
       const u32 spec = lzx_pipe_task_spec(up, f, in_arena, recs, &sh.p);
-#else
-      const u32 spec = 0u;
-#endif
       if (lzx_pipe_task_parse(up, f, in_arena, out_arena, recs, toks, &ctl[4], pool_chunks, &sh.p, spec, stream))
         lzx_pipe_task_tail(up, f, in_arena, out_arena, recs, toks, &ctl[4], pool_chunks, &sh.p);
       __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");      // the resolver reuses the LDS

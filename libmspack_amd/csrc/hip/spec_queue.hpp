@@ -20,13 +20,9 @@
 #pragma once
 #include "wave_common.hpp"
 
-#ifndef SPQ_CAP
 #define SPQ_CAP 160
-#endif
 #define SPQ_RING 2048u            /* positions the start-flag ring covers (one BIT per position) */
-#ifndef SPQ_SPAN
 #define SPQ_SPAN 512u             /* resolve when this many output bytes are pending */
-#endif
 #define SPQ_GROUP 4               /* 64-byte chunks resolved per memory round trip */
 
 #ifdef LZX_MARKS        /* analysis builds: static instruction counts between marks (tools/count_isa.py) */
@@ -192,9 +188,7 @@ __device__ __forceinline__ void spq_resolve(SpecQueueLds &l, SpecQueue &q, u8 *c
 // stores.  That is what long stretches of zeros and of repeated records look like after LZ77 with a maximal match length
 // of 257 / 258 (lzxd.c:588, mszipd.c:62-66) -- the reference's own large-files.test (a 64-byte line repeated for 2 GiB:
 // ~127 matches of 257 bytes at offset 64 per frame) is the pure case.  
-#ifndef SPQ_RUN_MIN
 #define SPQ_RUN_MIN 512u            /* a batch takes the run path when it spans at least this many bytes */
-#endif
 // which matches of a batch (lanes 0..n-1, in position order) END a run that is worth the fill path: bit l set = the run that ends
 // with lane l spans at least SPQ_RUN_MIN bytes; seg_first = the lane the run of a lane's match begins with.  A run is a maximal
 // stretch of matches that follow each other without a gap and share one offset (one match alone -- at most 258 bytes -- never
@@ -203,9 +197,6 @@ __device__ __forceinline__ u64 spq_find_runs(const bool ism, const u32 n, const 
                                              u32 &seg_first)
 {
   seg_first = lane;
-#ifdef SPQ_NO_RUNS                 /* analysis builds: everything through the queue */
-  return 0ull;
-#endif
   // (a run of >= SPQ_RUN_MIN bytes is made of LONG matches -- encoders take the longest match there is --: without two of at
   // least 64 bytes the batch is ordinary data and pays three instructions here, not twenty)
   { const u64 longm = ballot(ism && olen >= 64u); if (!(longm & (longm - 1ull))) return 0ull; }
@@ -227,9 +218,6 @@ __device__ __forceinline__ void spq_fill_run(u8 *const out, const u32 s, const u
                                              const u32 clip = 0xFFFFFFFFu)
 {
   const u8 *const src = out + (s - off);
-#if defined(SPQ_RUN_TRACE) && defined(MSPACK_WAVE_EMU)     /* emulator analysis builds: which runs took this path */
-  if (lane == 0) fprintf(stderr, "spq_fill_run: [%u, %u) period %u\n", s, e, off);
-#endif
   if (off <= 64u) {
     // the whole period sits in one register across the wave: byte (b - s) mod off comes from a lane, not from memory
     u32 k = lane % off;                                  // (one division per run)

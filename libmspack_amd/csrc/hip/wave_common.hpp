@@ -32,44 +32,18 @@ typedef uint64_t u64;
 // Accesses to the arenas and the work scratch on the hot paths go through gld / gst.  Pointers that live in structs or
 // reach a real (non-inlined) device function have lost their address space, so these are FLAT instructions.  Casting them
 // to address space 1 (global_load / global_store) was measured on the headline launch (round 3, same box, same session):
-// 3.38 ms flat vs 3.49 ms global, 6.43 vs 6.77 ms at 8192 units -- the explicit form is SLOWER here, so it is off.
-// streaming stores of the parse waves (literals, match records): analysis builds can mark them non-temporal
-#if defined(MSPACK_NT_STORES) && !defined(MSPACK_WAVE_EMU)
-template <typename T> __device__ __forceinline__ void gst_stream(T *p, T v) { __builtin_nontemporal_store(v, p); }
-__device__ __forceinline__ void gst_stream(uint2 *p, uint2 v) { __builtin_nontemporal_store(v.x, &p->x); __builtin_nontemporal_store(v.y, &p->y); }
-#else
-#define gst_stream gst
-#endif
-#if !defined(MSPACK_GLOBAL_ACCESS) || defined(MSPACK_WAVE_EMU)
+// 3.38 ms flat vs 3.49 ms global, 6.43 vs 6.77 ms at 8192 units -- the explicit form is SLOWER here
+// (profiles/round3_abc_loops_access.txt), so these stay plain dereferences.
 template <typename T> __device__ __forceinline__ T gld(const T *p) { return *p; }
 template <typename T> __device__ __forceinline__ void gst(T *p, T v) { *p = v; }
-#else
-template <typename T> __device__ __forceinline__ T gld(const T *p) { return *(const __attribute__((address_space(1))) T *) p; }
-template <typename T> __device__ __forceinline__ void gst(T *p, T v) { *(__attribute__((address_space(1))) T *) p = v; }
-typedef unsigned int gv2u_ __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ uint2 gld(const uint2 *p) { const gv2u_ t = *(const __attribute__((address_space(1))) gv2u_ *) p; return make_uint2(t.x, t.y); }
-__device__ __forceinline__ void gst(uint2 *p, uint2 v) { gv2u_ t; t.x = v.x; t.y = v.y; *(__attribute__((address_space(1))) gv2u_ *) p = t; }
-#endif
-// write-through forms (`sc1`: the bytes go to memory at once and the line is dropped from the XCD's L2) for payload that only
-// another workgroup reads: an agent-scope release (buffer_wbl2) writes back EVERY dirty line of the XCD's L2, so what a wave leaves
-// dirty there is written out -- partially filled -- by whichever of the XCD's 512 waves publishes next (MI355X guide: stores of each
-// flavour; profiles/round6_sc1_stores.txt).  MSPACK_SC1_RECORDS: the parse waves' match records; MSPACK_SC1_ROWS: their literal rows.
-#if defined(MSPACK_SC1_RECORDS) && !defined(MSPACK_WAVE_EMU)
-__device__ __forceinline__ void gst_record(uint2 *p, uint2 v) {
-  __hip_atomic_store((unsigned long long *) p, ((unsigned long long) v.y << 32) | v.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-#else
-__device__ __forceinline__ void gst_record(uint2 *p, uint2 v) { gst_stream(p, v); }
-#endif
-#if defined(MSPACK_SC1_ROWS) && !defined(MSPACK_WAVE_EMU)
-typedef unsigned int gv4u_ __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void gst_row(uint4 *p, uint4 v) {
-  gv4u_ t; t.x = v.x; t.y = v.y; t.z = v.z; t.w = v.w;
-  asm volatile("flat_store_dwordx4 %0, %1 sc1" :: "v"(p), "v"(t) : "memory");
-}
-#else
-#define gst_row(p_, v_) gst((p_), (v_))
-#endif
+// The parse waves' stores, named for what they carry: single literals and MSZIP records (gst_stream), LZX match records
+// (gst_record), 16-byte literal rows (gst_row).  All three are plain stores.  Non-temporal stores for literals and records
+// were far slower (profiles/round3_nt_stores.txt).  Write-through (`sc1`) forms were tried because an agent-scope release
+// (buffer_wbl2) writes back EVERY dirty line of the XCD's L2, partially filled ones too: sc1 records cost 311 MB more write
+// traffic (the L2 does merge them), sc1 rows change nothing (profiles/round6_sc1_stores.txt).
+template <typename T> __device__ __forceinline__ void gst_stream(T *p, T v) { gst(p, v); }
+__device__ __forceinline__ void gst_record(uint2 *p, uint2 v) { gst(p, v); }
+__device__ __forceinline__ void gst_row(uint4 *p, uint4 v) { gst(p, v); }
 
 __device__ __forceinline__ u32 rfl(u32 v) { return (u32) __builtin_amdgcn_readfirstlane((int) v); }
 __device__ __forceinline__ u32 rdl(u32 v, u32 l) { return (u32) __builtin_amdgcn_readlane((int) v, (int) l); }

@@ -23,7 +23,7 @@ for _i in range(291):
 MAIN_MAX = 256 + 290 * 8          # LZX_MAINTREE_MAXSYMBOLS: the reference builds every main table over this many symbols
 LEN_MAX = 250                     # LZX_LENGTH_MAXSYMBOLS
 ERR_OK, ERR_READ, ERR_DECRUNCH = 0, 3, 11
-LZX_SUB_CAP = (528 + 720 + 16 + 250 + 70 + 8) // 2    # lzx_kernel.hpp: the parse waves' second-level room (windows <= 2^21)
+LZX_SUB_CAP = (528 + 720 + 16 + 250 + 70 + 8) // 2    # lzx_pipe_parse.hpp: the parse waves' second-level room (windows <= 2^21)
 
 
 # ---- canonical codes --------------------------------------------------------------------------------------------------
