@@ -46,6 +46,7 @@ extern "C" {
                                        it compares with the CFDATA headers (cabd.c:1411-1417) when the results are back        */
 
 #define MSPACK_HIP_MASK_FRAME_TABLES 0x80000000u   /* mspack_hip_decode_batch_device(kind_mask): see there */
+#define MSPACK_HIP_MASK_CRC32        0x40000000u   /* mspack_hip_decode_batch_device(kind_mask): units may carry MSPACK_HIP_UF_CRC32 */
 
 /* result flags */
 #define MSPACK_HIP_F_E8_APPLIED     1u  /* >=1 frame went through the E8 translation (lzxd.c:706-736) */
@@ -103,6 +104,16 @@ extern "C" {
                                            CFDATA block, cabd.c:1322-1324): ERR_READ at once, without the
                                            two fabricated zero bytes of a clean EOF (readbits.h:194-208) */
 
+#define MSPACK_HIP_UF_CRC32       128u  /* every decoding kind (1 to 6): result.in_used carries a digest of the first result.out_len bytes of
+                                           the unit's output region instead of the diagnostic byte count -- CRC-32, reflected polynomial
+                                           0xEDB88320, register started at 0xFFFFFFFF and NOT inverted at the end (the OAB block check,
+                                           crc32.h / oabd.c:88-100): zlib's crc32(bytes) ^ 0xFFFFFFFF; 0xFFFFFFFF for out_len == 0.  Written
+                                           for failing units too, over what they produced.  Every other result field and every output
+                                           byte are those of a run without the flag.  Computed on the device, behind the decode, where the
+                                           bytes lie (aligned 16-byte reads: up to 15 bytes below out_off that share its row are read and
+                                           ignored).  Rejected on MSPACK_HIP_KIND_XORSUM units (the host entry points return an error).
+                                           Ask mspack_hip_features() & MSPACK_HIP_FEAT_CRC32 before setting it on a library of unknown age */
+
 typedef struct mspack_hip_unit {
   uint64_t in_off;       /* byte offset of the unit's compressed bytes in the input arena          */
   uint64_t out_off;      /* byte offset of the unit's output in the output arena                   */
@@ -131,7 +142,7 @@ typedef struct mspack_hip_result {
   int32_t  err;          /* MSPACK_ERR_* exactly as the reference's decompress call returns        */
   uint32_t flags;        /* MSPACK_HIP_F_*                                                         */
   uint32_t out_len;      /* bytes produced (handed to sys->write in the reference)                 */
-  uint32_t in_used;      /* compressed bytes the unit pulled (diagnostic)                          */
+  uint32_t in_used;      /* compressed bytes the unit pulled (diagnostic); MSPACK_HIP_UF_CRC32: the digest */
   uint32_t good_len;     /* bytes decoded before the failing point (== out_len when err == 0).  A
                             request that ends at or before good_len succeeds in the reference too
                             (it decodes no further than asked): LZX counts whole frames, MSZIP
@@ -152,6 +163,10 @@ int  mspack_hip_device_count(void);
 int  mspack_hip_set_device(int device);
 const char *mspack_hip_version(void);
 const char *mspack_hip_last_error(void);
+/* capability word: what this provider of the batch ABI can do beyond version 0.3 (a driver that may be linked against
+ * another provider declares the function weak and treats its absence as 0) */
+#define MSPACK_HIP_FEAT_CRC32 1u        /* MSPACK_HIP_UF_CRC32 / MSPACK_HIP_MASK_CRC32 */
+unsigned mspack_hip_features(void);
 
 /* ---- device-resident batch decode (the hot path proper) ---------------------------------------
  * All pointers are DEVICE pointers valid on the current device.  `stream` is a hipStream_t (NULL =
@@ -173,7 +188,9 @@ const char *mspack_hip_last_error(void);
  *   kind_mask  : bit k set = units of kind k may be present; MSPACK_HIP_MASK_FRAME_TABLES set = LZX units may
  *                carry frame tables (MSPACK_HIP_UF_FRAME_TABLE): only then are the parse wavefronts launched.
  *                Was: bit k set = units of kind k may be present (one kernel per codec is launched;
- *                units of other kinds are skipped); 0 = all three codecs
+ *                units of other kinds are skipped); 0 = all three codecs.
+ *                MSPACK_HIP_MASK_CRC32 set = units may carry MSPACK_HIP_UF_CRC32: only then is the digest pass launched
+ *                behind the codecs (two more launches; flagged units of a kind the mask leaves out get no digest worth reading)
  * MSZIP units need 32768 bytes of slack after out_len in their output region.
  * Units with a frame / block table: the parse wavefronts store literals into the unit's output region (for MSZIP incl. its
  * slack) before the unit is known to decode; the first result.out_len bytes are the decoded data, the rest of the region

@@ -17,6 +17,9 @@ CORPUS_SO = os.path.join(HERE, "libmspack_corpus.so")
 KIND_MSZIP, KIND_QUANTUM, KIND_LZX, KIND_LZX_DELTA, KIND_LZSS, KIND_KWAJ_LZH = 1, 2, 3, 4, 5, 6
 F_E8_APPLIED, F_LOOKAHEAD_READ, F_INTEL_HEADER, F_BLOCK_OPEN, F_FRAMES_ADOPTED = 1, 2, 4, 16, 32
 UF_MSZIP_REPAIR = 1
+UF_CRC32 = 128               # result.in_used = CRC-32 (OAB flavour: zlib.crc32(out[:out_len]) ^ 0xFFFFFFFF) of the decoded bytes
+MASK_CRC32 = 0x40000000      # decode_batch_device(kind_mask): launch the digest pass
+FEAT_CRC32 = 1
 ERR_OK, ERR_ARGS, ERR_OPEN, ERR_READ, ERR_WRITE, ERR_SEEK, ERR_NOMEMORY, ERR_SIGNATURE, \
     ERR_DATAFORMAT, ERR_CHECKSUM, ERR_CRUNCH, ERR_DECRUNCH = range(12)
 
@@ -63,6 +66,8 @@ def lib():
         L.mspack_hip_job_wait_unit.argtypes = [vp, sz]
         L.mspack_hip_job_end.argtypes = [vp]
         L.mspack_hip_release.restype = None
+        L.mspack_hip_features.restype = C.c_uint
+        L.mspack_hip_features.argtypes = []
         _lib = L
     return _lib
 
@@ -74,13 +79,18 @@ EXPORTED_SYMBOLS = [
     "mspack_hip_decode_batch_to_device", "mspack_hip_release",
     "mspack_hip_set_default_devices", "mspack_hip_default_devices", "mspack_hip_set_cache_mb", "mspack_hip_cache_mb",
     "mspack_hip_host_path_stats", "mspack_hip_pin", "mspack_hip_unpin", "mspack_hip_stage_alloc", "mspack_hip_stage_free",
-    "mspack_hip_decode_batch_begin", "mspack_hip_job_wait_unit", "mspack_hip_job_end",
+    "mspack_hip_decode_batch_begin", "mspack_hip_job_wait_unit", "mspack_hip_job_end", "mspack_hip_features",
 ]
 
 
 def _check(rc, what):
     if rc != 0:
         raise MspackHipError("%s failed (%d): %s" % (what, rc, lib().mspack_hip_last_error().decode()))
+
+
+def features():
+    """capability word of the loaded library (FEAT_*): mspack_hip_features()"""
+    return int(lib().mspack_hip_features())
 
 
 def frames_of(units):

@@ -48,6 +48,7 @@ static_assert(sizeof(lzxp::LzxFrameRec) == sizeof(lzxn::LzxFrameRec), "one recor
 #include "mszip_kernel.hpp"
 #include "qtm_kernel.hpp"
 #include "lzss_kernel.hpp"
+#include "crc32_kernel.hpp"
 
 // One wavefront == one workgroup == one unit.  blockIdx -> unit through the optional launch order
 // (longest unit first keeps the tail of the batch short).  One kernel per codec (their register
@@ -598,6 +599,30 @@ void mspack_xorsum(const mspack_hip_unit *units, const u32 *order, u32 n_units, 
   }
 }
 
+// MSPACK_HIP_UF_CRC32 (crc32_kernel.hpp): the digest pass over a compact list of flagged units, launched behind the codec
+// kernels that wrote results[] -- stream order is the only ordering.  First the start value's share, one unit per lane ...
+__global__ __launch_bounds__(64)
+void mspack_crc32_init(const mspack_hip_unit *units, const u32 *order, u32 n_units, mspack_hip_result *results)
+{
+  const u32 j = blockIdx.x * 64u + threadIdx.x;
+  if (j >= n_units) return;
+  const u32 ui = order ? order[j] : j;
+  const mspack_hip_unit u = units[ui];
+  if (crc_unit_wanted(u)) crc_init_unit(u, &results[ui]);
+}
+// ... then the bytes: segs_y wavefronts per unit, wave y takes the unit's segments y, y + segs_y, ...
+__global__ __launch_bounds__(64)
+void mspack_crc32(const mspack_hip_unit *units, const u32 *order, u32 n_units, u32 segs_y, const u8 *out_arena, mspack_hip_result *results)
+{
+  __shared__ CrcShared sh;
+  const u32 j = blockIdx.x / segs_y, y = blockIdx.x % segs_y;
+  if (j >= n_units) return;
+  const u32 ui = rfl(order ? order[j] : j);
+  const mspack_hip_unit u = units[ui];
+  if (!crc_unit_wanted(u)) return;
+  crc_unit_segments(u, out_arena, &results[ui], y, segs_y, &sh);
+}
+
 // ---------------------------------------------------------------------------------------------------
 // Host side of the C ABI.
 // ---------------------------------------------------------------------------------------------------
@@ -776,6 +801,21 @@ static hipError_t launch_kind(unsigned kind, const mspack_hip_unit *d_units, con
   }
   return hipSuccess;
 }
+// the digest pass over units order[0..n): at most max_len bytes per unit.  Enough waves per unit for the longest one, as long as
+// the grid stays near 64 Ki blocks (a block whose unit has no segment for it leaves at once)
+static hipError_t launch_crc32(const mspack_hip_unit *d_units, const uint32_t *d_order, size_t n, uint64_t max_len, void *d_out,
+                               mspack_hip_result *d_results, hipStream_t st)
+{
+  if (n == 0) return hipSuccess;
+#ifdef MSPACK_HOST_CHECK      /* tests/hostcheck runs no kernel and its stand-in for a launch computes no digest */
+  return hipErrorInvalidValue;
+#endif
+  const uint64_t max_seg = std::max<uint64_t>(1, (max_len + 15u + CRC_SEG - 1u) / CRC_SEG);
+  const u32 segs_y = (u32) std::min<uint64_t>(max_seg, std::max<uint64_t>(1, 65536u / n));
+  LK(launch(mspack_crc32_init, dim3((unsigned)((n + 63) / 64)), dim3(64), st, d_units, d_order, (u32) n, d_results));
+  LK(launch(mspack_crc32, dim3((unsigned)(n * segs_y)), dim3(64), st, d_units, d_order, (u32) n, segs_y, (const u8 *) d_out, d_results));
+  return hipSuccess;
+}
 #undef LK
 
 extern "C" {
@@ -813,8 +853,9 @@ int mspack_hip_debug_pipe_phases(unsigned long long *out32) {
   return hipMemcpyToSymbol(HIP_SYMBOL(lzxn::g_pipe_phase), z, sizeof(z)) == hipSuccess ? 0 : -1;
 }
 #endif
-const char *mspack_hip_version(void) { return "mspack-hip 0.3 (gfx950; LZX/LZX-DELTA/Quantum/MSZIP batch decode)"; }
+const char *mspack_hip_version(void) { return "mspack-hip 0.4 (gfx950; LZX/LZX-DELTA/Quantum/MSZIP batch decode)"; }
 const char *mspack_hip_last_error(void) { return g_err; }
+unsigned mspack_hip_features(void) { return MSPACK_HIP_FEAT_CRC32; }
 
 int mspack_hip_device_count(void) {
   int n = 0;
@@ -832,7 +873,7 @@ int mspack_hip_decode_batch_device(const mspack_hip_unit *d_units, const uint32_
                                    void *d_frame_scratch, size_t n_frames_total, unsigned kind_mask,
                                    void *stream)
 {
-  (void) in_bytes; (void) out_bytes;
+  (void) in_bytes;
   if (n_units == 0) return 0;
   if ((kind_mask & 0xFEu) == 0) kind_mask |= 0xFEu;     // bit k = units of kind k may be present
   // the caller's unit table lives on the device, so the kinds cannot be compacted here: every codec in the
@@ -842,6 +883,9 @@ int mspack_hip_decode_batch_device(const mspack_hip_unit *d_units, const uint32_
     if (kind_mask & (1u << k))
       CK(launch_kind(k, d_units, d_order, n_units, d_in, d_out, d_results, d_frame_scratch, n_frames_total, 0, n_frames_total,
                      (hipStream_t) stream, (kind_mask & MSPACK_HIP_MASK_FRAME_TABLES) != 0u));
+  // (the flags are on the device too: the digest pass is launched only when the caller says some unit may carry MSPACK_HIP_UF_CRC32)
+  if (kind_mask & MSPACK_HIP_MASK_CRC32)
+    CK(launch_crc32(d_units, d_order, n_units, std::min<uint64_t>(out_bytes, 0xFFFFFFFFu), d_out, d_results, (hipStream_t) stream));
   return 0;
 }
 
@@ -935,6 +979,7 @@ struct Chunk {
   uint64_t in_lo, in_hi, out_lo, out_hi;
   size_t order_off[8], order_n[8];      // per kind: slice of the order array
   size_t fm_lo, fm_n;
+  size_t crc_off, crc_n; uint64_t crc_max;      // the chunk's units that carry MSPACK_HIP_UF_CRC32: slice of the order array, the longest
   bool has_ftab;                        // some LZX unit of the chunk carries a frame table
 };
 
@@ -1048,7 +1093,7 @@ static int pipeline_on_current_device(int dev, mspack_hip_unit *units, const uin
   std::vector<mspack_hip_unit> local(n_sel);
   bool monotone = !per_unit_back;
   uint64_t in_lo = ~0ull, in_hi = 0, out_lo = ~0ull, out_hi = 0, prev_hi = 0, in_sum = 0;
-  size_t n_frames = 0, n_rec_slots = 0;
+  size_t n_frames = 0, n_rec_slots = 0, n_crc = 0;      // n_crc: units that want a digest (MSPACK_HIP_UF_CRC32)
   for (size_t i = 0; i < n_sel; i++) {
     mspack_hip_unit &u = local[i];
     u = units[idx[i]];
@@ -1056,6 +1101,7 @@ static int pipeline_on_current_device(int dev, mspack_hip_unit *units, const uin
         !(u.kind == MSPACK_HIP_KIND_QUANTUM && (u.flags & MSPACK_HIP_UF_QTM_MARKS))) u.ref_len = 0;
     if (u.kind > MSPACK_HIP_KIND_XORSUM) { snprintf(errbuf, errcap, "unit %u: unknown kind %u", idx[i], u.kind); return -1; }
     if (u.kind == MSPACK_HIP_KIND_XORSUM) {                // reads its input, owns no output
+      if (u.flags & MSPACK_HIP_UF_CRC32) { snprintf(errbuf, errcap, "unit %u: a checksum unit decodes nothing to take a CRC-32 of", idx[i]); return -1; }
       if (u.out_len) { snprintf(errbuf, errcap, "unit %u: a checksum unit has no output", idx[i]); return -1; }
       if (u.in_off + u.in_len > in_bytes) { snprintf(errbuf, errcap, "unit outside arena"); return -1; }
       in_lo = std::min<uint64_t>(in_lo, u.in_off); in_hi = std::max<uint64_t>(in_hi, u.in_off + u.in_len);
@@ -1079,6 +1125,7 @@ static int pipeline_on_current_device(int dev, mspack_hip_unit *units, const uin
     }
     out_lo = std::min(out_lo, lo); out_hi = std::max(out_hi, hi);
     in_sum += u.in_len;
+    if ((u.flags & MSPACK_HIP_UF_CRC32) && u.kind != 0) n_crc++;
   }
   // frame slots: the units that carry a usable frame / block table first -- only their slots hold records and tokens
   for (int pass = 0; pass < 2; pass++) {
@@ -1180,7 +1227,7 @@ static int pipeline_on_current_device(int dev, mspack_hip_unit *units, const uin
       }
     }
     // per chunk: spans, per-kind launch lists (longest compressed unit first: the slowest chain starts first)
-    std::vector<uint32_t> order(n_sel);
+    std::vector<uint32_t> order(n_sel + n_crc);
     size_t op = 0;
     uint64_t ci_prev_hi = out_lo == ~0ull ? 0 : out_lo;
     for (Chunk &c : chunks) {
@@ -1210,6 +1257,15 @@ static int pipeline_on_current_device(int dev, mspack_hip_unit *units, const uin
         std::stable_sort(order.begin() + c.order_off[k], order.begin() + op, [&](uint32_t x, uint32_t y) {
           return local[x].in_len + (local[x].out_len >> 2) > local[y].in_len + (local[y].out_len >> 2); });
       }
+      // the digest pass's list (launched behind the codecs): the chunk's flagged units, in arena order
+      c.crc_off = op; c.crc_max = 0;
+      if (n_crc)
+        for (size_t i = c.a; i < c.b; i++)
+          if ((local[i].flags & MSPACK_HIP_UF_CRC32) && local[i].kind != 0 && local[i].kind != MSPACK_HIP_KIND_XORSUM) {
+            order[op++] = (uint32_t) i;
+            c.crc_max = std::max<uint64_t>(c.crc_max, local[i].out_len);
+          }
+      c.crc_n = op - c.crc_off;
     }
     if (pg) {
       std::lock_guard<std::mutex> lk(pg->mu);
@@ -1227,7 +1283,7 @@ static int pipeline_on_current_device(int dev, mspack_hip_unit *units, const uin
     TRY(grow(cx.d_in, in_span + 64, false));
     if (!dev_out) TRY(grow(cx.d_out, out_span + 64, false));
     TRY(grow(cx.d_units, n_sel * sizeof(mspack_hip_unit), false));
-    TRY(grow(cx.d_order, n_sel * sizeof(uint32_t), false));
+    TRY(grow(cx.d_order, (n_sel + n_crc) * sizeof(uint32_t), false));
     TRY(grow(cx.d_res, n_sel * sizeof(mspack_hip_result), false));
     TRY(grow(cx.d_fm, lzx_scratch(nullptr, n_frames, n_rec_slots).bytes, false));
     // (pinned staging: the results, and room for the few output bytes that lie outside every page-locked range -- below)
@@ -1258,7 +1314,7 @@ static int pipeline_on_current_device(int dev, mspack_hip_unit *units, const uin
     const size_t n_comp = (host_out && !has_qtm) ? std::min<size_t>(few, (size_t) cx.n_compute) : (size_t) cx.n_compute;
     hipStream_t st_in = cx.st[0], st_out = one ? cx.st[0] : cx.st[1];
     TRY(hipMemcpyAsync(d_units, local.data(), n_sel * sizeof(mspack_hip_unit), hipMemcpyHostToDevice, st_in));
-    TRY(hipMemcpyAsync(d_order, order.data(), n_sel * sizeof(uint32_t), hipMemcpyHostToDevice, st_in));
+    TRY(hipMemcpyAsync(d_order, order.data(), (n_sel + n_crc) * sizeof(uint32_t), hipMemcpyHostToDevice, st_in));
     TRY(hipMemsetAsync(cx.d_fm.p, 0, (n_frames + 1) * sizeof(int32_t), st_in));
     TRY(hipMemsetAsync(d_in + in_span, 0, 64, st_in));
     // The copies back are issued by a second thread.  A copy into PAGEABLE memory holds its calling thread and (measured,
@@ -1411,6 +1467,7 @@ static int pipeline_on_current_device(int dev, mspack_hip_unit *units, const uin
       for (unsigned k = 1; k <= MSPACK_HIP_KIND_XORSUM; k++)
         TRY(launch_kind(k, d_units, d_order + c.order_off[k], c.order_n[k], d_in, d_out, d_res, cx.d_fm.p, n_frames, c.fm_lo, c.fm_n, st,
                         c.has_ftab, (unsigned) ci, n_rec_slots, one));
+      if (c.crc_n) TRY(launch_crc32(d_units, d_order + c.crc_off, c.crc_n, c.crc_max, d_out, d_res, st));      // behind every codec's store of its results
       TRY(hipMemcpyAsync(h_res + c.a, d_res + c.a, (c.b - c.a) * sizeof(mspack_hip_result), hipMemcpyDeviceToHost, st));
       if (!one) { TRY(hipEventRecord(cx.ev_done[ci], st)); issued.store(ci + 1, std::memory_order_release); }
     }

@@ -34,6 +34,10 @@ struct oab_blk {
   size_t unit;                        /* index into the unit table (compressed blocks)                */
 };
 
+/* The provider of the batch ABI this driver is linked with may be older than MSPACK_HIP_UF_CRC32 (or a CPU stand-in that never
+ * learnt it): the capability call is a weak reference, and a provider that does not have it is asked for nothing new. */
+extern unsigned mspack_hip_features(void) __attribute__((weak));
+
 static unsigned int crc_table[256];
 static void crc_init(void) {
   unsigned int i, k;
@@ -76,6 +80,8 @@ static int oab_run(struct oabd_p *self, const char *input, const char *base, con
   mspack_hip_result *res = NULL;
   int ret = MSPACK_ERR_OK, tail_err = MSPACK_ERR_OK;
   const unsigned int hsize = patch ? 0x1c : 0x10;
+  /* the blocks' CRCs on the device, behind their decode (result.in_used), where the provider can; else crc_update below */
+  const int dev_crc = mspack_hip_features && (mspack_hip_features() & MSPACK_HIP_FEAT_CRC32);
 
   crc_init();
   if (!(infh = sys->open(sys, input, MSPACK_SYS_OPEN_READ))) return MSPACK_ERR_OPEN;
@@ -166,6 +172,7 @@ static int oab_run(struct oabd_p *self, const char *input, const char *base, con
       u->out_off = out_bytes; u->out_len = b->dsize;
       u->kind = MSPACK_HIP_KIND_LZX_DELTA; u->window_bits = (uint8_t) b->window_bits;
       u->ref_len = b->ssize;
+      if (dev_crc) u->flags |= MSPACK_HIP_UF_CRC32;
       out_bytes += b->dsize;
     }
     if (!(out_arena = (unsigned char *) sys->alloc(sys, out_bytes + 64))) { ret = MSPACK_ERR_NOMEMORY; goto out; }
@@ -228,7 +235,8 @@ static int oab_run(struct oabd_p *self, const char *input, const char *base, con
       if (write_slice(sys, outfh, out_arena + u->out_off, n)) { ret = MSPACK_ERR_WRITE; break; }
       if (err) { ret = err; break; }
       if (b->in_have < b->csize) { ret = MSPACK_ERR_READ; break; }            /* the padding skip fails */
-      if (crc_update(0xffffffffu, out_arena + u->out_off, n) != b->crc) { ret = MSPACK_ERR_CHECKSUM; break; }
+      /* (the device's digest covers r->out_len bytes: a block that produced more than it may write is summed here) */
+      if ((dev_crc && b->dsize && n == r->out_len ? r->in_used : crc_update(0xffffffffu, out_arena + u->out_off, n)) != b->crc) { ret = MSPACK_ERR_CHECKSUM; break; }
     }
   }
   if (!ret) ret = tail_err;
