@@ -146,7 +146,8 @@ typedef struct mspack_hip_result {
   uint32_t good_len;     /* bytes decoded before the failing point (== out_len when err == 0).  A
                             request that ends at or before good_len succeeds in the reference too
                             (it decodes no further than asked): LZX counts whole frames, MSZIP
-                            whole blocks, Quantum the position of the failing symbol              */
+                            whole blocks, Quantum the position at which the failing token starts
+                            (a match: every request that ends inside it fails with it)            */
   uint32_t in_next;      /* LZX: input byte offset (from in_off) right after the 16-bit realignment that
                             follows the last completely decoded non-empty frame (lzxd.c:695-697), i.e.
                             where a decoder that keeps going reads the next frame from.  The CHM driver

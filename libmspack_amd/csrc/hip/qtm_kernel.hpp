@@ -556,7 +556,8 @@ __device__ __forceinline__ void qtm_decode_unit(const mspack_hip_unit &u, const 
     /* a match that overshot the frame fails every request that needed that match: `good` still       \
      * holds the position where it started */                                                         \
     if (frame_todo > QTM_FRAME) { err = ERR_DECRUNCH; break; }         /* qtmd.c:424 */               \
-    good = P ? P - 1u : 0u;       /* errors in the frame-end handling hit the request ending here */  \
+    /* errors in the frame-end handling hit every request that needed the pass's last token: `good`  \
+     * holds the position where that token started (a match: every request that ends inside it) */    \
     if (frame_todo == 0u) {                                                                           \
       int n = d.rbl & 7;                                               /* qtmd.c:432 */               \
       if (n) { d.need(n); d.bb <<= n; d.bl -= n; d.rbl -= n; }                                        \
@@ -605,6 +606,8 @@ __device__ __forceinline__ void qtm_decode_unit(const mspack_hip_unit &u, const 
   if (err == ERR_OK) good = written;
   if (lane == 0) {
     res->err = err; res->flags = 0; res->out_len = written; res->good_len = good; res->in_next = 0;
-    res->in_used = d.w.origin + ((d.cons_bits() + (u32) d.rbl) >> 3);
+    // (a READ_BYTES that fails has still taken the byte in front of the end, if there was one: the reference's i_ptr stands
+    // at the end of the input, fabricated bytes included -- qtmd.c:27-36, readbits.h:184-214)
+    res->in_used = err == ERR_READ ? d.w.in_len + d.w.eofs : d.w.origin + ((d.cons_bits() + (u32) d.rbl) >> 3);
   }
 }

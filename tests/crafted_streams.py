@@ -10,6 +10,7 @@ is a small LZ77 expansion of the tokens here, E8 translation included, and None 
 case() objects: name, codec ('lzx' | 'lzxd' | 'mszip'), stream (bytes, zero-padded), out_len, wb, reset, ref (DELTA
 reference data), tab (frame table: LZX offsets at every 16-bit re-alignment / MSZIP 'CK' offsets), plain (bytes or None),
 err (the error code the decoders must report), props (what the case is about, checked by the CPU test)."""
+import bisect
 import random
 
 FRAME = 32768
@@ -482,6 +483,381 @@ class Deflate:
     def stream(self, pad=8):
         self.byte_align()
         return bytes(self.out) + b"\0" * pad
+
+
+# ---- Quantum ----------------------------------------------------------------------------------------------------------
+QPB, QPE, QLB, QLE = [], [], [], []                  # position / length slots: base and extra bits (qtmd.c:52-64)
+_b = 0
+for _i in range(42):
+    QPE.append(0 if _i < 2 else (_i - 2) >> 1); QPB.append(_b); _b += 1 << QPE[-1]
+_b = 0
+for _i in range(26):
+    QLE.append(0 if _i < 2 else (_i - 2) >> 2); QLB.append(_b); _b += 1 << QLE[-1]
+QLB.append(254); QLE.append(0)
+SPQ_CAP, SPQ_RING = 160, 2048                        # spec_queue.hpp: matches the queue holds, bytes its start flags cover
+
+
+def qtm_pos_slot(v):
+    return bisect.bisect_right(QPB, v) - 1
+
+
+def qtm_len_slot(v):
+    return bisect.bisect_right(QLB, v) - 1
+
+
+class QtmModel:
+    """one adaptive model with the reference's update rule (qtmd.c:125-182); counts its rescales and re-sorts"""
+
+    def __init__(self, start, n):
+        self.n = n
+        self.sym = list(range(start, start + n + 1))
+        self.cf = [n - i for i in range(n + 1)]
+        self.shiftsleft = 4
+        self.rescales = self.resorts = self.tied_resorts = self.moving_resorts = 0
+        self.used = set()
+        self.where = {s: i for i, s in enumerate(self.sym[:n])}
+
+    def bump(self, i):
+        cf = self.cf
+        cf[:i + 1] = [x + 8 for x in cf[:i + 1]]
+        if cf[0] > 3800:
+            self.update()
+
+    def update(self):
+        cf, sym, n = self.cf, self.sym, self.n
+        self.rescales += 1
+        self.shiftsleft -= 1
+        if self.shiftsleft:
+            for i in range(n - 1, -1, -1):
+                cf[i] >>= 1
+                if cf[i] <= cf[i + 1]:
+                    cf[i] = cf[i + 1] + 1
+            return
+        self.shiftsleft = 50
+        self.resorts += 1
+        f = [((cf[i] - cf[i + 1]) + 1) >> 1 for i in range(n)]
+        if len(set(f)) < n:
+            self.tied_resorts += 1
+        before = sym[:n]
+        for i in range(n - 1):
+            for j in range(i + 1, n):
+                if f[i] < f[j]:
+                    f[i], f[j] = f[j], f[i]
+                    sym[i], sym[j] = sym[j], sym[i]
+        if sym[:n] != before:
+            self.moving_resorts += 1
+        for i in range(n - 1, -1, -1):
+            cf[i] = f[i] + cf[i + 1]
+        self.where = {s: i for i, s in enumerate(sym[:n])}
+
+
+def qtm_models(wb):
+    """the nine models by name (qtm.h:49-77, qtmd.c:242-251)"""
+    m = {"lit%d" % k: QtmModel(64 * k, 64) for k in range(4)}
+    m.update({"4": QtmModel(0, min(24, 2 * wb)), "5": QtmModel(0, min(36, 2 * wb)), "6": QtmModel(0, 2 * wb),
+              "6len": QtmModel(0, 27), "sel": QtmModel(0, 7)})
+    return m
+
+
+class Qtm:
+    """A Quantum stream writer: the nine models, the 16-bit carry-less coder with pending bits, raw bits spliced in at
+    arithmetic bit 16 + shifts (the decoder's C register runs 16 bits ahead), frames with their trailers.  It expands its own
+    tokens -- a circular window of zeros, byte-serial copies -- and keeps the reference's bits_left (`rbl`) as the reads of
+    qtmd.c would leave it, so that a case can say how many 16-bit refills one symbol took."""
+
+    def __init__(self, wb, auto=True):
+        self.wb, self.wsize, self.auto = wb, 1 << wb, auto
+        self.M = qtm_models(wb)
+        self.out = bytearray()
+        self.win, self.wpos = bytearray(self.wsize), 0
+        self.plain = bytearray()
+        self.frame_todo = FRAME
+        self.fail = False
+        self.rbl = self.consumed = 0          # the reference's bits_left; bits its reads have taken out of the buffer
+        self.props = {"sels": set(), "slots": {4: {}, 5: {}, 6: {}}, "len_slots": {}, "max_n": 0, "max_mu": 0, "max_k": 0,
+                      "max_raw": 0, "crossing": [], "before_start": [], "junk": [], "align": [], "double_refills": 0,
+                      "lengths": set()}
+        self._open = False
+
+    @property
+    def pos(self):
+        return len(self.plain)
+
+    # ---- the coder ----
+    def _begin(self):
+        if not self._open:
+            self.abits, self.raws = [], []
+            self.H, self.L, self.pending, self.shifts = 0xFFFF, 0, 0, 0
+            self._open = True
+            self._take(16)                            # the frame's 16 bits of C (qtmd.c:292-295)
+
+    def _take(self, n, one_at_a_time=True):
+        """the reference's bits_left over a read of n bits"""
+        self.consumed += n
+        if one_at_a_time:                             # READ_BITS: refill while short
+            while self.rbl < n:
+                self.rbl += 16
+            self.rbl -= n
+        else:                                         # READ_MANY_BITS (readbits.h:143-153)
+            while n > 0:
+                if self.rbl <= 16:
+                    self.rbl += 16
+                run = min(self.rbl, n)
+                self.rbl -= run
+                n -= run
+
+    def interval(self, model, i):
+        rng = self.H - self.L + 1
+        tot = model.cf[0]
+        return (self.L + model.cf[i] * rng // tot - 1) & 0xFFFF, (self.L + model.cf[i + 1] * rng // tot) & 0xFFFF
+
+    @staticmethod
+    def renorm_counts(H, L):
+        """(n, mu): plain shifts and underflow steps the interval H, L takes (qtmd.c:107-122)"""
+        n = mu = 0
+        while True:
+            if (L ^ H) & 0x8000:
+                if (L & 0x4000) and not (H & 0x4000):
+                    L &= 0x3FFF; H |= 0x4000; mu += 1
+                else:
+                    return n, mu
+            else:
+                n += 1
+            L = (L << 1) & 0xFFFF; H = ((H << 1) | 1) & 0xFFFF
+
+    def _code(self, name, sym):
+        self._begin()
+        model = self.M[name]
+        i = model.where[sym]
+        model.used.add(sym)
+        H, L = self.interval(model, i)
+        model.bump(i)
+        n = mu = 0
+        ab = self.abits
+        while True:
+            if (L ^ H) & 0x8000:
+                if (L & 0x4000) and not (H & 0x4000):
+                    self.pending += 1; L &= 0x3FFF; H |= 0x4000; mu += 1
+                else:
+                    break
+            else:
+                b = L >> 15
+                ab.append(b)
+                if self.pending:
+                    ab.extend([b ^ 1] * self.pending); self.pending = 0
+                n += 1
+            L = (L << 1) & 0xFFFF; H = ((H << 1) | 1) & 0xFFFF
+        self.shifts += n + mu
+        self.H, self.L = H, L
+        p = self.props
+        k = n + mu
+        if n > p["max_n"]: p["max_n"] = n
+        if mu > p["max_mu"]: p["max_mu"] = mu
+        if k > p["max_k"]: p["max_k"] = k
+        if k > self.rbl + 16:
+            p["double_refills"] += 1
+        self._take(k)
+
+    def _raw(self, v, nbits):
+        if nbits:
+            assert 0 <= v < 1 << nbits
+            self.raws.append((self.shifts, v, nbits))
+            self.props["max_raw"] = max(self.props["max_raw"], nbits)
+            self._take(nbits, one_at_a_time=False)
+
+    # ---- tokens ----
+    def _emit(self, data):
+        n = min(len(data), self.wsize - self.wpos)
+        self.win[self.wpos:self.wpos + n] = data[:n]
+        self.win[:len(data) - n] = data[n:]
+        self.wpos = (self.wpos + len(data)) & (self.wsize - 1)
+        self.plain += data
+        self.frame_todo -= len(data)
+        if self.frame_todo < 0:
+            self.fail = True                          # (a match beyond the frame's end: qtmd.c:424)
+        if self.auto and self.frame_todo == 0:
+            self.end_frame()
+
+    def lit(self, c):
+        assert self.frame_todo > 0
+        self.props["sels"].add(c >> 6)
+        self._code("sel", c >> 6); self._code("lit%d" % (c >> 6), c)
+        self._emit(bytes((c,)))
+
+    def lits(self, data):
+        for c in data:
+            self.lit(c)
+
+    def match(self, off, length, sel=None):
+        assert self.frame_todo > 0 and 1 <= off <= self.wsize and 3 <= length <= 259
+        if sel is None:
+            sel = 4 if length == 3 else 5 if length == 4 else 6
+        assert (sel, length) in ((4, 3), (5, 4)) or (sel == 6 and length >= 5)
+        p = self.props
+        p["sels"].add(sel); p["lengths"].add(length)
+        self._code("sel", sel)
+        if sel == 6:
+            ls = qtm_len_slot(length - 5)
+            self._code("6len", ls); self._raw(length - 5 - QLB[ls], QLE[ls])
+            p["len_slots"].setdefault(ls, set()).add(length - 5 - QLB[ls])
+        s = qtm_pos_slot(off - 1)
+        assert s < self.M[str(sel)].n, "offset %d has no slot in model %d at this window" % (off, sel)
+        self._code(str(sel), s); self._raw(off - 1 - QPB[s], QPE[s])
+        p["slots"][sel].setdefault(s, set()).add(off - 1 - QPB[s])
+        if off > self.pos:
+            p["before_start"].append(self.pos)
+        if self.wpos + length > self.wsize:
+            p["crossing"].append(self.pos)
+        # the expansion: byte-serial in the circular window
+        mask = self.wsize - 1
+        s0 = (self.wpos - off) & mask
+        if s0 + length <= self.wsize and self.wpos + length <= self.wsize and off < self.wsize:
+            pat = bytes(self.win[s0:s0 + min(off, length)])
+            data = (pat * (length // len(pat) + 1))[:length]
+        else:
+            w = bytearray(self.win)
+            d = bytearray()
+            wp = self.wpos
+            for _ in range(length):
+                b = w[(wp - off) & mask]
+                w[wp] = b; d.append(b); wp = (wp + 1) & mask
+            data = bytes(d)
+        self._emit(data)
+
+    def room(self, n):
+        """literals up to the frame's end if fewer than n bytes of it are left"""
+        if self.frame_todo < n:
+            self.lits(bytes((self.pos * 37 + 11) & 0xFF for _ in range(self.frame_todo)))
+
+    def grow(self, to, period=251):
+        """cheap output up to position `to`: matches of up to 259 bytes at offset `period`, a literal that depends on the
+        position behind every third one (so that a copy from the wrong place shows)"""
+        k = 0
+        while self.pos < to:
+            n = min(259, to - self.pos, self.frame_todo)
+            if n >= 5 and self.pos >= period:
+                self.match(period, n)
+            else:
+                self.lit((self.pos * 2654435761 >> 7) & 0xFF)
+            k += 1
+            if k % 3 == 0 and self.pos < to:
+                self.lit((self.pos * 2654435761 >> 11) & 0xFF)
+
+    # ---- frames ----
+    def _flush_coder(self):
+        """end the arithmetic code, cover the decoder's 16-bit look-ahead, splice the raw bits in, pad to a byte"""
+        if not self._open:
+            return
+        self.pending += 1
+        b = 1 if self.L >= 0x4000 else 0
+        self.abits.append(b); self.abits.extend([b ^ 1] * self.pending); self.pending = 0
+        while len(self.abits) < 16 + self.shifts:
+            self.abits.append(0)
+        bits, ri, ab, raws = [], 0, self.abits, self.raws
+        for i in range(len(ab) + 1):
+            while ri < len(raws) and 16 + raws[ri][0] == i:
+                _at, v, nb = raws[ri]
+                bits.extend((v >> k) & 1 for k in range(nb - 1, -1, -1))
+                ri += 1
+            if i < len(ab):
+                bits.append(ab[i])
+        assert ri == len(raws)
+        self.props["align"].append(len(bits) & 7)
+        bits.extend([0] * (-len(bits) & 7))
+        self.out += int("".join(map(str, bits)), 2).to_bytes(len(bits) // 8, "big")
+        self._open = False
+
+    def end_frame(self, junk=b"", trailer=True):
+        """the frame's payload, `junk` bytes (cabinets carry 0 to 4 null bytes here, qtmd.c:434-437), the 0xFF trailer"""
+        assert self.frame_todo <= 0 and 0xFF not in junk
+        self._flush_coder()
+        self.consumed += self.rbl & 7
+        self.rbl -= self.rbl & 7
+        self.out += junk + (b"\xff" if trailer else b"")
+        for _ in range(len(junk) + 1):
+            self._take(8)
+        self.props["junk"].append(bytes(junk))
+        self.frame_todo = FRAME
+
+    def stream(self):
+        """the stream, and in props["pulled"] the bytes the reference's reader has pulled when the last token is through.  An
+        open last frame gets the 0xFF that cabd puts behind every block, and zeros up to 2 bytes short of what was pulled:
+        READ_MANY_BITS refills whenever 16 bits or fewer are left, needed or not, and the two bytes a clean end of input
+        fabricates (readbits.h:194-208) cover the rest"""
+        p = self.props
+        if self._open:
+            self._flush_coder()
+            self.out += b"\xff"
+            self.out += bytes(max(0, (self.consumed + self.rbl) // 8 - 2 - len(self.out)))
+        p["pulled"] = (self.consumed + self.rbl) // 8
+        for name, m in self.M.items():
+            p["model_" + name] = dict(rescales=m.rescales, resorts=m.resorts, tied_resorts=m.tied_resorts,
+                                      moving_resorts=m.moving_resorts, used=set(m.used), n=m.n)
+        return bytes(self.out)
+
+
+def qtm_read_maxima(stream, out_len, wb):
+    """the largest n, mu and k = n + mu a symbol takes when the Python model DECODES a valid stream (one that some other
+    encoder wrote) -> (n, mu, k, the decoded bytes)"""
+    M = qtm_models(wb)
+    bits = int.from_bytes(stream + b"\0" * 8, "big")
+    total = 8 * (len(stream) + 8)
+    st = {"p": 0}
+
+    def rd(n):
+        st["p"] += n
+        return (bits >> (total - st["p"])) & ((1 << n) - 1) if n else 0
+    out = bytearray()
+    mx = [0, 0, 0]
+    todo = FRAME
+    while len(out) < out_len:
+        H, L, C = 0xFFFF, 0, rd(16)
+
+        def sym(name):
+            nonlocal H, L, C
+            m = M[name]
+            rng = ((H - L) & 0xFFFF) + 1
+            symf = (((C - L + 1) * m.cf[0] - 1) // rng) & 0xFFFF
+            i = 1
+            while i < m.n and m.cf[i] > symf:
+                i += 1
+            s = m.sym[i - 1]
+            rng = H - L + 1
+            H, L = (L + m.cf[i - 1] * rng // m.cf[0] - 1) & 0xFFFF, (L + m.cf[i] * rng // m.cf[0]) & 0xFFFF
+            m.bump(i - 1)
+            n = mu = 0
+            while True:
+                if (L ^ H) & 0x8000:
+                    if (L & 0x4000) and not (H & 0x4000):
+                        C ^= 0x4000; L &= 0x3FFF; H |= 0x4000; mu += 1
+                    else:
+                        break
+                else:
+                    n += 1
+                L = (L << 1) & 0xFFFF; H = ((H << 1) | 1) & 0xFFFF; C = ((C << 1) | rd(1)) & 0xFFFF
+            mx[0] = max(mx[0], n); mx[1] = max(mx[1], mu); mx[2] = max(mx[2], n + mu)
+            return s
+        while todo > 0 and len(out) < out_len:
+            sel = sym("sel")
+            if sel < 4:
+                out.append(sym("lit%d" % sel)); todo -= 1
+                continue
+            length = 3 if sel == 4 else 4
+            if sel == 6:
+                ls = sym("6len")
+                length = QLB[ls] + rd(QLE[ls]) + 5
+            s = sym(str(sel))
+            off = QPB[s] + rd(QPE[s]) + 1
+            for _ in range(length):
+                out.append(out[-off] if off <= len(out) else 0)
+            todo -= length
+        if todo == 0:
+            st["p"] += -st["p"] & 7
+            while rd(8) != 0xFF:
+                pass
+            todo = FRAME
+    return mx[0], mx[1], mx[2], bytes(out[:out_len])
+
 
 
 # ---- the cases --------------------------------------------------------------------------------------------------------
@@ -1064,5 +1440,243 @@ def mszip_cases():
     return C
 
 
+def _qtm_case(name, q, out_len=None, err=ERR_OK, stream=None):
+    st = q.stream() if stream is None else stream
+    out_len = q.pos if out_len is None else out_len
+    if err == ERR_OK:
+        assert not q.fail, name
+    return Case(name, "qtm", st, out_len, q.wb, plain=bytes(q.plain[:out_len]) if err == ERR_OK else None, err=err, props=q.props)
+
+
+def _qlit(k):
+    return (k * 2654435761 >> 9) & 0xFF
+
+
+QTM_PATTERNS = ("hammered", "alternating", "round_robin", "geometric")
+
+
+def _pattern(kind, n, count, seed, rate=0.7):
+    """`count` indices below n"""
+    if kind == "hammered":
+        return [n // 3] * count
+    if kind == "alternating":
+        return [(1, n - 1)[k & 1] for k in range(count)]
+    if kind == "round_robin":
+        return [k % n for k in range(count)]
+    r = random.Random(seed)
+    return [min(n - 1, int(r.expovariate(rate))) for _ in range(count)]
+
+
+QTM_MODEL_SYMBOLS = 14200          # of one model: 54 rescales (the second re-sort) take 4 * ~470 + 50 * ~240 symbols
+
+
+def qtm_search_extremes(steps=6000):
+    """a stream that drives the renormalisation to its extremes.  A symbol's interval is narrowest -- about range / total, 4 to 5
+    wide at best -- when its frequency is 1 and its model's total is near 3800: 14 leading bits in common (n = 14) where it
+    lies inside one aligned group of four, and n + mu = 14 with a long underflow run (mu) where it straddles a multiple of a
+    high power of two.  So: one literal is hammered until its model's total is above 3700, then the entries still at their
+    smallest frequency are coded once each; then a search: the hammered literal (and a second one, to move L and H about) is
+    coded until some literal of that model would take a longer n, mu or n + mu -- or two 16-bit refills -- than any symbol so
+    far, and that one is coded.  -> the writer, the position behind the first symbol that took two refills (None: none did)"""
+    q = Qtm(16)
+    q.lits(b"\x41" * 500)
+    for k in range(64, 128):
+        while q.M["lit1"].cf[0] <= 3700:
+            q.lit(0x41)
+        q.lit(k)
+    first_double = None
+    ms, ml, p = q.M["sel"], q.M["lit1"], q.props
+    r = random.Random(16)
+    for _ in range(steps):
+        pick = None
+        if ml.cf[0] > 3000:
+            H, L = q.interval(ms, ms.where[1])
+            n, mu = q.renorm_counts(H, L)
+            rbl = q.rbl
+            while rbl < n + mu:
+                rbl += 16
+            rbl -= n + mu
+            for _k in range(n + mu):
+                L = (L << 1) & 0x7FFF if _k >= n else (L << 1) & 0xFFFF
+                H = ((H << 1) | 1) & 0xFFFF if _k < n else 0x8000 | ((H << 1) | 1) & 0x7FFF
+            keep = q.H, q.L
+            q.H, q.L = H, L
+            for i in range(64):
+                h2, l2 = q.interval(ml, i)
+                if h2 - l2 > 64:
+                    continue
+                n2, mu2 = q.renorm_counts(h2, l2)
+                if n2 > p["max_n"] or mu2 > p["max_mu"] or n2 + mu2 > p["max_k"] or n2 + mu2 > rbl + 16:
+                    pick = ml.sym[i]
+                    break
+            q.H, q.L = keep
+        q.room(2)
+        q.lit(pick if pick is not None else 0x41 if r.random() < 0.9 else 0x42)
+        if first_double is None and p["double_refills"]:
+            first_double = q.pos
+    return q, first_double
+
+
+def qtm_cases():
+    C = []
+    rnd = random.Random(4711)
+
+    # ---- 1. the source lies before the first decoded byte (the `off > P` loop of qtm_copy; zeros, this project's convention) ----
+    for P in (0, 1, 3):
+        q = Qtm(10); q.lits(b"xyz"[:P]); q.match(P + 7, 20); q.lits(b"end")
+        C.append(_qtm_case("qtm_offset_beyond_the_start_at_P%d" % P, q))
+    q = Qtm(10); q.match(1024, 30); q.lits(b"end"); q.match(1024, 9)
+    C.append(_qtm_case("qtm_offset_of_the_whole_window_at_P0", q))
+    q = Qtm(12); q.lits(b"abcde"); q.match(8, 7); q.lits(b"-"); q.match(40, 100); q.lits(b"end")
+    C.append(_qtm_case("qtm_match_reads_zeros_then_real_bytes", q))
+    q = Qtm(12); q.lits(b"ab"); q.match(5, 40); q.lits(b"cd"); q.match(50, 259); q.match(400, 259, sel=6)
+    C.append(_qtm_case("qtm_periodic_match_from_before_the_start", q))
+    q = Qtm(21); q.lits(b"qtm")
+    for sel, ln in ((4, 3), (5, 4), (6, 5)):
+        for sl in range(q.M[str(sel)].n):
+            for v in (0, (1 << QPE[sl]) - 1):
+                q.match(QPB[sl] + v + 1, ln if sel != 6 or sl % 5 else 70)
+            q.lit(_qlit(sl))
+    C.append(_qtm_case("qtm_w21_every_slot_of_models_4_5_6_from_before_the_start", q))
+
+    # ---- 2. every position slot of every position model, both ends of its extra bits, with a real source; every length slot ----
+    for wb in (10, 12, 17, 18, 21):
+        q = Qtm(wb)
+        q.lits(bytes(_qlit(k) for k in range(260)))
+        todo = sorted((QPB[sl] + v + 1, sel) for sel in (4, 5, 6) for sl in range(q.M[str(sel)].n)
+                      for v in (0, (1 << QPE[sl]) - 1))
+        for off, sel in todo:
+            if off > q.pos:
+                q.grow(off)
+            q.room(8)
+            q.match(off, (3, 4, 7)[sel - 4])
+            q.lit(_qlit(off))
+        assert q.pos > q.wsize
+        if wb == 12:
+            for sl in range(27):
+                for v in (0, (1 << QLE[sl]) - 1):
+                    q.room(259); q.match(300 + sl, QLB[sl] + v + 5); q.lit(_qlit(v))
+        if wb == 21:
+            q.grow(q.wsize + 5000); q.room(20); q.match(q.wsize, 11); q.lits(b"tail")
+        C.append(_qtm_case("qtm_every_slot_w%d" % wb, q))
+
+    # ---- 3. short periods ----
+    q = Qtm(16); q.lits(bytes(rnd.getrandbits(8) for _ in range(64)))
+    for off in range(1, 64):
+        for ln in (64, 65, 128, 259):
+            q.room(260); q.match(off, ln); q.lit(_qlit(off * 4 + ln))
+    q.room(260); q.match(64, 259)
+    for n in (3, 4, 5, 63, 64, 65, 100, 259):
+        q.room(260); q.lits(bytes(rnd.getrandbits(8) for _ in range(3))); q.match(n, n)
+    C.append(_qtm_case("qtm_short_periods_1_to_64", q))
+
+    # ---- 4. the literal buffer and the match queue ----
+    for n in (63, 64, 65):
+        q = Qtm(15); q.lits(bytes(rnd.getrandbits(8) for _ in range(n))); q.match(1, 9); q.match(n, 2 * n); q.lits(b"end")
+        C.append(_qtm_case("qtm_%d_literals_then_a_match_of_the_last" % n, q))
+    q = Qtm(15); q.lits(b"abc")
+    for _ in range(3 * SPQ_CAP):
+        q.match(3, 3)
+    q.match(700, 100)
+    q.lits(bytes(rnd.getrandbits(8) for _ in range(SPQ_RING + 1500)))        # (literals resolve nothing: the queue's base stays)
+    q.match(SPQ_RING + 1400, 259); q.match(3, 3); q.match(259, 259)
+    for _ in range(SPQ_CAP + 40):
+        q.match(3, 3)
+    q.lits(b"end")
+    C.append(_qtm_case("qtm_queue_overflows_and_a_match_beyond_its_ring", q))
+
+    # ---- 5. the window's ends ----
+    for wb in range(10, 15):
+        q = Qtm(wb); w = q.wsize
+        ends = [k * w for k in range(1, 12) if k * w % FRAME]
+        q.grow(ends[0] - 10); q.match(w - 3, 30)                 # crossing, its source before the start (first lap)
+        q.grow(ends[1] - 40); q.match(17, 40); q.lits(b"x")      # ends exactly at the window's end
+        q.grow(ends[2] - 1); q.match(5, 20)                      # starts at its last byte
+        q.grow(ends[3] - 100); q.match(1, 259)                   # a crossing run
+        q.lits(b"end")
+        C.append(_qtm_case("qtm_window_ends_w%d" % wb, q))
+    q = Qtm(15); q.grow(FRAME - 20); q.match(7, 20); q.grow(2 * FRAME - 1); q.lit(7); q.grow(2 * FRAME + 700)
+    C.append(_qtm_case("qtm_w15_frame_end_and_window_end_on_one_byte", q))
+
+    # ---- 6. the frame's end ----
+    for over, at, ln in ((1, FRAME - 10, 11), (258, FRAME - 1, 259)):
+        q = Qtm(16); q.grow(at); q.match(9, ln)
+        C.append(_qtm_case("qtm_match_overshoots_the_frame_by_%d" % over, q, out_len=40000, err=ERR_DECRUNCH))
+    q = Qtm(16); q.grow(FRAME - 259); q.match(300, 259); q.grow(FRAME + 900)
+    C.append(_qtm_case("qtm_match_ends_on_the_frame_end", q))
+    for n in (0, 1, 4, 300):
+        for kind in ("zero", "nonzero"):
+            if n == 0 and kind == "nonzero":
+                continue
+            q = Qtm(16, auto=False)
+            for f in range(2):
+                q.grow((f + 1) * FRAME)
+                q.end_frame(junk=bytes(n) if kind == "zero" else bytes(1 + (0x11 + 7 * k) % 253 for k in range(n)))
+            q.grow(2 * FRAME + 500)
+            C.append(_qtm_case("qtm_trailer_behind_%d_%s_bytes" % (n, kind), q))
+    found, t = {}, 0
+    while len(found) < 8:
+        q = Qtm(16); q.lits(bytes(_qlit(k) for k in range(20 + t))); q.grow(FRAME + 300)
+        found.setdefault(q.props["align"][0], q)
+        t += 1
+    for r_ in range(8):
+        C.append(_qtm_case("qtm_frame_payload_ends_at_bit_%d" % r_, found[r_]))
+    for nf in (1, 2):
+        for trailer in (False, True):
+            q = Qtm(16, auto=False)
+            for f in range(nf):
+                q.grow((f + 1) * FRAME); q.end_frame(trailer=trailer or f + 1 < nf)
+            C.append(_qtm_case("qtm_%d_whole_frames_%s_the_last_trailer" % (nf, "with" if trailer else "without"), q,
+                               err=ERR_OK if trailer else ERR_READ))
+
+    # ---- 7. the models: each pattern long enough for the second re-sort (rescale 54) of the models it drives ----
+    for kind in QTM_PATTERNS:
+        # the selector (7 entries) and, through it, whatever it selects
+        q = Qtm(13)
+        q.lits(b"seed")
+        for k, sel in enumerate(_pattern(kind, 7, QTM_MODEL_SYMBOLS, 1, rate=1.6)):
+            q.room(8)
+            if sel < 4:
+                q.lit(64 * sel + 5)
+            else:
+                q.match(1 + k % 3, (3, 4, 6)[sel - 4])
+        C.append(_qtm_case("qtm_selector_model_%s" % kind, q))
+        # one literal model, the length model and the three position models at their truncated and their full sizes
+        for wb in (10, 17, 21):
+            q = Qtm(wb)
+            n4, n5, n6 = q.M["4"].n, q.M["5"].n, q.M["6"].n
+            pats = [_pattern(kind, n, QTM_MODEL_SYMBOLS, 10 * wb + j) for j, n in enumerate((64, 27, n4, n5, n6))]
+            for a, b, c, d, e in zip(*pats):
+                q.room(270)
+                q.lit(128 + a)
+                q.match(QPB[c] + 1 + (a & ((1 << QPE[c]) - 1)), 3)
+                q.match(QPB[d] + (1 << QPE[d]), 4)
+                q.match(QPB[e] + 1 + (a * 2654435761 & ((1 << QPE[e]) - 1)), QLB[b] + (a & ((1 << QLE[b]) - 1)) + 5)
+            C.append(_qtm_case("qtm_literal_length_position_models_%s_w%d" % (kind, wb), q))
+
+    # ---- 8. the coder's extremes ----
+    q, first_double = qtm_search_extremes()
+    C.append(_qtm_case("qtm_renormalisation_extremes", q))
+    if first_double is not None:
+        q2 = Qtm(16)
+        q2.lits(q.plain[:first_double]); q2.lits(b"two refills")
+        assert q2.props["double_refills"] >= 1
+        C.append(_qtm_case("qtm_two_refills_in_one_symbol", q2))
+
+    # ---- 9. small requests and inputs ----
+    def small():
+        q = Qtm(10); q.lits(b"small "); q.match(6, 30); q.lits(b"requests"); q.match(3, 100); q.lits(b"end")
+        return q
+    for n in (0, 1, 2):
+        C.append(_qtm_case("qtm_request_of_%d_bytes" % n, small(), out_len=n))
+    for n in range(4):
+        q = small()
+        C.append(_qtm_case("qtm_input_of_%d_bytes" % n, q, err=ERR_READ, stream=q.stream()[:n]))
+    C.append(_qtm_case("qtm_request_ends_inside_a_match", small(), out_len=6 + 30 + 8 + 50))
+    q = Qtm(10); q.grow(1024 - 10); q.match(50, 30); q.lits(b"end")
+    C.append(_qtm_case("qtm_request_ends_inside_a_window_crossing_match", q, out_len=1024 - 5, err=ERR_DECRUNCH))
+    return C
+
+
 def all_cases():
-    return lzx_cases() + lzxd_cases() + mszip_cases()
+    return lzx_cases() + lzxd_cases() + mszip_cases() + qtm_cases()

@@ -182,6 +182,11 @@ def oracle_qtm(data, out_bytes, window_bits):
     return res.err, buf.raw[:min(res.out_len, out_bytes)], res
 
 
+def oracle_set_hard_eof(on):
+    """the feeder's read FAILS at the end of the input (MSPACK_HIP_UF_HARD_EOF) for this thread's next oracle calls; 0 switches it off"""
+    oracle().oracle_set_hard_eof(1 if on else 0)
+
+
 def oracle_qtm_marks(data, out_bytes, window_bits, marks):
     """one oracle decode of the whole request with marks (oracle_qtm_set_marks): -> (err, [what a request ending at each mark holds back])"""
     import numpy as np

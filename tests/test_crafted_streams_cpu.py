@@ -8,7 +8,7 @@ import sys
 import pytest
 
 import crafted_streams as CS
-from helpers import emu_so, have_ref, oracle_lzx, oracle_lzxd, oracle_mszip, ref_lzx, ref_lzxd, ref_mszip
+from helpers import emu_so, have_ref, oracle_lzx, oracle_lzxd, oracle_mszip, oracle_qtm, ref_lzx, ref_lzxd, ref_mszip, ref_qtm
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CASES = CS.all_cases()
@@ -19,13 +19,16 @@ def run_oracle(c):
         e, o, r = oracle_lzx(c.stream, c.out_len, c.wb, c.reset)
     elif c.codec == "lzxd":
         e, o, r = oracle_lzxd(c.stream, c.out_len, c.wb, c.ref)
+    elif c.codec == "qtm":
+        e, o, r = oracle_qtm(c.stream, c.out_len, c.wb)
     else:
         e, o, r, _ = oracle_mszip(c.stream, c.out_len)
     return e, o, r
 
 
 def test_case_names_are_unique():
-    assert len({c.name for c in CASES}) == len(CASES) >= 40
+    assert len({c.name for c in CASES}) == len(CASES) >= 40 + 70
+    assert sum(c.codec == "qtm" for c in CASES) >= 70
 
 
 @pytest.mark.parametrize("c", CASES, ids=[c.name for c in CASES])
@@ -45,6 +48,10 @@ def test_oracle_equals_the_reference(built, c):
         re, ro, rw = ref_lzx(c.stream, c.out_len, c.wb, c.reset)
     elif c.codec == "lzxd":
         re, ro, rw = ref_lzxd(c.stream, c.out_len, c.wb, c.ref)
+    elif c.codec == "qtm":
+        re, ro, rw = ref_qtm(c.stream, c.out_len, c.wb)
+        if c.props["before_start"]:       # qtmd_init does not clear its window: what lies before the start is undefined there
+            ro = o[:rw]
     else:
         re, ro, rw = ref_mszip(c.stream, c.out_len)
     assert re == e and rw == r.out_len and ro == o[:rw], (re, e, rw, r.out_len)
@@ -134,13 +141,99 @@ def test_cases_have_the_property_they_name():
     assert 257 + 27 in p["len_codes"] and p["max_dist"] == 32768
 
 
+# what the coder-extremes search reaches (crafted_streams.qtm_search_extremes), frozen: the case must not quietly degrade.
+# (k = n + mu >= 17, two 16-bit refills in one symbol, is not reached: an interval is never narrower than range / total - 1
+# >= 2^14 / 3808 - 1 = 3, which leaves at most 14 leading bits in common, and an underflow run behind n shifts needs an interval
+# narrower still.)
+QTM_MAX_N, QTM_MAX_MU, QTM_MAX_K = 14, 13, 14
+
+
+def test_quantum_cases_have_the_property_they_name(built):
+    """measured on what the writer wrote (props), not declared"""
+    Q = {c.name: c for c in CASES if c.codec == "qtm"}
+    P = lambda name: Q[name].props
+    # sources before the start: the offset is beyond P; zeros first, then real bytes; a period walked back more than once
+    for p0 in (0, 1, 3):
+        assert P("qtm_offset_beyond_the_start_at_P%d" % p0)["before_start"] == [p0]
+    p = P("qtm_offset_of_the_whole_window_at_P0")
+    assert p["before_start"][0] == 0 and max(p["slots"][6]) == 19 and 255 in p["slots"][6][19]
+    assert P("qtm_match_reads_zeros_then_real_bytes")["before_start"] == [5, 13]
+    assert P("qtm_periodic_match_from_before_the_start")["before_start"] == [2, 44, 303] and Q["qtm_periodic_match_from_before_the_start"].plain[2:9] == b"\0\0\0ab\0\0"
+    p = P("qtm_w21_every_slot_of_models_4_5_6_from_before_the_start")
+    assert [sorted(p["slots"][k]) for k in (4, 5, 6)] == [list(range(24)), list(range(36)), list(range(42))]
+    assert p["max_raw"] == 19 and len(p["before_start"]) >= 72 and Q["qtm_w21_every_slot_of_models_4_5_6_from_before_the_start"].out_len < 4096
+    # every slot with a real source: no match reads before the start; both ends of every slot's extra bits
+    for wb in (10, 12, 17, 18, 21):
+        p = P("qtm_every_slot_w%d" % wb)
+        assert not p["before_start"], wb
+        for sel, n in ((4, min(24, 2 * wb)), (5, min(36, 2 * wb)), (6, 2 * wb)):
+            assert sorted(p["slots"][sel]) == list(range(n)), (wb, sel)
+            assert all(p["slots"][sel][sl] >= {0, (1 << CS.QPE[sl]) - 1} for sl in range(n)), (wb, sel)
+    assert all(P("qtm_every_slot_w12")["len_slots"][sl] >= {0, (1 << CS.QLE[sl]) - 1} for sl in range(27))
+    assert 259 in P("qtm_every_slot_w12")["lengths"]
+    c = Q["qtm_every_slot_w21"]
+    assert c.out_len > (1 << 21) and (1 << 19) - 1 in c.props["slots"][6][41] and len(c.props["slots"][6][41]) >= 2
+    # short periods; the literal buffer; the queue
+    assert P("qtm_short_periods_1_to_64")["lengths"] >= {64, 65, 128, 259}
+    assert set(range(6)) <= set(P("qtm_short_periods_1_to_64")["slots"][6])
+    assert Q["qtm_queue_overflows_and_a_match_beyond_its_ring"].out_len > CS.SPQ_RING + 3 * CS.SPQ_CAP
+    # window ends: a crossing match with its source before the start; one ending at the end; one starting on the last byte
+    for wb in range(10, 15):
+        c = Q["qtm_window_ends_w%d" % wb]
+        w = 1 << wb
+        assert len(c.props["crossing"]) == 3 and c.props["crossing"][0] == w - 10 == c.props["before_start"][0], wb
+        assert (c.props["crossing"][1] + 1) % w == 0 and (c.props["crossing"][2] + 100) % w == 0, wb
+    assert P("qtm_w15_frame_end_and_window_end_on_one_byte")["junk"] == [b"", b""]
+    # frame ends: the trailers' junk, the eight alignments of the payload's end
+    for n in (1, 4, 300):
+        assert P("qtm_trailer_behind_%d_zero_bytes" % n)["junk"] == [bytes(n)] * 2
+        j = P("qtm_trailer_behind_%d_nonzero_bytes" % n)["junk"]
+        assert len(j[0]) == n and 0 not in j[0] and 255 not in j[0]
+    for r_ in range(8):
+        assert P("qtm_frame_payload_ends_at_bit_%d" % r_)["align"][0] == r_
+    for nf in (1, 2):
+        assert not Q["qtm_%d_whole_frames_without_the_last_trailer" % nf].stream.endswith(b"\xff")
+        assert Q["qtm_%d_whole_frames_with_the_last_trailer" % nf].stream.endswith(b"\xff")
+        assert Q["qtm_%d_whole_frames_with_the_last_trailer" % nf].out_len == nf * CS.FRAME
+    # the models: at least two re-sorts, one of them with tied frequencies, of every model the case is about
+    for kind in CS.QTM_PATTERNS:
+        m = P("qtm_selector_model_%s" % kind)["model_sel"]
+        assert m["resorts"] >= 2 and m["tied_resorts"] >= 1, (kind, m)
+        for wb, sizes in ((10, (20, 20, 20)), (17, (24, 34, 34)), (21, (24, 36, 42))):
+            p = P("qtm_literal_length_position_models_%s_w%d" % (kind, wb))
+            assert tuple(p["model_" + k]["n"] for k in ("4", "5", "6")) == sizes
+            for k in ("lit2", "6len", "4", "5", "6"):
+                m = p["model_" + k]
+                assert m["resorts"] >= 2 and m["tied_resorts"] >= 1, (kind, wb, k, m)
+                if kind == "round_robin":
+                    assert len(m["used"]) == m["n"], (wb, k)
+    assert any(P("qtm_literal_length_position_models_%s_w21" % k)["model_6"]["moving_resorts"] for k in CS.QTM_PATTERNS)
+    # the coder's extremes, against what one stream of the project's own encoder takes (tests/test_gpu_qtm.py)
+    p = P("qtm_renormalisation_extremes")
+    assert (p["max_n"], p["max_mu"], p["max_k"]) == (QTM_MAX_N, QTM_MAX_MU, QTM_MAX_K) and p["double_refills"] == 0
+    import libmspack_amd as M
+    d = M.gen_plaintext(9, M.TEXT_MIX, 120000)
+    n, mu, k, plain = CS.qtm_read_maxima(M.qtm_encode(d, 16)[0], d.size, 16)
+    assert plain == d.tobytes()
+    print("the encoder's stream: n %d mu %d k %d" % (n, mu, k))
+    assert QTM_MAX_N > n and QTM_MAX_MU > mu and QTM_MAX_K > k, (n, mu, k)
+    # small requests
+    assert [Q["qtm_request_of_%d_bytes" % n].out_len for n in (0, 1, 2)] == [0, 1, 2]
+    assert [len(Q["qtm_input_of_%d_bytes" % n].stream) for n in range(4)] == [0, 1, 2, 3]
+    c = Q["qtm_request_ends_inside_a_window_crossing_match"]
+    assert c.props["crossing"] == [1014] and 1014 < c.out_len < 1024
+
+
+# the emulator run leaves out (at most two, by name): minutes each there, milliseconds on the GPU, which leaves out none
+EMU_LEAVES_OUT = ("qtm_literal_length_position_models_alternating_w10", "qtm_literal_length_position_models_alternating_w17")
+
 EMU_WORKER = r'''
 import sys
 sys.path.insert(0, %r); sys.path.insert(0, %r + "/tests")
 import libmspack_amd as M
 import test_gpu_crafted as G
 assert "emu" in M.HIP_SO
-G.check_all(G.CS.all_cases())
+G.check_all([c for c in G.CS.all_cases() if c.name not in %r])
 print("EMU_CRAFTED_OK")
 '''
 
@@ -149,7 +242,7 @@ print("EMU_CRAFTED_OK")
 def test_crafted_streams_on_the_wavefront_emulator(built, tmp_path):
     so = emu_so()                  # (rebuilt when a kernel source is newer: the run must see the kernels as they are)
     script = tmp_path / "w.py"
-    script.write_text(EMU_WORKER % (ROOT, ROOT))
+    script.write_text(EMU_WORKER % (ROOT, ROOT, EMU_LEAVES_OUT))
     env = dict(os.environ, MSPACK_HIP_SO=so)
-    p = subprocess.run([sys.executable, str(script)], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=1500)
+    p = subprocess.run([sys.executable, str(script)], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=3000)
     assert p.returncode == 0 and b"EMU_CRAFTED_OK" in p.stdout, p.stdout.decode()[-3000:]

@@ -3,13 +3,15 @@ with and without their frame tables -- against the oracle (error, out_len, in_ne
 up to out_len) and against the helper's own plaintext; the multi-frame cases with one block per frame must really take the
 frame-parallel path.  Then every valid LZX case 600 times in one batch with its frame table, so that the pipe's tickets no
 longer all find a wave at once (the speculative header path and the other ticket orders run): ~16 000 units, ~900 MB of
-output, 2.5 s on an MI355X."""
+output, 2.5 s on an MI355X.  The Quantum cases go in three times each -- in_len exact, in_len extended over 160 zero bytes
+(the lean reader), exact with a failing feeder -- and in_used and good_len are held against the oracle too; then every valid
+one 200 times in one batch, every third unit with marks (wall time of the Quantum tests on an MI355X: not measured yet)."""
 import numpy as np
 import pytest
 
 import crafted_streams as CS
 import libmspack_amd as M
-from helpers import oracle_lzx, oracle_lzxd, oracle_mszip
+from helpers import oracle_lzx, oracle_lzxd, oracle_mszip, oracle_qtm, oracle_qtm_marks, oracle_set_hard_eof
 import test_gpu_lzx_frames as T
 import test_gpu_lzxd as D
 import test_gpu_mszip_blocks as B
@@ -61,10 +63,76 @@ def check_mszip(cases):
         assert res["in_next"][i] == r.in_next and (int(res["flags"][i]) & ~ADOPTED) == r.flags, (c.name, res[i], r.in_next, r.flags)
 
 
+UF_HARD_EOF = 2                    # MSPACK_HIP_UF_HARD_EOF (include/mspack_hip.h)
+QTM_PAD = 160                      # zero bytes behind every stream: more than the 96 the lean reader wants ahead of it
+
+
+def qtm_arena(cases):
+    """one copy of every stream, QTM_PAD zero bytes behind each -> (arena, offsets)"""
+    offs, pos = [], 0
+    for c in cases:
+        pos = (pos + 15) & ~15
+        offs.append(pos); pos += len(c.stream) + QTM_PAD
+    arena = np.zeros(pos + 64, dtype=np.uint8)
+    for c, o in zip(cases, offs):
+        arena[o:o + len(c.stream)] = np.frombuffer(c.stream, dtype=np.uint8)
+    return arena, offs
+
+
+def check_qtm_good_len(name, data, wb, hard, out_len, r):
+    """a failing unit's good_len: a request that ends there succeeds, the next longer one fails as the unit did"""
+    oracle_set_hard_eof(hard)
+    try:
+        g = int(r["good_len"])
+        assert g <= out_len, (name, r)
+        assert oracle_qtm(data, g, wb)[0] == 0, (name, "a request of good_len fails", r)
+        if g < out_len:
+            e1 = oracle_qtm(data, g + 1, wb)[0]
+            assert e1 == r["err"], (name, "a request of good_len + 1 gives", e1, r)
+    finally:
+        oracle_set_hard_eof(0)
+
+
+def check_qtm(cases):
+    """every case three times: in_len exact (a tiny stream never leaves the exact reader), in_len extended over the zeros behind
+    it (the lean reader runs up to the last token), exact with a failing feeder (MSPACK_HIP_UF_HARD_EOF)"""
+    arena, offs = qtm_arena(cases)
+    variants = [(0, 0), (QTM_PAD, 0), (0, UF_HARD_EOF)]
+    rep = lambda v: np.repeat(np.asarray(v), len(variants))
+    units, out_bytes = M.make_units(M.KIND_QUANTUM, rep(offs), rep([len(c.stream) for c in cases]), rep([c.out_len for c in cases]),
+                                    window_bits=rep([c.wb for c in cases]))
+    units["in_len"] += np.tile([v[0] for v in variants], len(cases)).astype(np.uint32)
+    units["flags"] |= np.tile([v[1] for v in variants], len(cases)).astype(np.uint32)
+    out, res = M.decode_batch(units, arena, out_bytes)
+    for j, c in enumerate(cases):
+        for k, (pad, flag) in enumerate(variants):
+            i = len(variants) * j + k
+            data = c.stream + bytes(pad)
+            oracle_set_hard_eof(bool(flag))
+            try:
+                e, o, r = oracle_qtm(data, c.out_len, c.wb)
+            finally:
+                oracle_set_hard_eof(0)
+            what = (c.name, ("exact", "extended", "hard_eof")[k], res[i], e, r.out_len, r.in_used)
+            assert res["err"][i] == e and res["out_len"][i] == r.out_len, what
+            got = out[units["out_off"][i]:units["out_off"][i] + r.out_len].tobytes()
+            assert got == o[:r.out_len], what
+            if k == 0:
+                assert e == c.err, what
+            if c.plain is not None and e == 0:
+                assert got == c.plain, what
+            assert res["in_used"][i] == r.in_used, what
+            if e != 0:
+                check_qtm_good_len(what[:2], data, c.wb, bool(flag), c.out_len, res[i])
+            else:
+                assert res["good_len"][i] == r.out_len, what
+
+
 def check_all(cases):
     check_lzx([c for c in cases if c.codec == "lzx"])
     check_lzxd([c for c in cases if c.codec == "lzxd"])
     check_mszip([c for c in cases if c.codec == "mszip"])
+    check_qtm([c for c in cases if c.codec == "qtm"])
 
 
 def test_crafted_streams_vs_oracle(built):
@@ -98,3 +166,41 @@ def test_valid_lzx_cases_600_times_in_one_batch(built):
             assert (int(res["flags"][i]) & ~ADOPTED) == r.flags, (c.name, i, res[i])
             assert c.name not in MUST_ADOPT or res["flags"][i] & ADOPTED, (c.name, i, res[i])
             assert np.array_equal(out[units["out_off"][i]:units["out_off"][i] + c.out_len], want), (c.name, i)
+
+
+def test_valid_qtm_cases_200_times_in_one_batch(built):
+    """(the 200 units of a case share one copy of its stream; every third unit carries marks -- every 97th position and around every
+    window end -- and so runs in the mark-bearing kernel)"""
+    cases = [c for c in CS.qtm_cases() if c.err == 0 and c.out_len > 0]
+    n = 200
+    arena, offs = qtm_arena(cases)
+    marks, toffs, pos = [], [], (len(arena) + 3) & ~3
+    for c in cases:
+        m = sorted(set(range(97, c.out_len, 97)) |
+                   set((k << c.wb) + j for k in range(1, (c.out_len >> c.wb) + 1) for j in range(-4, 2) if 0 < (k << c.wb) + j < c.out_len))
+        marks.append(m); toffs.append(pos); pos += 4 * len(m)
+    arena = np.concatenate([arena, np.zeros(pos + 64 - len(arena), dtype=np.uint8)])
+    for m, o in zip(marks, toffs):
+        arena[o:o + 4 * len(m)] = np.asarray(m, dtype=np.uint32).view(np.uint8)
+    rep = lambda v: np.repeat(np.asarray(v), n)
+    units, _ = M.make_units(M.KIND_QUANTUM, rep(offs), rep([len(c.stream) + QTM_PAD for c in cases]), rep([c.out_len for c in cases]),
+                            window_bits=rep([c.wb for c in cases]))
+    marked = np.arange(len(units)) % 3 == 0
+    units["flags"][marked] |= M.UF_QTM_MARKS
+    units["in_chunk"] = np.where(marked, rep(toffs) // 4, 0)
+    units["ref_len"] = np.where(marked, rep([len(m) for m in marks]), 0)
+    # (room for the logs: 16 bytes of alignment + 4 bytes per mark behind a marked unit's output)
+    sizes = ((units["out_len"].astype(np.int64) + 15) & ~15) + np.where(marked, 16 + 4 * units["ref_len"].astype(np.int64), 0)
+    units["out_off"] = np.concatenate([[0], np.cumsum(sizes)[:-1]])
+    out, res = M.decode_batch(units, arena, int(sizes.sum()))
+    for j, c in enumerate(cases):
+        e, _o, r = oracle_qtm(c.stream + bytes(QTM_PAD), c.out_len, c.wb)
+        _e, want_log = oracle_qtm_marks(c.stream + bytes(QTM_PAD), c.out_len, c.wb, marks[j])
+        want = np.frombuffer(c.plain, dtype=np.uint8)
+        for i in range(j * n, (j + 1) * n):
+            assert res["err"][i] == e == 0 and res["out_len"][i] == r.out_len and res["in_used"][i] == r.in_used, (c.name, i, res[i])
+            o = int(units["out_off"][i])
+            assert np.array_equal(out[o:o + c.out_len], want), (c.name, i)
+            if marked[i]:
+                lo = o + ((c.out_len + 15) & ~15)
+                assert out[lo:lo + 4 * len(marks[j])].view(np.uint32).tolist() == want_log, (c.name, i)

@@ -12,7 +12,7 @@ import libmspack_amd as M
 from helpers import oracle_lzx, oracle_mszip, oracle_qtm
 from test_gpu_lzx import run_units as run_lzx
 from test_gpu_mszip import run as run_mszip, folder as zip_folder
-from test_gpu_qtm import run as run_qtm
+from test_gpu_qtm import run as run_qtm, check_in_used_and_good_len
 
 pytestmark = pytest.mark.gpu
 
@@ -232,6 +232,7 @@ def test_fuzz_qtm(built):
     for i, st in enumerate(streams):
         e, o, r = oracle_qtm(st, lens[i], wbs[i])
         compare("qtm", i, res, units, out, e, o, r)
+        check_in_used_and_good_len(i, st, lens[i], wbs[i], res[i], r)
 
 
 def test_long_runs_overflow_the_match_queue(built):

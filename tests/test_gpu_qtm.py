@@ -23,6 +23,18 @@ def run(streams, out_lens, wbs):
     return units, out, res
 
 
+def check_in_used_and_good_len(i, stream, out_len, wb, r, want):
+    """in_used is the reference's i_ptr; a failing unit's good_len: a request that ends there succeeds, the next longer one fails as
+    the unit did"""
+    assert r["in_used"] == want.in_used, (i, r, want.in_used)
+    if r["err"] == 0:
+        assert r["good_len"] == want.out_len, (i, r)
+        return
+    g = int(r["good_len"])
+    assert g <= out_len and oracle_qtm(stream, g, wb)[0] == 0, (i, r)
+    assert g == out_len or oracle_qtm(stream, g + 1, wb)[0] == r["err"], (i, r)
+
+
 def test_qtm_kinds_and_windows(built):
     streams, lens, wbs, plains = [], [], [], []
     for kind in range(6):
@@ -61,6 +73,7 @@ def test_qtm_partial_truncated_corrupt(built):
         if e == 0:
             got = out[units["out_off"][i]:units["out_off"][i] + r.out_len].tobytes()
             assert got == o[:r.out_len], i
+        check_in_used_and_good_len(i, st, lens[i], 16, res[i], r)
 
 
 def test_qtm_marks_vs_oracle(built):
