@@ -1,4 +1,4 @@
-// fold_common.hpp -- a 32 KiB frame's SOURCE MAP in LDS: what mspack_lzx_fold / mspack_mszip_fold (shim.hip) share.
+// fold_common.hpp -- a 32 KiB frame's SOURCE MAP in LDS: what mspack_lzx_fold / mspack_mszip_fold (entry_kernels.hpp) share.
 //
 // The per-folder chain of LZ77 copies (lzxd.c:613-646, mszipd.c:262-296) cut down to one gather pass per frame: off the chain a
 // wave writes, for every byte of ITS frame, the position that byte is copied from (fold_fill_batch: the frame's match records, 64

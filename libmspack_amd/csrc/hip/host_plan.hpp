@@ -1,0 +1,272 @@
+// host_plan.hpp -- the host path's chunk planner: from the caller's unit table to a BatchPlan (units in arena order, frame-slot
+// numbers, chunks with their spans, per-kind launch lists and CRC lists, the units rebased to the spans).  Pure arithmetic: no HIP
+// call, no global, no environment variable, no lock -- only <mspack_hip.h> and standard headers, so a test includes this file alone
+// (tests/hostcheck/plan_check.cpp).  The knobs come in as a PlanKnobs (host_pipeline.hpp fills one from the environment).
+#pragma once
+#include <mspack_hip.h>
+#include <stdint.h>
+#include <stddef.h>
+#include <stdio.h>
+#include <algorithm>
+#include <vector>
+#define MSPK_MAX_CHUNKS 8
+struct Chunk {
+  size_t a, b;                          // local unit range [a, b)
+  uint64_t in_lo, in_hi, out_lo, out_hi;
+  size_t order_off[8], order_n[8];      // per kind: slice of the order array
+  size_t fm_lo, fm_n;
+  size_t crc_off, crc_n; uint64_t crc_max;      // the chunk's units that carry MSPACK_HIP_UF_CRC32: slice of the order array, the longest
+  bool has_ftab;                        // some LZX unit of the chunk carries a frame table
+};
+
+// bytes below out_off that belong to the unit, and the room it may write past out_len
+static inline uint64_t unit_below(const mspack_hip_unit &u) {
+  return (u.kind == MSPACK_HIP_KIND_LZSS || u.kind == MSPACK_HIP_KIND_KWAJ_LZH) ? 4096u
+       : (u.kind == MSPACK_HIP_KIND_LZX_DELTA ? u.ref_len : 0u);
+}
+static inline uint64_t unit_above(const mspack_hip_unit &u) {
+  if (u.kind == MSPACK_HIP_KIND_LZX && (u.flags & MSPACK_HIP_UF_LZX_LOG))                   // the reset log, where MSZIP's would be
+    return ((((uint64_t) u.out_len + 32768u + 15u) & ~15ull) - u.out_len) + 4u + 4u * (uint64_t) u.ref_len;
+  if (u.kind == MSPACK_HIP_KIND_QUANTUM && (u.flags & MSPACK_HIP_UF_QTM_MARKS) && u.ref_len)   // the log of its marks
+    return ((((uint64_t) u.out_len + 15u) & ~15ull) - u.out_len) + 4u * (uint64_t) u.ref_len;
+  if (u.kind != MSPACK_HIP_KIND_MSZIP) return 0u;
+  uint64_t a = 32768u;
+  if ((u.flags & MSPACK_HIP_UF_MSZIP_REPAIR) && (u.flags & MSPACK_HIP_UF_MSZIP_LOG))      // the repair log behind the slack
+    a = ((((uint64_t) u.out_len + 32768u + 15u) & ~15ull) - u.out_len) + 4u + 8u * (uint64_t)(u.e8_base > 0 ? u.e8_base : 0);
+  return a;
+}
+static inline bool unit_has_ftab(const mspack_hip_unit &u) {
+  if (!(u.flags & MSPACK_HIP_UF_FRAME_TABLE)) return false;
+  if (u.kind == MSPACK_HIP_KIND_LZX) return true;
+  return u.kind == MSPACK_HIP_KIND_MSZIP && !(u.flags & (MSPACK_HIP_UF_MSZIP_REPAIR | MSPACK_HIP_UF_MSZIP_KWAJ));
+}
+static inline uint64_t unit_ftab_bytes(const mspack_hip_unit &u) { return (((uint64_t) u.out_len + 32767u) / 32768u) * 4u; }
+// a table the unit reads out of the input arena besides its stream (in_chunk * 4: a frame / block table, a Quantum unit's marks)
+static inline bool unit_side_table(const mspack_hip_unit &u, uint64_t &lo, uint64_t &hi) {
+  if (unit_has_ftab(u)) { lo = (uint64_t) u.in_chunk * 4u; hi = lo + unit_ftab_bytes(u); return true; }
+  if (u.kind == MSPACK_HIP_KIND_QUANTUM && (u.flags & MSPACK_HIP_UF_QTM_MARKS) && u.ref_len) {
+    lo = (uint64_t) u.in_chunk * 4u; hi = lo + 4u * (uint64_t) u.ref_len; return true;
+  }
+  return false;
+}
+static inline size_t unit_frames(const mspack_hip_unit &u) {
+  if (u.kind == MSPACK_HIP_KIND_LZX || u.kind == MSPACK_HIP_KIND_LZX_DELTA) return (size_t) u.out_len / 32768u + 1u;
+  if (u.kind == MSPACK_HIP_KIND_MSZIP && unit_has_ftab(u)) return ((size_t) u.out_len + 32767u) / 32768u;   // one per CFDATA block
+  return 0u;
+}
+
+struct PlanKnobs {
+  size_t max_chunks, chunk_bytes, chunk_units;      // at most so many chunks, each >= chunk_bytes of input and >= chunk_units units
+  int shape;                                        // the chunks' shares (plan_batch); -1 = by destination
+  std::vector<uint64_t> weights;                    // the first shares spelled out (sweeps)
+};
+// what plan_batch computes.  local[i] is unit idx[i] of the caller's table, offsets relative to in_lo / out_lo; the chunks are
+// ranges of local[]; order holds every chunk's per-kind lists and its CRC list (indices into local[])
+struct BatchPlan {
+  std::vector<uint32_t> idx;
+  std::vector<mspack_hip_unit> local;
+  std::vector<uint32_t> order;
+  std::vector<Chunk> chunks;
+  uint64_t in_lo, in_hi, out_lo, out_hi, in_sum;
+  size_t n_frames, n_rec_slots, n_crc;              // n_crc: units that want a digest (MSPACK_HIP_UF_CRC32)
+  bool monotone, has_qtm;
+};
+
+// plan_batch's first step: the units in arena order, validated, their frame slots numbered, the batch's spans
+static int plan_units(mspack_hip_unit *units, const uint32_t *sel, size_t n_sel, size_t in_bytes, size_t out_bytes,
+                      bool dev_out, bool per_unit_back, BatchPlan &p, char *errbuf, size_t errcap)
+{
+  std::vector<uint32_t> &idx = p.idx;
+  std::vector<mspack_hip_unit> &local = p.local;
+  idx.resize(n_sel);
+  for (size_t i = 0; i < n_sel; i++) idx[i] = sel ? sel[i] : (uint32_t) i;
+  std::stable_sort(idx.begin(), idx.end(), [&](uint32_t x, uint32_t y) { return units[x].in_off < units[y].in_off; });
+  local.resize(n_sel);
+  bool monotone = !per_unit_back;
+  uint64_t in_lo = ~0ull, in_hi = 0, out_lo = ~0ull, out_hi = 0, prev_hi = 0, in_sum = 0;
+  size_t n_frames = 0, n_rec_slots = 0, n_crc = 0;
+  for (size_t i = 0; i < n_sel; i++) {
+    mspack_hip_unit &u = local[i];
+    u = units[idx[i]];
+    if (u.kind != MSPACK_HIP_KIND_LZX_DELTA && !(u.kind == MSPACK_HIP_KIND_LZX && (u.flags & MSPACK_HIP_UF_LZX_LOG)) &&
+        !(u.kind == MSPACK_HIP_KIND_QUANTUM && (u.flags & MSPACK_HIP_UF_QTM_MARKS))) u.ref_len = 0;
+    if (u.kind > MSPACK_HIP_KIND_XORSUM) { snprintf(errbuf, errcap, "unit %u: unknown kind %u", idx[i], u.kind); return -1; }
+    if (u.kind == MSPACK_HIP_KIND_XORSUM) {                // reads its input, owns no output
+      if (u.flags & MSPACK_HIP_UF_CRC32) { snprintf(errbuf, errcap, "unit %u: a checksum unit decodes nothing to take a CRC-32 of", idx[i]); return -1; }
+      if (u.out_len) { snprintf(errbuf, errcap, "unit %u: a checksum unit has no output", idx[i]); return -1; }
+      if (u.in_off + u.in_len > in_bytes) { snprintf(errbuf, errcap, "unit outside arena"); return -1; }
+      in_lo = std::min<uint64_t>(in_lo, u.in_off); in_hi = std::max<uint64_t>(in_hi, u.in_off + u.in_len);
+      continue;
+    }
+    // kind 0 = "no codec": the unit is carried along, no kernel takes it, its result says MSPACK_ERR_ARGS
+    const uint64_t below = unit_below(u);
+    if (below > u.out_off) { snprintf(errbuf, errcap, "unit's lower region outside arena"); return -1; }
+    const uint64_t lo = u.out_off - below, hi = u.out_off + u.out_len + unit_above(u);
+    if (u.in_off + u.in_len > in_bytes || hi > out_bytes) { snprintf(errbuf, errcap, "unit outside arena"); return -1; }
+    if (i && lo < prev_hi) monotone = false;
+    prev_hi = hi;
+    in_lo = std::min<uint64_t>(in_lo, u.in_off); in_hi = std::max<uint64_t>(in_hi, u.in_off + u.in_len);
+    {
+      uint64_t tl, th;
+      if (unit_side_table(u, tl, th)) {
+        if (th > in_bytes) { snprintf(errbuf, errcap, "unit's table outside arena"); return -1; }
+        if (u.kind == MSPACK_HIP_KIND_QUANTUM && (u.out_off & 3u)) { snprintf(errbuf, errcap, "unit %u: a Quantum unit with marks needs out_off %% 4 == 0", idx[i]); return -1; }
+        in_lo = std::min(in_lo, tl); in_hi = std::max(in_hi, th);
+      }
+    }
+    out_lo = std::min(out_lo, lo); out_hi = std::max(out_hi, hi);
+    in_sum += u.in_len;
+    if ((u.flags & MSPACK_HIP_UF_CRC32) && u.kind != 0) n_crc++;
+  }
+  // frame slots: the units that carry a usable frame / block table first -- only their slots hold records and tokens
+  for (int pass = 0; pass < 2; pass++) {
+    for (size_t i = 0; i < n_sel; i++) {
+      mspack_hip_unit &u = local[i];
+      if ((pass == 0) != unit_has_ftab(u)) continue;
+      u.frame_base = (uint32_t) n_frames; units[idx[i]].frame_base = (uint32_t) n_frames;
+      n_frames += unit_frames(u);
+    }
+    if (pass == 0) n_rec_slots = n_frames;
+  }
+  in_lo &= ~15ull;                                     // keep the units' alignment
+  if (out_lo > out_hi) out_lo = out_hi = 0;            // (checksum units only: nothing is written)
+  if (dev_out) out_lo = 0;                             // the caller's device buffer is addressed as is
+  p.in_lo = in_lo; p.in_hi = in_hi; p.out_lo = out_lo; p.out_hi = out_hi; p.in_sum = in_sum;
+  p.n_frames = n_frames; p.n_rec_slots = n_rec_slots; p.n_crc = n_crc; p.monotone = monotone;
+  return 0;
+}
+
+// the second: which units go into which chunk
+static void plan_chunks(bool to_host, const PlanKnobs &kn, BatchPlan &p)
+{
+  const std::vector<mspack_hip_unit> &local = p.local;
+  const size_t n_sel = local.size();
+  const bool monotone = p.monotone;
+  const uint64_t in_sum = p.in_sum;
+  // chunks: arena-contiguous runs of units; enough of them to overlap the copies with the decode, each
+  // big enough to be worth a launch.  Outputs that interleave (not monotone) are copied back unit by unit.
+  // (a chunk: >= chunk_bytes of input -- 8 MiB: a copy of >= 150 us -- and >= chunk_units units: 256)
+  bool has_qtm = false;
+  const size_t max_chunks = std::min<size_t>(kn.max_chunks, MSPK_MAX_CHUNKS);
+  size_t want = monotone ? std::min<size_t>(max_chunks, std::max<size_t>(1, in_sum / kn.chunk_bytes)) : 1;
+  {
+    // (units that decode: checksum units ride along and are no reason to cut)
+    size_t n_dec = 0;
+    for (size_t i = 0; i < n_sel; i++) {
+      if (local[i].kind != MSPACK_HIP_KIND_XORSUM) n_dec++;
+      if (local[i].kind == MSPACK_HIP_KIND_QUANTUM) has_qtm = true;
+    }
+    want = std::min(want, std::max<size_t>(1, n_dec / kn.chunk_units));
+  }
+  p.has_qtm = has_qtm;
+  std::vector<Chunk> &chunks = p.chunks;
+  chunks.clear();
+  {
+    // shares of the input bytes.  MSPACK_HIP_CHUNK_SHAPE: 0 equal; 1 = 1 : 1 : 2 : 4 ... (to the device: the default -- the small
+    // chunks get the launches going while most of the input is still on its way, and the LAST chunk, whose launches end the call,
+    // is the large one that fills the chip: headline 4.64-4.84 -> 4.05-4.15 ms, every growing shape within 0.1 ms of it, falling
+    // ones and more than four chunks slower; 1024 and 16 384 units: no difference -- profiles/round6_jobs.txt; round 3 had it at
+    // 4.55 against 4.74 and kept the equal shares); 2 = a first chunk of half a share (to the host: the default -- the copy-back,
+    // the longest leg, starts as soon as the first chunk is through; 1 there: 8.2 against 7.6 ms); 3, 4: a x1.5 ramp, falling shares
+    // (sweeps)
+    const int shape = kn.shape >= 0 ? kn.shape : (to_host ? 2 : 1);
+    uint64_t wsum = 0, w[MSPK_MAX_CHUNKS];
+    // (kn.weights, MSPACK_HIP_CHUNK_WEIGHTS="1,1,2,4": the shares spelled out -- sweeps)
+    for (size_t k = 0; k < want; k++) {
+      static const uint64_t ramp[MSPK_MAX_CHUNKS] = { 4, 6, 9, 13, 20, 30, 45, 67 };          // (3: every chunk half as large again)
+      static const uint64_t fall[MSPK_MAX_CHUNKS] = { 8, 6, 4, 3, 2, 2, 1, 1 };               // (4: the last chunks -- whose launches end the call -- small)
+      w[k] = (k < kn.weights.size()) ? kn.weights[k] : shape == 4 ? fall[k] : shape == 3 ? ramp[k] : shape == 1 ? (k >= 2 ? (uint64_t) 2 << (k - 1) : 2) : (shape == 2 && k == 0 && want >= 3 ? 1 : 2);
+      wsum += w[k];
+    }
+    // (a unit weighs what it reads that the NEXT unit does not start inside: a CHM's intervals are all given "to the end of the
+    // file" as input, chmd.c:1146-1149 -- by in_len alone config 3's four chunks held 77, 174, 227 and 546 of its 1024 intervals)
+    auto weight = [&](size_t i) -> uint64_t {
+      uint64_t wgt = local[i].in_len;
+      for (size_t j = i + 1; j < n_sel; j++) {
+        if (local[j].kind == MSPACK_HIP_KIND_XORSUM) continue;
+        if (local[j].in_off > local[i].in_off && local[j].in_off - local[i].in_off < wgt) wgt = local[j].in_off - local[i].in_off;
+        break;
+      }
+      return wgt;
+    };
+    uint64_t w_sum = 0;
+    for (size_t i = 0; i < n_sel; i++) if (local[i].kind != MSPACK_HIP_KIND_XORSUM) w_sum += weight(i);
+    size_t a = 0; uint64_t acc = 0, upto = 0;
+    for (size_t i = 0; i < n_sel; i++) {
+      if (local[i].kind != MSPACK_HIP_KIND_XORSUM) acc += weight(i);           // (the checksum units ride along)
+      const uint64_t goal = (uint64_t)((double) w_sum * (double)(upto + w[chunks.size()]) / (double) wsum);
+      if (i + 1 == n_sel || (acc >= goal && chunks.size() + 1 < want)) {
+        Chunk c; c.a = a; c.b = i + 1; upto += w[chunks.size()]; chunks.push_back(c); a = i + 1;
+      }
+    }
+  }
+}
+
+// the third, per chunk: spans, per-kind launch lists (longest compressed unit first: the slowest chain starts first)
+static void plan_lists(BatchPlan &p)
+{
+  const std::vector<mspack_hip_unit> &local = p.local;
+  std::vector<Chunk> &chunks = p.chunks;
+  const size_t n_sel = local.size(), n_crc = p.n_crc;
+  const uint64_t out_lo = p.out_lo;
+  std::vector<uint32_t> &order = p.order;
+  order.assign(n_sel + n_crc, 0u);
+  size_t op = 0;
+  uint64_t ci_prev_hi = out_lo == ~0ull ? 0 : out_lo;
+  for (Chunk &c : chunks) {
+    c.in_lo = ~0ull; c.in_hi = 0; c.out_lo = ~0ull; c.out_hi = 0;
+    c.fm_lo = ~(size_t) 0; c.fm_n = 0; c.has_ftab = false;
+    for (size_t i = c.a; i < c.b; i++) {
+      const mspack_hip_unit &u = local[i];
+      c.in_lo = std::min<uint64_t>(c.in_lo, u.in_off); c.in_hi = std::max<uint64_t>(c.in_hi, u.in_off + u.in_len);
+      { uint64_t tl, th; if (unit_side_table(u, tl, th)) { c.in_lo = std::min(c.in_lo, tl); c.in_hi = std::max(c.in_hi, th); } }
+      if (unit_has_ftab(u)) {
+        c.has_ftab = true;
+        c.fm_lo = std::min<size_t>(c.fm_lo, u.frame_base);          // (the chunk's table units' slots are contiguous)
+        c.fm_n += unit_frames(u);
+      }
+      if (u.kind == MSPACK_HIP_KIND_XORSUM) continue;
+      c.out_lo = std::min<uint64_t>(c.out_lo, u.out_off - unit_below(u));
+      c.out_hi = std::max<uint64_t>(c.out_hi, u.out_off + u.out_len + unit_above(u));
+    }
+    if (c.out_lo > c.out_hi) c.out_lo = c.out_hi = (ci_prev_hi);         // (a chunk of checksum units only: an empty span)
+    ci_prev_hi = c.out_hi;
+    if (c.fm_lo == ~(size_t) 0) c.fm_lo = 0;
+    c.in_lo &= ~15ull;
+    for (unsigned k = 1; k <= MSPACK_HIP_KIND_XORSUM; k++) {
+      c.order_off[k] = op;
+      for (size_t i = c.a; i < c.b; i++) if (local[i].kind == k) order[op++] = (uint32_t) i;
+      c.order_n[k] = op - c.order_off[k];
+      std::stable_sort(order.begin() + c.order_off[k], order.begin() + op, [&](uint32_t x, uint32_t y) {
+        return local[x].in_len + (local[x].out_len >> 2) > local[y].in_len + (local[y].out_len >> 2); });
+    }
+    // the digest pass's list (launched behind the codecs): the chunk's flagged units, in arena order
+    c.crc_off = op; c.crc_max = 0;
+    if (n_crc)
+      for (size_t i = c.a; i < c.b; i++)
+        if ((local[i].flags & MSPACK_HIP_UF_CRC32) && local[i].kind != 0 && local[i].kind != MSPACK_HIP_KIND_XORSUM) {
+          order[op++] = (uint32_t) i;
+          c.crc_max = std::max<uint64_t>(c.crc_max, local[i].out_len);
+        }
+    c.crc_n = op - c.crc_off;
+  }
+}
+
+// `sel` lists the unit indices of the batch (NULL = all n_sel units).  to_host: the outputs go back to the caller's host buffer;
+// dev_out: they stay in the caller's DEVICE buffer (out_off relative to it); per_unit_back: they are copied back unit by unit (one
+// chunk).  Writes frame_base into units[] too.  0, or -1 with the reason in errbuf.
+static int plan_batch(mspack_hip_unit *units, const uint32_t *sel, size_t n_sel, size_t in_bytes, size_t out_bytes, bool to_host,
+                      bool dev_out, bool per_unit_back, const PlanKnobs &kn, BatchPlan &p, char *errbuf, size_t errcap)
+{
+  if (plan_units(units, sel, n_sel, in_bytes, out_bytes, dev_out, per_unit_back, p, errbuf, errcap)) return -1;
+  plan_chunks(to_host, kn, p);
+  plan_lists(p);
+  std::vector<mspack_hip_unit> &local = p.local;
+  const uint64_t in_lo = p.in_lo, out_lo = p.out_lo;
+  for (size_t i = 0; i < n_sel; i++) {
+    { uint64_t tl, th; if (unit_side_table(local[i], tl, th)) local[i].in_chunk -= (uint32_t)(in_lo >> 2); }      // in_lo is a multiple of 16
+    local[i].in_off -= in_lo;
+    if (local[i].kind != MSPACK_HIP_KIND_XORSUM) local[i].out_off -= out_lo;
+  }
+  return 0;
+}

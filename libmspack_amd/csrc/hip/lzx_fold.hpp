@@ -1,4 +1,4 @@
-// lzx_fold.hpp -- the per-FOLDER chain of LZ77 copies cut down to one gather pass per frame (mspack_lzx_fold, shim.hip).
+// lzx_fold.hpp -- the per-FOLDER chain of LZ77 copies cut down to one gather pass per frame (mspack_lzx_fold, entry_kernels.hpp).
 // Included by lzx_pipe_resolve.hpp (plain LZX build, namespace lzxn, only); reference loops it replaces: lzxd.c:613-646 (the match copy), :565-586 (R0-R2).
 //
 // What a folder of ordinary data is bound by: frame f's matches copy bytes of frames < f, so the
@@ -15,7 +15,7 @@
 //       pass over the bytes whose sources lie in earlier frames -- 64 loads in flight, no dependent LDS step, no match logic.
 // The parse side is unchanged (lzx_pipe_parse: literals in place, one record per match); the same records, the same checks
 // (lzxd.c:613-634) and the same hand-over to the serial path (rs_* in the unit's first record) as lzx_pipe_resolve.
-// shim.hip decides per launch which of the two runs (few long units: this; many short ones: lzx_pipe_resolve).
+// entry_kernels.hpp (lzx_fold_on) decides per launch which of the two runs (few long units: this; many short ones: lzx_pipe_resolve).
 #pragma once
 
 #define LZX_SYM0 0xFFFFFFF0u                      /* "R0 / R1 / R2 as they are at the frame's first byte" (no offset is that large) */

@@ -1,4 +1,4 @@
-// lzx_pipe.hpp -- what the tasks of the frame-parallel path (mspack_lzx_pipe, shim.hip) share: the frame record and its
+// lzx_pipe.hpp -- what the tasks of the frame-parallel path (mspack_lzx_pipe, entry_kernels.hpp) share: the frame record and its
 // status word, the hand-off (lzx_status_load / lzx_status_publish), the trace macros of LZX_PIPE_TRACE builds, lzx_seek_bit
 // and lzx_side_setup.  Compiled into lzxn (resolve tasks, the unit decoder's resume) and lzxp (parse tasks).  Nothing of the
 // reference corresponds to it: lzxd.c decodes a stream front to back; what makes frames independent is lzxd.c:695-697.
@@ -64,11 +64,11 @@ struct __align__(16) LzxFrameRec {
 };
 static_assert(sizeof(LzxFrameRec) == 1408, "LzxFrameRec layout");
 // LzxFrameRec::status.  The separate header / parse launches only use 0, 2, 1.  In the dependency-driven launch
-// (mspack_lzx_pipe, shim.hip) the word is also the hand-off flag between the frame's parse task and the unit's wave:
+// (mspack_lzx_pipe, entry_kernels.hpp) the word is also the hand-off flag between the frame's parse task and the unit's wave:
 //   0 untouched | 5 a parse wave claimed the frame | 2 its code lengths are in the record, tokens still being parsed |
 //   1 tokens parsed (final) | 3 code lengths valid, no tokens (final) | 4 nothing usable (final; the chain of code
 //   lengths is broken for the rest of the reset interval) | 6 the unit's own wave took the frame (decodes it serially)
-#ifdef LZX_PIPE_TRACE      /* analysis builds: time a unit task spends waiting for parse tasks (shim.hip: g_pipe_wait) */
+#ifdef LZX_PIPE_TRACE      /* analysis builds: time a unit task spends waiting for parse tasks (entry_kernels.hpp: g_pipe_trace) */
 __device__ unsigned long long g_pipe_wait[1 << 16];
 __device__ unsigned long long g_pipe_phase[16];     /* summed over all waves: s_memrealtime ticks per phase (PH below) */
 /* (accumulated in registers, added to the global sums once per task: an atomic per stamp would serialise the waves) */

@@ -507,7 +507,7 @@ __device__ __forceinline__ void lzx_parse_emit(LzxDec &d, const bool length_empt
 // has published them (status HEADER or later), reads its own header at the position the frame table states, publishes
 // its lengths, and only then parses its tokens (lzx_parse_emit) -- so the chain costs one header per link, not one
 // frame.  It works on guesses (one block per frame, at the table's position) and gives up silently; the serial path stays the judge.
-// Waiting is safe: the task it waits for has an earlier ticket (shim.hip), i.e. a live wave is working on it.
+// Waiting is safe: the task it waits for has an earlier ticket (entry_kernels.hpp), i.e. a live wave is working on it.
 // ---------------------------------------------------------------------------------------------------
 // the rest of a frame whose first block ended inside it: header, tables, tokens -- block by block to the frame's end.  A real
 // call: frames like this are one in a few hundred, and inlined the general case's registers counted against every frame's
@@ -689,7 +689,7 @@ __device__ __forceinline__ void lzx_pipe_apply_header(LzxShared *sh, const u32 l
 
 // Returns 1 when the frame's first block ended inside it and lzx_pipe_parse_tail has to go on (its arguments wait in the stage's
 // spare words); 0 otherwise.  `spec`: the caller has read the frame's header ahead of the chain (lzx_pipe_spec_header: the
-// program is in the stage).  Both are calls of the ticket loop (shim.hip), not of this function: nested, their frames -- and the
+// program is in the stage).  Both are calls of the ticket loop (entry_kernels.hpp), not of this function: nested, their frames -- and the
 // registers this function had to save around them -- added up in every wave's scratch allocation (324 B per lane in round 5).
 #define LZX_TAIL_ARGS (LZX_STAGE_WORDS + 32u)                  /* stage words: bytes done, records, bit position, record chunks */
 __device__ u32 lzx_pipe_parse(const mspack_hip_unit &u, const mspack_hip_unit *up, const u32 f, const u8 *in_arena, u8 *out_arena,

@@ -245,7 +245,7 @@ __device__ void lzx_pipe_resolve(const mspack_hip_unit &u, const u32 f, u8 *out_
 // takes the records up WHILE the frame is parsed: lzx_parse_emit publishes, behind every pass but the last, how many match records
 // and output bytes are in memory (`prog`, with the same release recipe as a status word), and this task works through what has
 // arrived -- whole groups of 256 records -- one acquire per event.  The frame's chain is then the longer of its parse and its
-// resolve, not their sum.  Only where waves are spare (shim.hip: control word 3): a resolve wave that has started on a frame
+// resolve, not their sum.  Only where waves are spare (launch.hpp: control word 3): a resolve wave that has started on a frame
 // holds its slot until the frame's parse task is through.  Same records, same checks, same hand-over as lzx_pipe_resolve.
 // ---------------------------------------------------------------------------------------------------
 __device__ void lzx_pipe_resolve_stream(const mspack_hip_unit &u, const u32 f, u8 *out_arena, LzxFrameRec *urecs, const uint2 *pool_base, LzxResolveLds *rl)

@@ -862,7 +862,7 @@ __device__ __forceinline__ bool zip_run_tokens(ZipDec &d, const uint2 *pool_base
 }
 
 // ---------------------------------------------------------------------------------------------------
-// zip_fold_block -- the copies of CFDATA block b of a folder as a FOLD task (fold_common.hpp; mspack_mszip_fold, shim.hip): what
+// zip_fold_block -- the copies of CFDATA block b of a folder as a FOLD task (fold_common.hpp; mspack_mszip_fold, entry_kernels.hpp): what
 // zip_run_tokens does on the folder's own wave, block after block (0.25 ms per block: one folder of ordinary data at 130 MB/s),
 // done by one wave per block with only the gather of bytes that come from the block BELOW left on the folder's chain.
 // Same records, same checks as zip_run_tokens; a block is only folded when every block below it is a full one that was folded

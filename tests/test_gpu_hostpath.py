@@ -386,7 +386,7 @@ def test_many_decompressors_one_process(built, tmp_path):
     """VERDICT round 4, item 1.  25 x (create -> open -> extract -> close -> destroy) of the config-3 CHM (24 MB arena) and of a
     cabinet with a 6 MB gather arena in ONE process, against what the real chmd answered (tests/golden/chm_extract.json) and
     the cabinet's plaintext.  Round 4 failed this from the second lifetime on, intermittently: the arena's page-lock was
-    rounded outward and took in the allocator's neighbouring blocks (shim.hip: PinRange)."""
+    rounded outward and took in the allocator's neighbouring blocks (host_pins.hpp: PinRange)."""
     script = tmp_path / "w.py"
     script.write_text(LIFETIMES_WORKER % (ROOT, ROOT, ROOT))
     p = subprocess.run([sys.executable, str(script), "25"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=900)

@@ -167,7 +167,7 @@ _LAUNCH_PATHS_CACHE = None
                                  {"MSPACK_HIP_TICKET_ORDER": "2"}, {"MSPACK_HIP_NO_FRAME_PARSE": "1"}],
                          ids=["pipe", "pipe_no_stream", "level_order", "mixed_sections", "unit_major", "serial"])
 def test_launch_paths_same_bytes(built, env, tmp_path_factory):
-    """shim.hip launch_kind: the shipped default (mspack_lzx_pipe: one dependency-driven launch) and the serial kernel alone
+    """launch.hpp launch_kind: the shipped default (mspack_lzx_pipe: one dependency-driven launch) and the serial kernel alone
     (MSPACK_HIP_NO_FRAME_PARSE; round 2's header / parse / unit kernels in a row were removed in round 4) --
     same results, on launches smaller than, about and larger than the chip, and on units of three frames; launches with a wave for
     every ticket (300 units of three frames, 1024 of two) take their frames up while they are parsed (lzx_pipe_resolve_stream, round 6) --

@@ -1,5 +1,5 @@
 """scratch (GPU box): where do the fold tasks pay?  n folders of f frames each (text, LZX-21 with blocks of 1 MiB; MSZIP with history) through
-mspack_hip_decode_batch -- run it with MSPACK_HIP_FOLD=0, 1 and 2 and compare (the rule: shim.hip, lzx_fold_on).
+mspack_hip_decode_batch -- run it with MSPACK_HIP_FOLD=0, 1 and 2 and compare (the rule: entry_kernels.hpp, lzx_fold_on).
   MSPACK_HIP_FOLD=1 python tools/fold_policy_sweep.py"""
 import os, sys, time, zlib
 import numpy as np
