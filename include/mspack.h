@@ -180,6 +180,29 @@ struct mscab_decompressor {
   int (*last_error)(struct mscab_decompressor *self);
 };
 
+/* extension of this library (a plain function: struct mscab_decompressor keeps the reference's layout).
+ *
+ * Gather every not-yet-decoded folder of the given cabinets into ONE GPU batch, so that the extract() calls
+ * that follow are slices of it.  Advice: what extract() returns, writes and says is the same with and without it.
+ *
+ * Without it a batch is formed by the first extract() that touches a cabinet, of that cabinet's folders (or its set's):
+ * a directory of thousands of small cabinets is then thousands of batches of one or two folders each.
+ *   cabs[i]   cabinets this decompressor opened or found with search().  A member of a set joined with append() / prepend()
+ *             stands for the set's folder list; an entry given twice, or two members of one set, are harmless, and so are
+ *             folders that are decoded already or part of a batch that is still running.
+ *   folders   stored folders are streamed as ever and are left out, as are folders continued from a cabinet that is not
+ *             joined; a folder whose cabinet file cannot be opened stays undecoded, and its extract() reports that.
+ *             Folders are taken in argument order, then in list order, while their estimated decoded size (32 KiB per CFDATA
+ *             block) fits MSCABD_PARAM_HIP_CACHE_MB; the others are decoded on demand by extract().
+ *   params    MSCABD_PARAM_FIXMSZIP, _SALVAGE, _DECOMPBUF and _HIP_DEVICES are read when the batch is built, i.e. here (as
+ *             a cabinet's first extract() reads them): set them first.
+ *   returns   MSPACK_ERR_OK (also for n_cabs == 0 and when nothing is left to decode: no batch is started then);
+ *             MSPACK_ERR_ARGS for self == NULL, n_cabs < 0, cabs == NULL with n_cabs > 0 or a NULL entry (nothing is gathered);
+ *             MSPACK_ERR_NOMEMORY; MSPACK_ERR_DECRUNCH when the batch call itself failed.  last_error() answers the same.
+ * With at least two folders on one device the batch runs as a job: the call returns at once and each extract() waits for
+ * its own folder only.  Closing a cabinet while the batch runs takes its folders out of it; the other cabinets' stay. */
+extern int mspack_cabd_prefetch(struct mscab_decompressor *self, struct mscabd_cabinet **cabs, int n_cabs);
+
 /* ---- CHM ---------------------------------------------------------------------------------------------- */
 struct mschm_decompressor;
 struct mschmd_header;

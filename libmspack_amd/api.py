@@ -104,6 +104,7 @@ MschmDecompressor._fields_ = [
 
 MSCABD_PARAM_SEARCHBUF, MSCABD_PARAM_FIXMSZIP, MSCABD_PARAM_DECOMPBUF, MSCABD_PARAM_SALVAGE = 0, 1, 2, 3
 MSCABD_PARAM_HIP_DEVICES, MSCABD_PARAM_HIP_CACHE_MB = 100, 101
+MSPACK_ERR_OK, MSPACK_ERR_ARGS = 0, 1
 
 
 def _setup(L=None):
@@ -117,6 +118,8 @@ def _setup(L=None):
     L.mspack_create_chm_decompressor.restype = _P(MschmDecompressor)
     L.mspack_create_chm_decompressor.argtypes = [C.c_void_p]
     L.mspack_destroy_chm_decompressor.argtypes = [_P(MschmDecompressor)]
+    L.mspack_cabd_prefetch.restype = C.c_int
+    L.mspack_cabd_prefetch.argtypes = [_P(MscabDecompressor), _P(_P(MscabdCabinet)), C.c_int]
     L.mspack_version.argtypes = [C.c_int]
     L.mspack_sys_selftest_internal.argtypes = [C.c_int]
     return L
@@ -318,6 +321,14 @@ class CabSet:
 
     def prepend(self, a, b):
         return self.d.contents.prepend(self.d, self._cab(a), self._cab(b))
+
+    def prefetch(self, indices=None):
+        """mspack_cabd_prefetch (mspack.h): the not-yet-decoded folders of these cabinets (indices into the list given to the
+        constructor; None = all that opened) in ONE batch; the extract() calls that follow are slices of it -> MSPACK_ERR_*"""
+        if indices is None:
+            indices = [i for i, c in enumerate(self.cabs) if c]
+        arr = (_P(MscabdCabinet) * max(len(indices), 1))(*[self.cabs[i] for i in indices])
+        return self.L.mspack_cabd_prefetch(self.d, arr, len(indices))
 
     def file_ptrs(self, i):
         return list(_walk(self.cabs[i].contents.files))

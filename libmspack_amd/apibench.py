@@ -30,6 +30,8 @@ def lib():
         for fn in (L.mspk_api_bench_cab, L.mspk_api_bench_chm):
             fn.restype = C.c_int
             fn.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint, C.POINTER(Stats)]
+        L.mspk_api_bench_cabs.restype = C.c_int
+        L.mspk_api_bench_cabs.argtypes = [C.c_void_p, C.c_void_p, C.c_uint, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(Stats)]
         L.mspk_api_cab_run.restype = C.c_int
         L.mspk_api_cab_run.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]
@@ -62,6 +64,32 @@ def run(kind, image, out_cap, max_files=65536):
     rc = fn(image.ctypes.data, image.size, out.ctypes.data, int(out_cap), offs.ctypes.data, max_files + 1, C.byref(st))
     d = {k: getattr(st, k) for k, _t in Stats._fields_}
     return rc, out[:st.bytes_out], offs[:min(st.n_files, max_files) + 1], d
+
+
+def run_cabs(images, out_cap, prefetch, L=None):
+    """MANY cabinet images on one decompressor (mspk_api_bench_cabs): open all, [mspack_cabd_prefetch of all], extract every file,
+    cabinet by cabinet.  -> (rc, out uint8[bytes_out], stats dict; first_extract_s is the prefetch's time when there was one)"""
+    L = L or lib()
+    offs = np.zeros(len(images) + 1, dtype=np.uint64)
+    offs[1:] = np.cumsum([len(i) for i in images])
+    blob = np.frombuffer(b"".join(bytes(i) for i in images), dtype=np.uint8)
+    out = np.zeros(int(out_cap) + 64, dtype=np.uint8)
+    st = Stats()
+    rc = L.mspk_api_bench_cabs(blob.ctypes.data, offs.ctypes.data, len(images), int(bool(prefetch)), out.ctypes.data, int(out_cap), C.byref(st))
+    return rc, out[:st.bytes_out], {k: getattr(st, k) for k, _t in Stats._fields_}
+
+
+def build_small_cabs(M, n=4096, ub=32768, plain=None):
+    """config 2's plaintext as n cabinets of ONE folder of one MSZIP CFDATA block of ub bytes and one file each.  -> ([image], plaintext)"""
+    import zlib
+    if plain is None:
+        plain = M.gen_plaintext(0xC0FFEE, 0, n * ub)
+    images = []
+    for i in range(n):
+        co = zlib.compressobj(6, zlib.DEFLATED, -15)
+        blob = b"CK" + co.compress(plain[i * ub:(i + 1) * ub].tobytes()) + co.flush()
+        images.append(M.cab_write([(1, [blob], [ub])], [(b"f%05d.bin" % i, ub, 0, 0)]))
+    return images, plain
 
 
 def summary(d, reps_note=""):

@@ -32,12 +32,14 @@ typedef struct mspk_api_stats {
 struct mem_sys {
   struct mspack_system sys;
   const unsigned char *image; size_t image_len;
+  /* (mspk_api_bench_cabs: many images, back to back in `image`; image k is image[many_offs[k] .. many_offs[k + 1]), its name "c<k>") */
+  const unsigned long long *many_offs; unsigned int n_many;
   unsigned char *out; size_t out_cap, out_len;
   double read_s, write_s;
   unsigned long long bytes_read;
   unsigned int n_messages;
 };
-struct mem_file { struct mem_sys *ms; int writing; size_t pos; };
+struct mem_file { struct mem_sys *ms; int writing; size_t pos; const unsigned char *img; size_t img_len; };
 
 static double now_s(void) { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return (double) ts.tv_sec + 1e-9 * (double) ts.tv_nsec; }
 
@@ -46,9 +48,15 @@ static struct mspack_file *ms_open(struct mspack_system *self, const char *filen
   struct mem_sys *ms = (struct mem_sys *) self;
   struct mem_file *f;
   const int writing = mode == MSPACK_SYS_OPEN_WRITE || mode == MSPACK_SYS_OPEN_APPEND || mode == MSPACK_SYS_OPEN_UPDATE;
-  if (!writing && strcmp(filename, "in") != 0) return NULL;
+  const unsigned char *img = ms->image; size_t img_len = ms->image_len;
+  if (!writing && ms->many_offs && filename[0] == 'c') {
+    const unsigned long k = strtoul(filename + 1, NULL, 10);
+    if (k >= ms->n_many) return NULL;
+    img = ms->image + ms->many_offs[k]; img_len = (size_t)(ms->many_offs[k + 1] - ms->many_offs[k]);
+  }
+  else if (!writing && strcmp(filename, "in") != 0) return NULL;
   if (!(f = (struct mem_file *) malloc(sizeof(*f)))) return NULL;
-  f->ms = ms; f->writing = writing; f->pos = 0;
+  f->ms = ms; f->writing = writing; f->pos = 0; f->img = img; f->img_len = img_len;
   return (struct mspack_file *) f;
 }
 static void ms_close(struct mspack_file *file) { free(file); }
@@ -59,9 +67,9 @@ static int ms_read(struct mspack_file *file, void *buffer, int bytes)
   const double t0 = now_s();
   size_t n;
   if (f->writing || bytes < 0) return -1;
-  n = ms->image_len - f->pos;
+  n = f->img_len - f->pos;
   if (n > (size_t) bytes) n = (size_t) bytes;
-  memcpy(buffer, ms->image + f->pos, n);
+  memcpy(buffer, f->img + f->pos, n);
   f->pos += n; ms->bytes_read += n;
   ms->read_s += now_s() - t0;
   return (int) n;
@@ -81,9 +89,9 @@ static int ms_write(struct mspack_file *file, void *buffer, int bytes)
 static int ms_seek(struct mspack_file *file, off_t offset, int mode)
 {
   struct mem_file *f = (struct mem_file *) file;
-  off_t base = mode == MSPACK_SYS_SEEK_START ? 0 : (mode == MSPACK_SYS_SEEK_CUR ? (off_t) f->pos : (off_t) f->ms->image_len);
+  off_t base = mode == MSPACK_SYS_SEEK_START ? 0 : (mode == MSPACK_SYS_SEEK_CUR ? (off_t) f->pos : (off_t) f->img_len);
   if (f->writing) return -1;
-  if (base + offset < 0 || (size_t)(base + offset) > f->ms->image_len) return -1;
+  if (base + offset < 0 || (size_t)(base + offset) > f->img_len) return -1;
   f->pos = (size_t)(base + offset);
   return 0;
 }
@@ -169,6 +177,57 @@ int mspk_api_bench_cab(const unsigned char *cab, size_t cab_len, unsigned char *
   mspack_destroy_cab_decompressor(d);
   finish(&ms, st, t0);
   return 0;
+}
+
+/* MANY cabinet images on ONE decompressor -- the directory of small cabinets: open them all, then extract every file, cabinet by
+ * cabinet.  prefetch == 0: every cabinet's first extract() forms its own batch; != 0: mspack_cabd_prefetch() of all of them first
+ * (its time is reported as first_extract_s).  images: the cabinets back to back, image k = [offs[k], offs[k + 1]). */
+int mspk_api_bench_cabs(const unsigned char *images, const unsigned long long *offs, unsigned int n_cabs, int prefetch,
+                        unsigned char *out, size_t out_cap, mspk_api_stats *st)
+{
+  struct mem_sys ms;
+  struct mscab_decompressor *d;
+  struct mscabd_cabinet **cabs;
+  char (*names)[12];
+  unsigned int k;
+  double t0, t1;
+  int rc = 0;
+  memset(st, 0, sizeof(*st));
+  mem_sys_init(&ms, images, (size_t) offs[n_cabs], out, out_cap);
+  ms.many_offs = offs; ms.n_many = n_cabs;
+  cabs = (struct mscabd_cabinet **) calloc(n_cabs ? n_cabs : 1, sizeof(*cabs));
+  names = (char (*)[12]) calloc(n_cabs ? n_cabs : 1, sizeof(*names));         /* (they must outlive the cabinets) */
+  if (!cabs || !names) { free(cabs); free(names); return -1; }
+  mspack_hip_host_path_stats(NULL, 1);
+  t0 = now_s();
+  if (!(d = mspack_create_cab_decompressor(&ms.sys))) { free(cabs); free(names); return -1; }
+  t1 = now_s();
+  for (k = 0; k < n_cabs && !rc; k++) {
+    snprintf(names[k], sizeof(names[k]), "c%u", k);
+    if (!(cabs[k] = d->open(d, names[k]))) { st->first_error = d->last_error(d); rc = -2; }
+  }
+  st->open_s = now_s() - t1;
+  if (!rc && prefetch) {
+    const double e0 = now_s();
+    const int err = mspack_cabd_prefetch(d, cabs, (int) n_cabs);
+    st->first_extract_s = now_s() - e0;
+    if (err) { st->first_error = err; rc = -3; }
+  }
+  for (k = 0; k < n_cabs && !rc; k++) {
+    struct mscabd_file *f;
+    for (f = cabs[k]->files; f; f = f->next) {
+      const double e0 = now_s();
+      const int err = d->extract(d, f, "out");
+      if (st->n_files == 0 && !prefetch) st->first_extract_s = now_s() - e0;
+      if (err) { if (!st->n_errors) st->first_error = err; st->n_errors++; }
+      st->n_files++;
+    }
+  }
+  for (k = 0; k < n_cabs; k++) if (cabs[k]) d->close(d, cabs[k]);
+  mspack_destroy_cab_decompressor(d);
+  finish(&ms, st, t0);
+  free(cabs); free(names);
+  return rc;
 }
 
 /* one CHM image: open, extract every file of the directory in list order */

@@ -13,6 +13,8 @@
  * and every extract() is then a slice of that result.  A unit's result tells how far it decoded
  * without error; files that end inside that prefix succeed exactly as they do in the reference
  * (which never decodes further than asked), later ones return the unit's error.
+ * mspack_cabd_prefetch() (mspack.h) forms the same batch over the folders of MANY cabinets before the first extract():
+ * decode_cabinets() is the one routine behind both.
  * Cabinet sets: append()/prepend() join cabinets and merge a folder that
  * continues across them (reference cabd.c:870-1064); a merged folder is a list of (cabinet, offset)
  * segments, and a CFDATA block with uncompressed size 0 continues as the first block of the next
@@ -71,10 +73,11 @@ struct folder_p {
   unsigned int n_marks;
   unsigned int *marks;
   const unsigned char *mark_log;
-  /* (decode_cabinet: how many of the cabinet's files lie in this folder and the first of them in list order -- one pass over the
+  /* (decode_cabinets: how many of the cabinet's files lie in this folder and the first of them in list order -- one pass over the
    * file list for all folders, so that a folder's files are found without walking the whole list per folder) */
   unsigned int file_count;
   struct mscabd_file *first_file;
+  unsigned int listed;                /* (mspack_cabd_prefetch: cabd_p.list_stamp of the call that last saw the folder's list) */
   /* the folder's batch while it is still running (mspack_hip.h: jobs): unit job_k of it -- not decoded yet, and not to be gathered
    * again; folder_settle() waits for the unit and takes its result over */
   struct cab_batch *job;
@@ -112,6 +115,7 @@ struct cabd_p {
   int error, read_error;
   int searchbuf_size, fix_mszip, buf_size, salvage;
   int devices, cache_mb;
+  unsigned int list_stamp;            /* mspack_cabd_prefetch: one number per call, to tell a folder list that is named twice */
   /* stored (uncompressed) folders need no codec and are streamed exactly like the reference does it,
    * including what a later extract() sees after a failed one (cabd.c:1283-1345, 1530-1541) */
   struct blk_reader st;
@@ -172,9 +176,9 @@ static char *read_cstring(struct mspack_system *sys, struct mspack_file *fh, int
   return str;
 }
 
-static void batch_abandon(struct mspack_system *sys, struct cab_batch *B);
+static void batch_detach(struct mspack_system *sys, struct folder_p *f);
 static void free_folder_cache(struct mspack_system *sys, struct folder_p *f) {
-  if (f->job) batch_abandon(sys, f->job);                 /* (its batch is still running: to its end, nothing of it kept) */
+  if (f->job) batch_detach(sys, f);                       /* (its batch is still running -- for the other folders in it) */
   if (f->store && --f->store->refs == 0) { mspack_arena_free(sys, f->store->base); sys->free(f->store); }
   f->store = NULL; f->dec = NULL; f->decoded = 0;
   sys->free(f->rep); f->rep = NULL; f->rep_n = 0;
@@ -776,7 +780,7 @@ static void gather_marks(struct mspack_system *sys, struct cab_p *cab, struct ga
   unsigned int *v;
   g->n_marks = 0; g->marks = NULL; g->marks_off = 0;
   (void) cab;
-  nf = g->fol->file_count;                     /* (counted by decode_cabinet in one pass over the list) */
+  nf = g->fol->file_count;                     /* (counted by decode_cabinets in one pass over the lists) */
   if (!nf || !(v = (unsigned int *) sys->alloc(sys, 2 * nf * sizeof(unsigned int)))) return;
   for (f = g->fol->first_file, i = 0; f && i < nf; f = f->next) {
     if ((struct folder_p *) f->folder != g->fol) continue;
@@ -929,7 +933,8 @@ static int gather_folder(struct cabd_p *self, struct gathered *g, struct in_aren
   return err;
 }
 
-/* one batch of a cabinet's folders: what it reads (units, the input arena with the block parts' checksums noted in it), what it
+/* one batch of folders (a cabinet's, or those of several cabinets: mspack_cabd_prefetch): what it reads (units, the input arena
+ * with the block parts' checksums noted in it), what it
  * writes (results, the output arena = the folders' decoded bytes afterwards) and, while it runs as a job, the job */
 struct cab_batch {
   struct mspack_system *sys;
@@ -987,8 +992,11 @@ static void batch_take_folder(struct cab_batch *B, size_t k)
   fp->decoded = 1;
 }
 
-/* decode every not-yet-decoded folder of `cab` (budget permitting, `want` always) in ONE batch */
-static int decode_cabinet(struct cabd_p *self, struct cab_p *cab, struct folder_p *want)
+/* decode every not-yet-decoded folder of the cabinets cabs[0 .. n_cabs) -- no folder list named twice -- in ONE batch: in
+ * argument order, then in list order, budget permitting (`used` of it is taken already), `want` always.  extract() comes here with
+ * its folder's cabinet and want = that folder; mspack_cabd_prefetch() with a list and want = NULL -- then no folder's failure ends
+ * the call: one whose cabinet cannot be opened stays undecoded, for its extract() to report. */
+static int decode_cabinets(struct cabd_p *self, struct cab_p **cabs, size_t n_cabs, struct folder_p *want, size_t used)
 {
   struct mspack_system *sys = self->system;
   struct mscabd_folder *fo;
@@ -999,32 +1007,34 @@ static int decode_cabinet(struct cabd_p *self, struct cab_p *cab, struct folder_
   struct ck_list ck = { NULL, 0, 0, 0 };
   struct cab_batch B;
   unsigned char *out_arena = NULL;
-  size_t n = 0, k, out_bytes = 0, budget = (size_t) self->cache_mb << 20, used = 0, nu;
+  size_t n = 0, k, c, out_bytes = 0, budget = (size_t) self->cache_mb << 20, nu;
+  size_t kept = used;                                   /* what the folders this call decodes have taken of the budget */
   int err = MSPACK_ERR_OK, rc, again = 0;
 
   size_t n_qtm_files = 0;                               /* files in Quantum folders: two marks each at most (gather_marks) */
-  for (fo = cab->base.folders; fo; fo = fo->next) { n++; ((struct folder_p *) fo)->file_count = 0; ((struct folder_p *) fo)->first_file = NULL; }
-  {
+  for (c = 0; c < n_cabs; c++) {
     struct mscabd_file *fi;
-    for (fi = cab->base.files; fi; fi = fi->next) {
+    for (fo = cabs[c]->base.folders; fo; fo = fo->next) { n++; ((struct folder_p *) fo)->file_count = 0; ((struct folder_p *) fo)->first_file = NULL; }
+    for (fi = cabs[c]->base.files; fi; fi = fi->next) {
       struct folder_p *fp = (struct folder_p *) fi->folder;
       if (fp && !fp->file_count++) fp->first_file = fi;
       if (fp && (fp->base.comp_type & 0x0F) == MSCAB_COMP_QUANTUM) n_qtm_files++;
     }
+    /* (first guess for the arena: the cabinets' stated lengths, within reason -- it grows when that was wrong or the folders
+     *  go on in other cabinets) */
+    A.cap += (size_t) cabs[c]->base.length;
+    if (A.cap > ((size_t) 256 << 20)) A.cap = (size_t) 256 << 20;
   }
   gs = (struct gathered *) sys->alloc(sys, n * sizeof(*gs));
   units = NULL; res = NULL;                              /* (sized once the gather knows how many checksum units ride along) */
-  /* (first guess for the arena: the cabinet's stated length, within reason -- it grows when that was wrong or the folders
-   *  go on in other cabinets) */
-  A.cap = (size_t) cab->base.length;
-  if (A.cap > ((size_t) 256 << 20)) A.cap = (size_t) 256 << 20;
   /* (room for the Quantum folders' tables of marks too: an arena that has to grow is allocated anew -- page-locked -- and copied:
    * 170 ms for config 4's 190 MB when the tables' 131 KB did not fit the first guess) */
   A.cap += n * 96 + 65536 + 8 * n_qtm_files + 16 * n;
   A.p = (unsigned char *) mspack_arena_alloc(sys, A.cap);
   if (!gs || !A.p) { sys->free(gs); mspack_arena_free(sys, A.p); return MSPACK_ERR_NOMEMORY; }
   n = 0;
-  for (fo = cab->base.folders; fo; fo = fo->next) {
+  for (c = 0; c < n_cabs && !err; c++)
+  for (fo = cabs[c]->base.folders; fo; fo = fo->next) {
     struct folder_p *fp = (struct folder_p *) fo;
     size_t est = (size_t) fo->num_blocks * CAB_BLOCKMAX;
     if (fp->decoded || fp->job) continue;
@@ -1039,7 +1049,7 @@ static int decode_cabinet(struct cabd_p *self, struct cab_p *cab, struct folder_
     if (err == MSPACK_ERR_OPEN && fp != want) { err = MSPACK_ERR_OK; continue; }   /* that folder stays undecoded */
     if (err) break;
     gs[n].n_marks = 0; gs[n].marks = NULL; gs[n].marks_off = 0;
-    if ((fo->comp_type & 0x0F) == MSCAB_COMP_QUANTUM) gather_marks(sys, cab, &gs[n], &A);
+    if ((fo->comp_type & 0x0F) == MSCAB_COMP_QUANTUM) gather_marks(sys, fp->data.cab, &gs[n], &A);
     used += est;
     n++;
   }
@@ -1151,6 +1161,7 @@ static int decode_cabinet(struct cabd_p *self, struct cab_p *cab, struct folder_
         if (mine) continue;
       }
       batch_take_folder(&B, k);
+      kept += (size_t) fp->base.num_blocks * CAB_BLOCKMAX;
     }
     if (B.store && B.store->refs) out_arena = NULL;        /* the folders own it now */
     else if (B.store) sys->free(B.store);
@@ -1158,11 +1169,17 @@ static int decode_cabinet(struct cabd_p *self, struct cab_p *cab, struct folder_
   for (k = 0; k < n; k++) { sys->free(gs[k].boff); sys->free(gs[k].marks); }
   sys->free(gs); sys->free(units); sys->free(res); sys->free(ck.p); mspack_arena_free(sys, A.p); mspack_arena_free(sys, out_arena);
   /* (the folders flagged above defer nothing the second time: one more round at most) */
-  if (!err && again) return decode_cabinet(self, cab, want);
+  /* (a list without `want` keeps to its budget in that round: the folders this one decoded have had their share of it) */
+  if (!err && again) return decode_cabinets(self, cabs, n_cabs, want, want ? 0 : kept);
   return err;
 }
 
-/* ---- a cabinet's batch as a job ---- */
+static int decode_cabinet(struct cabd_p *self, struct cab_p *cab, struct folder_p *want)
+{
+  return decode_cabinets(self, &cab, 1, want, 0);
+}
+
+/* ---- a batch as a job ---- */
 /* the batch to its end and everything it held given back; the folders that have not taken their results stay undecoded */
 static void batch_release(struct mspack_system *sys, struct cab_batch *B)
 {
@@ -1177,7 +1194,15 @@ static void batch_release(struct mspack_system *sys, struct cab_batch *B)
   if (B->store && --B->store->refs == 0) { mspack_arena_free(sys, B->store->base); sys->free(B->store); }
   sys->free(B);
 }
-static void batch_abandon(struct mspack_system *sys, struct cab_batch *B) { batch_release(sys, B); }
+/* a folder leaves (its cabinet is closed, or joined to another) while its batch runs: the batch goes on for the other folders in
+ * it, which may be other cabinets' -- it owns its arenas, units and results, and with gs[k].fol gone nothing in it points to the
+ * folder or its cabinet any more (the checksum parts name their folder by its index in the batch).  The last one out releases. */
+static void batch_detach(struct mspack_system *sys, struct folder_p *f)
+{
+  struct cab_batch *B = f->job;
+  B->gs[f->job_k].fol = NULL; f->job = NULL;
+  if (--B->left == 0) batch_release(sys, B);
+}
 
 /* a folder whose batch is still running: wait for its unit (and its blocks' checksum units), take the result over.  Returns 0 with
  * the folder decoded -- or flagged and NOT decoded (a block failed its checksum on the device: the caller has it gathered again,
@@ -1429,6 +1454,39 @@ static int cabd_error(struct mscab_decompressor *base) {
   return self ? self->error : MSPACK_ERR_ARGS;
 }
 
+/* mspack.h: the not-yet-decoded folders of many cabinets in ONE batch -- what the first extract() does for its own cabinet
+ * (decode_cabinet), said by the caller for a list of them.  Advice: it says nothing through sys->message that the extract() calls
+ * would not have said, and a folder it leaves out (budget, a cabinet that cannot be opened) is decoded at its extract() as ever. */
+int mspack_cabd_prefetch(struct mscab_decompressor *base, struct mscabd_cabinet **cabs, int n_cabs)
+{
+  struct cabd_p *self = (struct cabd_p *) base;
+  struct mspack_system *sys;
+  struct cab_p **list;
+  size_t n = 0;
+  int i, todo = 0, err;
+  if (!self) return MSPACK_ERR_ARGS;
+  if (n_cabs < 0 || (n_cabs > 0 && !cabs)) return self->error = MSPACK_ERR_ARGS;
+  for (i = 0; i < n_cabs; i++) if (!cabs[i]) return self->error = MSPACK_ERR_ARGS;
+  if (n_cabs == 0) return self->error = MSPACK_ERR_OK;
+  sys = self->system;
+  if (!(list = (struct cab_p **) sys->alloc(sys, (size_t) n_cabs * sizeof(*list)))) return self->error = MSPACK_ERR_NOMEMORY;
+  /* every folder list once: the members of a set show the same list (cabd_merge), and an entry may be there twice */
+  if (!++self->list_stamp) ++self->list_stamp;
+  for (i = 0; i < n_cabs; i++) {
+    struct mscabd_folder *fo = cabs[i]->folders;
+    if (!fo || ((struct folder_p *) fo)->listed == self->list_stamp) continue;
+    for (; fo; fo = fo->next) {
+      struct folder_p *fp = (struct folder_p *) fo;
+      fp->listed = self->list_stamp;
+      if (!fp->decoded && !fp->job && (fo->comp_type & 0x0F) != MSCAB_COMP_NONE && !fp->merge_prev) todo = 1;
+    }
+    list[n++] = (struct cab_p *) cabs[i];
+  }
+  err = todo ? decode_cabinets(self, list, n, NULL, 0) : MSPACK_ERR_OK;
+  sys->free(list);
+  return self->error = err;
+}
+
 struct mscab_decompressor *mspack_create_cab_decompressor(struct mspack_system *sys)
 {
   struct cabd_p *self;
@@ -1446,7 +1504,7 @@ struct mscab_decompressor *mspack_create_cab_decompressor(struct mspack_system *
   self->system = sys;
   self->error = MSPACK_ERR_OK; self->read_error = MSPACK_ERR_OK;
   self->searchbuf_size = 32768; self->fix_mszip = 0; self->buf_size = 4096; self->salvage = 0;
-  self->devices = 1; self->cache_mb = 2048;
+  self->devices = 1; self->cache_mb = 2048; self->list_stamp = 0;
   memset(&self->st, 0, sizeof(self->st)); self->st_offset = 0; self->st_active = 0; self->last_folder = NULL;
   self->msg_folder = NULL; self->msg_offset = 0; self->msg_next = 0; self->msg_next_ck = 0;
   self->live_folder = NULL; self->live_offset = 0; self->live_failed = 0; self->live_err = MSPACK_ERR_OK;
