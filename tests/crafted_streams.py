@@ -7,7 +7,10 @@ a table, mod-17 deltas and a repeat code at position 0 can be forced), the token
 Written from the format (lzxd.c:138-183, 440-740; mszipd.c:100-360; readhuff.h make_decode_table); the expected plaintext
 is a small LZ77 expansion of the tokens here, E8 translation included, and None for cases that must fail.
 
-case() objects: name, codec ('lzx' | 'lzxd' | 'mszip'), stream (bytes, zero-padded), out_len, wb, reset, ref (DELTA
+LZSS and KWAJ LZH (lzssd.c, kwajd.c) have writers of their own further down: items and trees are explicit there too, the
+plaintext is the byte-serial ring rule, and a case carries the rooms its unit is given (the streams state no length).
+
+case() objects: name, codec ('lzx' | 'lzxd' | 'mszip' | 'qtm' | 'lzss' | 'lzh'), stream (bytes, zero-padded), out_len, wb, reset, ref (DELTA
 reference data), tab (frame table: LZX offsets at every 16-bit re-alignment / MSZIP 'CK' offsets), plain (bytes or None),
 err (the error code the decoders must report), props (what the case is about, checked by the CPU test)."""
 import bisect
@@ -862,10 +865,11 @@ def qtm_read_maxima(stream, out_len, wb):
 
 # ---- the cases --------------------------------------------------------------------------------------------------------
 class Case:
-    def __init__(self, name, codec, stream, out_len, wb=0, reset=0, ref=b"", tab=(), plain=None, err=ERR_OK, props=None):
+    def __init__(self, name, codec, stream, out_len, wb=0, reset=0, ref=b"", tab=(), plain=None, err=ERR_OK, props=None, rooms=()):
         self.name, self.codec, self.stream, self.out_len = name, codec, stream, out_len
         self.wb, self.reset, self.ref, self.tab, self.plain, self.err = wb, reset, bytes(ref), list(tab), plain, err
         self.props = props or {}
+        self.rooms = list(rooms)       # LZSS / LZH (wb: the LZSS mode): the rooms the unit is given, the first one ample
 
     def __repr__(self):
         return "Case(%s)" % self.name
@@ -1678,5 +1682,706 @@ def qtm_cases():
     return C
 
 
+# ---- LZSS and KWAJ LZH (lzssd.c:36-91, kwajd.c:444-547) -------------------------------------------------------------------
+ERR_ARGS, ERR_DATAFORMAT = 1, 8
+LZH_NSYMS = (16, 16, 32, 64, 256)          # MATCHLEN1, MATCHLEN2, LITLEN, OFFSET, LITERAL
+LZH_TABLEBITS = 9                          # KWAJ_TABLEBITS
+
+
+def _nz(seed, n):
+    """n bytes that are neither 0x00 nor 0x20: a dropped or stray byte cannot hide as a zero or a space"""
+    r = random.Random(seed)
+    return bytes(r.choice(_NZ) for _ in range(n))
+
+
+_NZ = [b for b in range(1, 256) if b != 0x20]
+
+
+class Lzss:
+    """items lit(b), match(distance, len), raw(mpos, len); control bytes LSB first, 1 = literal (mode 1: inverted).  The plaintext
+    is the byte-serial ring rule: window[pos] = window[mpos], both advancing, over 4096 spaces; first pos 4096-16 (mode 2: -18)."""
+
+    def __init__(self, mode=0):
+        self.mode = mode
+        self.start = 4096 - (18 if mode == 2 else 16)
+        self.win = bytearray(b" " * 4096)
+        self.plain = bytearray()
+        self.items = []                # (is literal, the item's bytes, plaintext length behind it)
+        self.fill = 0                  # the unused high bits of a last, partial control byte
+        self.props = dict(distances={}, before_start=[], straddle=[], ctrl=set(), in_match=[], d1_behind_literal=0,
+                          reads_previous_match=0)
+
+    def _put(self, b):
+        self.win[(self.start + len(self.plain)) & 4095] = b
+        self.plain.append(b)
+
+    def lit(self, b):
+        self._put(b)
+        self.items.append((1, bytes([b]), len(self.plain)))
+
+    def lits(self, data):
+        for b in data:
+            self.lit(b)
+
+    def raw(self, mpos, n):
+        assert 0 <= mpos < 4096 and 3 <= n <= 18
+        P = len(self.plain)
+        pos = (self.start + P) & 4095
+        d = ((pos - mpos - 1) & 4095) + 1
+        p = self.props
+        p["distances"].setdefault(n, set()).add(d)
+        if d > P:
+            p["before_start"].append(P)
+            if P and d - P < n:
+                p["straddle"].append(P)
+        p["in_match"].append(P + n // 2)
+        k = len(self.items) & 7
+        if k and self.items[-1][0] and d == 1:
+            p["d1_behind_literal"] += 1
+        if k and not self.items[-1][0] and d <= self._last_len:
+            p["reads_previous_match"] += 1
+        self._last_len = n
+        for j in range(n):
+            self._put(self.win[(mpos + j) & 4095])
+        self.items.append((0, bytes([mpos & 0xFF, ((mpos >> 4) & 0xF0) | (n - 3)]), len(self.plain)))
+
+    def match(self, d, n):
+        assert 1 <= d <= 4096
+        self.raw((self.start + len(self.plain) - d) & 4095, n)
+
+    def stream(self):
+        out, inv = bytearray(), 0xFF if self.mode == 1 else 0
+        self.ends = []                 # per item: (where it ends in the stream, plaintext length behind it)
+        for g in range(0, len(self.items), 8):
+            grp = self.items[g:g + 8]
+            c = sum(1 << i for i, it in enumerate(grp) if it[0])
+            if len(grp) < 8:
+                c |= (self.fill << len(grp)) & 0xFF
+            else:
+                self.props["ctrl"].add(c)
+            out.append(c ^ inv)
+            for it in grp:
+                out += it[1]
+                self.ends.append((len(out), it[2]))
+        return bytes(out)
+
+
+def _rooms(n, inside=()):
+    """ample, exactly what the stream produces, one byte less, a room that ends inside a match (or inside the output), none"""
+    r = [n + 64, n, n - 1] + [x for x in inside if 0 < x < n][:1] + [n // 2, 0]
+    out = []
+    for x in r:
+        if x >= 0 and x not in out:
+            out.append(x)
+    return out
+
+
+def _lzss_case(name, z, cut=None):
+    s = z.stream()
+    plain = bytes(z.plain)
+    if cut is not None:                # a prefix of the stream: the items that are whole in it
+        s = s[:cut]
+        plain = plain[:max([pl for end, pl in z.ends if end <= cut] or [0])]
+    inside = [x for x in z.props["in_match"] if x < len(plain)]
+    props = dict(z.props, in_used=len(s))                 # (an LZSS stream is always read to its end)
+    return Case(name, "lzss", s, len(plain), wb=z.mode, plain=plain, props=props,
+                rooms=_rooms(len(plain), inside[len(inside) // 2:]))
+
+
+def _lzss_control_bytes(mode):
+    """every control byte value, each with its eight items; matches right behind a literal of their group (d = 1), matches that
+    read what the match before them in the group wrote, others anywhere in the 4096 bytes behind them"""
+    r = random.Random(77)
+    z = Lzss(mode)
+    for c in range(256):
+        for i in range(8):
+            if (c >> i) & 1:
+                z.lit(r.choice(_NZ))
+                continue
+            n = r.choice((3, 3, 4, 7, 17, 18, r.randint(3, 18)))
+            prev = z.items[-1] if i else None
+            if prev and prev[0] and r.random() < 0.5:
+                d = 1
+            elif prev and not prev[0] and r.random() < 0.6:
+                d = r.randint(1, z._last_len)
+            else:
+                d = r.randint(1, min(4096, max(len(z.plain), 1)))
+            z.match(d, n)
+    return z
+
+
+def lzss_cases():
+    C = []
+    modes = (0, 1, 2)
+    # every distance 1..4096 (mpos == ring: 4096; mpos == ring + 1: 4095) behind 4200 literals; the output wraps the ring 4 and 18 times
+    for n in (3, 18):
+        for m in modes:
+            z = Lzss(m)
+            z.lits(_nz(n + m, 4200))
+            for d in range(1, 4097):
+                z.match(d, n)
+            C.append(_lzss_case("lzss_every_distance_at_length_%d_mode%d" % (n, m), z))
+    # the same raw (mpos, len) bytes: another plaintext in mode 0 (start 4096-16) than in mode 2 (start 4096-18)
+    for m in modes:
+        z = Lzss(m)
+        z.lits(b"0123456789abcdefghij")
+        for mp in (4080, 4078, 4079, 4081, 0, 4095, 5):
+            z.raw(mp, 5)
+            z.lit(0x7E)
+        C.append(_lzss_case("lzss_same_raw_items_mode%d" % m, z))
+    # the first item is a match into the pre-fill
+    for d in (1, 16, 18, 4096):
+        for m in (0, 2):
+            z = Lzss(m)
+            z.match(d, 18); z.lits(b"Xy"); z.match(20, 18); z.match(4096, 3); z.lits(b"z")
+            C.append(_lzss_case("lzss_first_item_is_a_match_at_distance_%d_mode%d" % (d, m), z))
+    # a source that starts in the pre-fill and runs into real bytes with d < len: periodic over spaces plus data
+    for m in modes:
+        z = Lzss(m)
+        z.lits(b"AB"); z.match(5, 18); z.lit(0x43); z.match(22, 18); z.match(4096, 18); z.lits(b"DE"); z.match(4095, 17)
+        C.append(_lzss_case("lzss_source_from_the_prefill_into_data_mode%d" % m, z))
+        assert z.props["straddle"], z.props
+    # overlaps
+    for m in modes:
+        z = Lzss(m)
+        z.lits(_nz(5, 19))
+        for d in (1, 2, 3, 7, 17):
+            z.match(d, 18); z.lit(0x30 + d)
+        for n in range(3, 19):
+            z.match(n, n); z.lit(0x40 + n)
+        C.append(_lzss_case("lzss_overlapping_matches_mode%d" % m, z))
+    # all 256 control bytes; then the first 300 bytes of that stream cut at every length
+    for m in modes:
+        C.append(_lzss_case("lzss_every_control_byte_mode%d" % m, _lzss_control_bytes(m)))
+    z = _lzss_control_bytes(0)
+    for cut in range(301):
+        C.append(_lzss_case("lzss_every_control_byte_first_%03d_bytes" % cut, z, cut=cut))
+    # inputs of 0..3 bytes: nothing, the control byte alone, a match's first byte, a match
+    for m in modes:
+        for cut in range(4):
+            z = Lzss(m)
+            z.match(4096, 9); z.lits(b"q")
+            C.append(_lzss_case("lzss_input_of_%d_bytes_mode%d" % (cut, m), z, cut=cut))
+    z = Lzss(0); z.lits(b"pq"); z.match(1, 3)
+    for cut in range(4):
+        C.append(_lzss_case("lzss_input_of_%d_bytes_literals_first" % cut, z, cut=cut))
+    # maximum expansion: control bytes of 0x00, length 18 throughout -- 17 bytes in, 144 out (the pre-fill's spaces: no literal fits in)
+    for m in modes:
+        for groups in (1, 40):
+            z = Lzss(m)
+            for k in range(8 * groups):
+                z.match((1, 4096, 16, 18, 143)[k % 5], 18)
+            c = _lzss_case("lzss_maximum_expansion_%d_bytes_in_mode%d" % (17 * groups, m), z)
+            c.props["ratio"] = (c.out_len, len(c.stream))
+            C.append(c)
+    # mode 3: refused, no byte written
+    z = Lzss(0); z.lits(b"never")
+    C.append(Case("lzss_mode_3_is_refused", "lzss", z.stream(), 0, wb=3, plain=b"", err=ERR_ARGS, props=dict(in_used=0), rooms=[64, 0]))
+    return C
+
+
+class LzhReader:
+    """lzh_decompress restated: bits MSB first, fed a byte at a time; behind the end of the input zero bytes are fed, and the first
+    read that used one of their bits ends the stream, as does the top of the token loop once a zero byte has been fed at all"""
+
+    def __init__(self, data):
+        self.data, self.ip, self.bb, self.bl, self.end = bytes(data), 0, 0, 0, 0
+        self.lens, self.types, self.dec = [], [], []
+
+    def ensure(self, n):
+        while self.bl < n:
+            b = 0
+            if self.ip < len(self.data):
+                b = self.data[self.ip]; self.ip += 1
+            else:
+                self.end += 8
+            self.bb = (self.bb << 8) | b
+            self.bl += 8
+
+    def bits(self, n):
+        """-> value, or None when the read used a fed bit"""
+        self.ensure(n)
+        v = (self.bb >> (self.bl - n)) & ((1 << n) - 1)
+        self.bl -= n
+        self.bb &= (1 << self.bl) - 1
+        return None if self.end and self.bl < self.end else v
+
+    def sym(self, t):
+        """-> symbol; None past the end; -1 no such code"""
+        self.ensure(16)
+        peek = (self.bb >> (self.bl - 16)) & 0xFFFF
+        for L in range(1, 17):
+            s = self.dec[t].get((peek >> (16 - L), L))
+            if s is not None:
+                self.bl -= L
+                self.bb &= (1 << self.bl) - 1
+                self.last_len = L
+                return None if self.end and self.bl < self.end else s
+        return -1
+
+    def read_lens(self, typ, n):
+        """lzh_read_lens -> lengths, or None past the end.  Types 4..15 read nothing and leave the lengths as they are: zero here, as
+        in the kernel and the oracle (the reference's array is uninitialised heap memory there)"""
+        lens = [0] * n
+        if typ == 0:
+            return [{16: 4, 32: 5, 64: 6, 256: 8}[n]] * n
+        if typ == 3:
+            for i in range(n):
+                lens[i] = self.bits(4)
+                if lens[i] is None:
+                    return None
+        elif typ in (1, 2):
+            c = self.bits(4)
+            if c is None:
+                return None
+            lens[0] = c
+            for i in range(1, n):
+                sel = self.bits(1 if typ == 1 else 2)
+                if sel is None:
+                    return None
+                if typ == 1 and sel:
+                    sel = self.bits(1)
+                    if sel is None:
+                        return None
+                    sel = 3 if sel else 2             # '10': ++c, '11': four bits
+                elif typ == 1:
+                    sel = 1
+                if sel == 3:
+                    c = self.bits(4)
+                    if c is None:
+                        return None
+                else:
+                    c = (c + sel - 1) & 0xFF          # (the lengths are bytes)
+                lens[i] = c
+        return lens
+
+    def header(self):
+        """-> ERR_OK / ERR_DATAFORMAT, or None when the input ends inside it"""
+        for _ in range(6):
+            v = self.bits(4)
+            if v is None:
+                return None
+            self.types.append(v)
+        for t in range(5):
+            lens = self.read_lens(self.types[t], LZH_NSYMS[t])
+            if lens is None:
+                return None
+            self.lens.append(lens)
+            if not lzh_accepts(lens):
+                return ERR_DATAFORMAT
+            self.dec.append({c: s for s, c in enumerate(canon(lens, LZH_TABLEBITS)) if c})
+        return ERR_OK
+
+    def decode(self):
+        """-> (err, plaintext, bytes of input taken)"""
+        win, out, lit_run = bytearray(b" " * 4096), bytearray(), 0
+        e = self.header()
+        if e != ERR_OK:
+            return e or ERR_OK, b"", self.ip
+        while not self.end:
+            n = self.sym(1 if lit_run else 0)
+            if n is None or n < 0:
+                return (ERR_OK if n is None else ERR_DATAFORMAT), bytes(out), self.ip
+            if n > 0:
+                n += 2; lit_run = 0
+                j = self.sym(3)
+                if j is None or j < 0:
+                    return (ERR_OK if j is None else ERR_DATAFORMAT), bytes(out), self.ip
+                low = self.bits(6)
+                if low is None:
+                    break
+                off = (j << 6) | low
+                for _ in range(n):
+                    b = win[(len(out) - off) & 4095]
+                    win[len(out) & 4095] = b; out.append(b)
+            else:
+                n = self.sym(2)
+                if n is None or n < 0:
+                    return (ERR_OK if n is None else ERR_DATAFORMAT), bytes(out), self.ip
+                n += 1
+                lit_run = 0 if n == 32 else 1
+                for _ in range(n):
+                    j = self.sym(4)
+                    if j is None or j < 0:
+                        return (ERR_OK if j is None else ERR_DATAFORMAT), bytes(out), self.ip
+                    win[len(out) & 4095] = j; out.append(j)
+        return ERR_OK, bytes(out), self.ip
+
+
+def lzh_accepts(lens):
+    """make_decode_table with 9 table bits: the short codes may not overflow; if they fill the table it is accepted as it is (longer
+    lengths then get no code); otherwise the lengths 1..16 must be exactly complete.  Lengths above 16 count nowhere."""
+    short = sum(1 << (16 - l) for l in lens if 1 <= l <= LZH_TABLEBITS)
+    if short >= 65536:
+        return short == 65536
+    return sum(1 << (16 - l) for l in lens if 1 <= l <= 16) == 65536
+
+
+class Lzh:
+    """trees: five (type, spec).  spec: a list of code lengths, written in the tree's encoding (type 0 writes nothing and means the
+    flat lengths whatever the list says; type 1 writes x == c + 1 as '++c', so ...15, 16, 17 comes out as the overflow it is; type 2
+    steps modulo 256, so 0, 255, 0 is a step down and up again); or a str of '0' / '1', the length field's bits as they are.  The
+    lengths the tokens are coded with are READ BACK from the bits written (props["lens"]).  Tokens: run(literal symbols) and
+    match(length symbol, offset symbol, low six bits)."""
+
+    def __init__(self, trees, sixth=0):
+        self.bitsv = []
+        for t, _ in trees:
+            self.put(t, 4)
+        self.put(sixth, 4)
+        for (t, spec), n in zip(trees, LZH_NSYMS):
+            if isinstance(spec, str):
+                self.bitsv += [int(ch) for ch in spec]
+            else:
+                assert len(spec) == n
+                self._put_lens(t, spec)
+        self.header_bits = len(self.bitsv)
+        rd = LzhReader(self.bytes_() + bytes(4))
+        self.header_err = rd.header()
+        self.lens, self.types = rd.lens, rd.types
+        self.codes = [canon(l, LZH_TABLEBITS) if lzh_accepts(l) else None for l in self.lens]
+        self.plain, self.win, self.lit_run, self.prev = bytearray(), bytearray(b" " * 4096), 0, "start"
+        self.props = dict(lens=self.lens, types=self.types, used=[set() for _ in range(5)], tables=set(), offsets=set(),
+                          before_start=[], in_match=[], match_syms=[set(), set()], run_lens=set(), match_bits=0, match_bytes=0)
+
+    def put(self, v, n):
+        self.bitsv += [(v >> k) & 1 for k in range(n - 1, -1, -1)]
+
+    def _put_lens(self, t, lens):
+        if t == 3:
+            for x in lens:
+                assert x <= 15
+                self.put(x, 4)
+        elif t in (1, 2):
+            c = lens[0]; self.put(c, 4)
+            for x in lens[1:]:
+                step = (x - c) & 0xFF
+                if t == 1 and step == 0:
+                    self.put(0, 1)
+                elif t == 1 and step == 1:
+                    self.put(2, 2)
+                elif t == 2 and step in (0xFF, 0, 1):
+                    self.put((step + 1) & 3, 2)
+                else:
+                    assert x <= 15
+                    self.put(3, 2); self.put(x, 4)
+                c = x
+
+    def bytes_(self):
+        b = self.bitsv + [0] * (-len(self.bitsv) % 8)
+        return bytes(int("".join(map(str, b[i:i + 8])), 2) for i in range(0, len(b), 8))
+
+    def coded(self, t):
+        return [s for s, c in enumerate(self.codes[t]) if c]
+
+    def _code(self, t, s):
+        c = self.codes[t][s]
+        assert c is not None, ("tree %d: symbol %d has no code" % (t, s))
+        self.put(c[0], c[1])
+        self.props["used"][t].add(c[1])
+        return c[1]
+
+    def _emit(self, b):
+        self.win[len(self.plain) & 4095] = b
+        self.plain.append(b)
+
+    def run(self, syms):
+        assert 1 <= len(syms) <= 32
+        tab = 1 if self.lit_run else 0
+        self._code(tab, 0); self._code(2, len(syms) - 1)
+        for s in syms:
+            self._code(4, s); self._emit(s)
+        self.props["tables"].add((tab, self.prev, "run"))
+        self.props["run_lens"].add(len(syms))
+        self.prev = "run32" if len(syms) == 32 else "run"
+        self.lit_run = 0 if len(syms) == 32 else 1
+
+    def match(self, lsym, osym, low):
+        assert 1 <= lsym <= 15 and 0 <= osym < 64 and 0 <= low < 64
+        tab = 1 if self.lit_run else 0
+        nb = self._code(tab, lsym) + self._code(3, osym) + 6
+        self.put(low, 6)
+        off, P, n = (osym << 6) | low, len(self.plain), lsym + 2
+        p = self.props
+        p["tables"].add((tab, self.prev, "match")); p["offsets"].add(off); p["match_syms"][tab].add(lsym)
+        p["match_bits"] += nb; p["match_bytes"] += n
+        if (off or 4096) > P:
+            p["before_start"].append(P)
+        p["in_match"].append(P + n // 2)
+        for _ in range(n):
+            self._emit(self.win[(len(self.plain) - off) & 4095])
+        self.prev, self.lit_run = "match", 0
+
+    def stream(self):
+        self.props["spare_bits"] = -len(self.bitsv) % 8
+        return self.bytes_()
+
+
+def _lzh_case(name, z, err=ERR_OK, cut=None, ref_undefined=False):
+    s = z.stream()
+    if cut is not None:
+        s = s[:cut]
+    e, plain, used = LzhReader(s).decode()
+    assert e == err, (name, e, err)
+    props = dict(z.props, in_used=used)
+    if cut is None and err == ERR_OK:
+        # what the tokens expand to against what a decoder makes of the stream: the reference stops at the top of its token loop once a
+        # zero byte has been fed, so tokens in the last two bytes may be left out, and zero bits of the padding may be one more
+        k = min(len(plain), len(z.plain))
+        assert plain[:k] == bytes(z.plain[:k]), name
+        props["pad_token"] = len(plain) > len(z.plain)
+        props["left_out"] = len(z.plain) - len(plain) if len(plain) < len(z.plain) else 0
+    if ref_undefined:
+        props["ref_undefined"] = True
+    inside = [x for x in z.props["in_match"] if x < len(plain)]
+    return Case(name, "lzh", s, len(plain), plain=plain, err=err, props=props,
+                rooms=_rooms(len(plain), inside[len(inside) // 2:]) if err == ERR_OK else [64, 0])
+
+
+def _skew(n, seed, maxlen=15):
+    """a complete code over all n symbols with lengths of many sizes"""
+    r = random.Random(seed)
+    leaves = [1, 1]
+    while len(leaves) < n:
+        i = r.choice([k for k, l in enumerate(leaves) if l < maxlen])
+        leaves[i] += 1
+        leaves.append(leaves[i])
+    r.shuffle(leaves)
+    assert kraft(leaves) == 65536
+    return leaves
+
+
+def _pad(lens, n, at=0):
+    """lens for the symbols at.., zero elsewhere"""
+    return [0] * at + list(lens) + [0] * (n - at - len(lens))
+
+
+LZH_FLAT = [(0, [0] * n) for n in LZH_NSYMS]
+
+
+def _lzh_trees(seed, typ=3):
+    return [(typ, _skew(n, seed * 10 + t)) for t, n in enumerate(LZH_NSYMS)]
+
+
+def _lzh_mix(z, seed, tokens=60):
+    """runs and matches over whatever symbols the trees give a code; literals other than 0x00 and 0x20 where there are any"""
+    r = random.Random(seed)
+    lit = [s for s in z.coded(4) if s not in (0, 0x20)] or z.coded(4)
+    for _ in range(tokens):
+        ml = z.coded(1 if z.lit_run else 0)
+        m = [s for s in ml if s]
+        if m and (0 not in ml or r.random() < 0.5):
+            z.match(r.choice(m), r.choice(z.coded(3)), r.randrange(64))
+        else:
+            z.run([r.choice(lit) for _ in range(r.choice(z.coded(2)) + 1)])
+
+
+CHAIN16 = list(range(1, 15)) + [15, 15]                  # sixteen symbols: one code of each length 1..14, two of 15
+CHAIN17 = list(range(1, 16)) + [16, 16]                  # seventeen: one of each length 1..15, two of 16
+FILL9 = list(range(1, 10)) + [9] + list(range(10, 16))   # short codes that fill a 9-bit table beside 10..15, which get no code
+
+LZH_BAD = {"oversubscribed_short_codes": [1, 1, 1],
+           "oversubscribed_long_codes_only": list(range(1, 10)) + [10, 10, 10],
+           "incomplete": [1, 2, 3, 12],
+           "all_lengths_zero": []}
+
+
+def _lzh_end_cases():
+    """the end of the last real token at each of the eight alignments.  Trees A: the all-zero code of MATCHLEN1, LITLEN and LITERAL
+    is one bit, so three spare zero bits or more are one more token (a run of one literal), which the reference emits -- the last
+    real token is a match whose offset code is 10 bits, so that no read before its end has to feed a zero byte (kwajd.c:465).  Two
+    spare bits or fewer are no token under any tree: the shortest one is three bits.  Trees B (flat): nine zero bits before a literal."""
+    C = []
+    off_a = _pad(list(range(1, 10)) + [10, 10], 64)
+    A = [(3, _pad([1, 1], 16)), (3, _pad([1, 1], 16)), (3, _pad([1, 1], 32)), (3, off_a), (3, _pad([1, 1], 256, 0x41))]
+    for name, trees, want in (("a_token_in_the_padding", A, True), ("no_token_in_the_padding", LZH_FLAT, False)):
+        for spare in range(8):
+            if want and spare < 3:
+                continue
+            for k in range(40):
+                z = Lzh(trees)
+                z.run([0x41, 0x42][:1 + k % 2])
+                for i in range(k // 2):
+                    z.run([0x42])
+                if trees is A:
+                    z.match(1, 9, 3)
+                else:
+                    for i in range(k % 4):
+                        z.match(1 + i, 0, 1 + i)
+                    z.match(2, 0, 2)
+                if -len(z.bitsv) % 8 != spare:
+                    continue
+                c = _lzh_case("lzh_end_with_%d_spare_bits_%s" % (spare, name), z)
+                if c.props["pad_token"] == want and not c.props["left_out"]:
+                    C.append(c)
+                    break
+            else:
+                raise AssertionError(("no such stream", name, spare))
+    return C
+
+
+def lzh_cases():
+    C = []
+    # each of the four encodings on each of the five trees (type 0: the flat lengths)
+    for k in range(5):
+        for typ in range(4):
+            trees = _lzh_trees(3 + k)
+            trees[k] = (typ, _skew(LZH_NSYMS[k], 40 + 4 * k + typ))
+            z = Lzh(trees)
+            _lzh_mix(z, 100 + 4 * k + typ)
+            C.append(_lzh_case("lzh_type_%d_on_tree_%d" % (typ, k), z))
+    z = Lzh(LZH_FLAT); _lzh_mix(z, 7, 80)
+    C.append(_lzh_case("lzh_type_0_on_every_tree", z))
+    # literal codes of every length 1..15, and 16 (type 1's ++c from 15: the only way to a 16-bit code); then 17 and 18, which get none
+    for name, tail in (("lzh_literal_codes_of_every_length_1_to_16", []), ("lzh_type_1_runs_on_to_17_and_18", [17, 18, 18])):
+        trees = _lzh_trees(5)
+        trees[4] = (1, _pad(CHAIN17 + tail, 256, 0x41))
+        z = Lzh(trees)
+        assert z.lens[4][0x41:0x41 + 17 + len(tail)] == CHAIN17 + tail
+        for s in range(0x41, 0x41 + 17):
+            z.run([s] * 2)
+            z.match(1 + s % 15, s % 64, s % 64)
+        C.append(_lzh_case(name, z))
+    # the same on the small trees: 16-bit codes for match lengths and offsets
+    trees = _lzh_trees(6)
+    trees[0] = trees[1] = (1, [1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 15])
+    trees[3] = (1, _pad(CHAIN17, 64, 20))
+    z = Lzh(trees)
+    for s in range(20, 37):
+        z.match(1 + s % 15, s, 63 - s)
+        z.run([0x61 + s % 20] * (1 + s % 5))
+    C.append(_lzh_case("lzh_offset_codes_of_16_bits", z))
+    # type 2 stepping below 0 to 255 (no code) and back up
+    for k in (0, 2, 4):
+        n = LZH_NSYMS[k]
+        trees = _lzh_trees(8 + k)
+        trees[k] = (2, [1, 0, 255, 0, 2, 3, 4, 4, 0, 255, 255, 0] + [0] * (n - 12))
+        z = Lzh(trees)
+        assert z.lens[k][2] == 255 and z.lens[k][9:11] == [255, 255] and len(z.coded(k)) == 5
+        _lzh_mix(z, 30 + k)
+        C.append(_lzh_case("lzh_type_2_steps_to_255_and_back_tree_%d" % k, z))
+    # type 3 with 15s: the match-length trees with one code of each length 1..14 and two of 15
+    trees = _lzh_trees(9)
+    trees[0] = (3, CHAIN16); trees[1] = (3, CHAIN16[::-1])
+    z = Lzh(trees)
+    for s in range(1, 16):
+        z.match(s, s, s); z.run([0x30 + s]); z.match(s, 63 - s, 63 - s)
+    C.append(_lzh_case("lzh_type_3_with_15s", z))
+    # short codes that exactly fill the 9-bit table beside lengths 10..15 that get no code: accepted
+    for k in range(5):
+        trees = _lzh_trees(11 + k)
+        trees[k] = (3, _pad(FILL9, LZH_NSYMS[k]))
+        z = Lzh(trees)
+        assert len(z.coded(k)) == 10
+        _lzh_mix(z, 50 + k)
+        C.append(_lzh_case("lzh_short_codes_fill_the_table_tree_%d" % k, z))
+    # rejected trees, in each of the five positions, the trees before them valid
+    for kind, lens in LZH_BAD.items():
+        for k in range(5):
+            trees = _lzh_trees(17 + k, typ=1 + k % 3)
+            trees[k] = (3, _pad(lens, LZH_NSYMS[k], 1))
+            z = Lzh(trees)
+            z.bitsv += [1, 0, 1, 1, 0, 0, 1, 0] * 12
+            C.append(_lzh_case("lzh_tree_%d_%s" % (k, kind), z, err=ERR_DATAFORMAT))
+    # types 4..15, and headers cut inside the tree description: the reference's length arrays are uninitialised heap memory there
+    # (kwajd.c:412-420, 497-546), its answer undefined; kernel and oracle take the lengths as zero -- kernel against oracle only
+    for typ in range(4, 16):
+        trees = _lzh_trees(23)
+        trees[typ % 5] = (typ, "")
+        z = Lzh(trees)
+        z.bitsv += [1, 1, 0, 1] * 20
+        C.append(_lzh_case("lzh_unknown_length_encoding_%d" % typ, z, err=ERR_DATAFORMAT, ref_undefined=True))
+    z = Lzh(_lzh_trees(24, typ=3)); _lzh_mix(z, 24, 10)
+    hdr = z.header_bits // 8
+    for cut in sorted(set(range(0, 5)) | set(range(5, hdr, 7)) | {10, 11, 12, 18, 19, 20, 34, 35, 36, 66, 67, 68, hdr - 1}):
+        # (inside the six type fields the reference has read no length yet and stops with OK: defined, and compared)
+        C.append(_lzh_case("lzh_header_cut_after_%03d_bytes" % cut, z, cut=cut, ref_undefined=cut >= 3))
+    # matches: every length symbol of both tables (which differ); the offsets at the edges; every offset symbol; the pre-fill; overlaps
+    trees = _lzh_trees(25)
+    z = Lzh(trees)
+    assert z.lens[0] != z.lens[1]
+    z.run(list(_nz(1, 32)))
+    for s in range(1, 16):
+        z.match(s, 0, 1 + s)                      # MATCHLEN1 (behind a run of 32, behind a match)
+        z.match(16 - s, 0, 40)
+        z.run(list(_nz(s, 3)))
+        z.match(s, 0, 2 + s)                      # MATCHLEN2 (behind a short run)
+    C.append(_lzh_case("lzh_every_match_length_in_both_tables", z))
+    z = Lzh(_lzh_trees(26))
+    z.run(list(_nz(2, 32)))
+    for r_ in range(140):
+        z.run(list(_nz(100 + r_, 32)))
+    for off in (0, 1, 63, 64, 65, 4095, 4094, 2, 3):
+        z.match(15, off >> 6, off & 63); z.match(1, off >> 6, off & 63); z.run([0x51])
+    C.append(_lzh_case("lzh_offsets_0_1_63_64_65_4095", z))
+    z = Lzh(_lzh_trees(27))
+    for r_ in range(130):
+        z.run(list(_nz(300 + r_, 32)))
+    for s in range(64):
+        z.match(1 + s % 15, s, 0); z.match(15 - s % 15, s, 63)
+    C.append(_lzh_case("lzh_every_offset_symbol_low_bits_0_and_63", z))
+    for off in (0, 1, 63, 64, 4095):
+        z = Lzh(_lzh_trees(28))
+        z.match(15, off >> 6, off & 63); z.run([0x58, 0x79]); z.match(9, 0, 19); z.match(3, 0, 0); z.run([0x7A])
+        C.append(_lzh_case("lzh_first_token_is_a_match_at_offset_%d" % off, z))
+    z = Lzh(_lzh_trees(29))
+    z.run([0x41, 0x42]); z.match(15, 0, 5); z.run([0x43]); z.match(15, 63, 63)     # from the pre-fill into data, d < len
+    for d in (1, 2, 3):
+        z.run(list(_nz(d, 3))); z.match(15, 0, d); z.match(1, 0, d)
+    C.append(_lzh_case("lzh_overlaps_at_distance_1_2_3_and_from_the_prefill_into_data", z))
+    # literal runs of every length; behind a run of 32 MATCHLEN1 applies, behind one of 31 MATCHLEN2: the two trees are each other's
+    # mirror image here, so the wrong one reads another token
+    trees = _lzh_trees(31)
+    trees[1] = (3, trees[0][1][::-1])
+    z = Lzh(trees)
+    assert z.lens[0] != z.lens[1]
+    for n in list(range(1, 33)) + [31, 32, 32, 31]:
+        z.run(list(_nz(n, n)))
+        z.match(1 + n % 15, 0, n)
+        z.run(list(_nz(n + 50, n)))
+    z.run(list(_nz(9, 32))); z.match(4, 0, 9); z.match(5, 0, 3); z.run(list(_nz(10, 31))); z.match(4, 0, 9)
+    C.append(_lzh_case("lzh_literal_runs_of_every_length_1_to_32", z))
+    # two-symbol trees of one-bit codes: a match of 17 bytes in 8 bits
+    one = lambda n, a, b: (3, [1 if s in (a, b) else 0 for s in range(n)])
+    z = Lzh([one(16, 0, 15), one(16, 0, 15), one(32, 0, 1), one(64, 0, 1), one(256, 0x41, 0x42)])
+    z.run([0x41, 0x42])
+    for k in range(400):
+        z.match(15, k & 1, 1 + (k * 7) % 63)
+    z.run([0x42, 0x41]); z.run([0x41]); z.run([0x42]); z.run([0x42])
+    C.append(_lzh_case("lzh_one_bit_trees_17_bytes_a_byte", z))
+    C += _lzh_end_cases()
+    # one mid-size stream cut at every byte behind its tree header
+    z = Lzh(_lzh_trees(33, typ=2)); _lzh_mix(z, 33, 9)
+    s = z.stream()
+    hdr = (z.header_bits + 7) // 8
+    assert 100 <= len(s) - hdr <= 250, len(s) - hdr
+    z.props["header_bytes"], z.props["whole"] = hdr, len(s)
+    for cut in range(hdr, len(s) + 1):                 # (the last one is the whole stream)
+        C.append(_lzh_case("lzh_stream_cut_after_%03d_bytes" % cut, z, cut=cut))
+    return C
+
+
+def szdd_container(stream, length, qbasic=False):
+    """an SZDD file around an LZSS stream (szddd.c:140-170): the normal header (mode 0) or QBasic's (mode 2)"""
+    n = length.to_bytes(4, "little")
+    return (b"SZ \x88\xF0\x27\x33\xD1" + n if qbasic else b"SZDD\x88\xF0\x27\x33A_" + n) + stream
+
+
+def kwaj_container(stream, method, length):
+    """a KWAJ file with the length field alone (kwajd.c:155-250): method 2 = LZSS mode 2, method 3 = LZH"""
+    return b"KWAJ\x88\xF0\x27\xD1" + method.to_bytes(2, "little") + (18).to_bytes(2, "little") + (1).to_bytes(2, "little") + \
+        length.to_bytes(4, "little") + stream
+
+
+_CACHE = {}
+
+
+def lz_cases():
+    """lzss_cases() + lzh_cases(), built once (nobody changes a case)"""
+    if "lz" not in _CACHE:
+        _CACHE["lz"] = lzss_cases() + lzh_cases()
+    return list(_CACHE["lz"])
+
+
 def all_cases():
-    return lzx_cases() + lzxd_cases() + mszip_cases() + qtm_cases()
+    return lzx_cases() + lzxd_cases() + mszip_cases() + qtm_cases() + lz_cases()

@@ -472,6 +472,11 @@ hipError_t emu_hipMalloc(void **p, size_t n) {
   *p = q;
   return hipSuccess;
 }
+// C-linkage doors for tests that hold "device" memory of their own (tests/test_gpu_hostpath.py DevBuf): the emulator's loaded, there is
+// no HIP runtime to ask
+extern "C" void *emu_dev_alloc(size_t n, int fill) { void *p = nullptr; if (emu_hipMalloc(&p, n) != hipSuccess) return nullptr; memset(p, fill, n); return p; }
+extern "C" void emu_dev_read(void *dst, const void *src, size_t n) { memmove(dst, src, n); }
+extern "C" int emu_dev_free(void *p);
 hipError_t hipFree(void *p) {
   if (!p) return hipSuccess;
   std::lock_guard<std::mutex> g(g_alloc_mu);
@@ -479,6 +484,7 @@ hipError_t hipFree(void *p) {
   for (int i = 0; i < cnt; i++) if (g_lo[i].load() == (uintptr_t) p) { g_hi[i].store(0); g_lo[i].store(0); free(p); return hipSuccess; }
   return hipErrorInvalidValue;
 }
+extern "C" int emu_dev_free(void *p) { return hipFree(p) == hipSuccess ? 0 : -1; }
 hipError_t emu_hipHostMalloc(void **p, size_t n) { *p = malloc(n ? n : 1); return *p ? hipSuccess : hipErrorOutOfMemory; }
 hipError_t hipHostFree(void *p) { free(p); return hipSuccess; }
 void emu_test_delay(void) {

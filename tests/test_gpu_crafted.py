@@ -5,13 +5,22 @@ frame-parallel path.  Then every valid LZX case 600 times in one batch with its 
 longer all find a wave at once (the speculative header path and the other ticket orders run): ~16 000 units, ~900 MB of
 output, 2.5 s on an MI355X.  The Quantum cases go in three times each -- in_len exact, in_len extended over 160 zero bytes
 (the lean reader), exact with a failing feeder -- and in_used and good_len are held against the oracle too; then every valid
-one 200 times in one batch, every third unit with marks (wall time of the Quantum tests on an MI355X: not measured yet)."""
+one 200 times in one batch, every third unit with marks (wall time of the Quantum tests on an MI355X: not measured yet).
+The LZSS and KWAJ LZH cases go in at every room of theirs (ample, exact, one byte less, inside a match, none) and, the valid
+ones, at every residue of in_off and out_off mod 16, in the test's own layout with guard bytes between the units; the same batch
+then goes into a device buffer full of 0xA5, in which nothing but the pre-fill's spaces and the decoded bytes may have changed:
+check_lzss (7605 units, both passes) takes 0.07 s and check_lzh (5091 units) 0.06 s on an MI355X once the library is warm,
+test_crafted_streams_vs_oracle with all codecs 10.1 s; every valid case 300 times in one batch, both kinds interleaved, every
+third unit with a CRC-32: 3.0 s."""
+import zlib
+
 import numpy as np
 import pytest
 
 import crafted_streams as CS
 import libmspack_amd as M
-from helpers import oracle_lzx, oracle_lzxd, oracle_mszip, oracle_qtm, oracle_qtm_marks, oracle_set_hard_eof
+from helpers import oracle_kwaj_lzh, oracle_lzss, oracle_lzx, oracle_lzxd, oracle_mszip, oracle_qtm, oracle_qtm_marks, oracle_set_hard_eof
+from test_gpu_hostpath import DevBuf
 import test_gpu_lzx_frames as T
 import test_gpu_lzxd as D
 import test_gpu_mszip_blocks as B
@@ -128,11 +137,102 @@ def check_qtm(cases):
                 assert res["good_len"][i] == r.out_len, what
 
 
+LZ_BELOW, LZ_GUARD = 4096, 64       # the window pre-fill below a unit's room; guard bytes between its room and the next unit
+
+
+def lz_variants(c):
+    """(room, in_off mod 16, out_off mod 16): every room of the case; a valid one at every residue of both offsets besides"""
+    v = [(room, 0, 0) for room in c.rooms]
+    if c.err == 0:
+        v += [(c.rooms[0], k, (7 * k + 5) % 16) for k in range(16)]
+    return v
+
+
+def lz_oracle(c, room):
+    return oracle_lzss(c.stream, c.wb, room) if c.codec == "lzss" else oracle_kwaj_lzh(c.stream, room)
+
+
+def lz_batch(items, in_offs=None, arena=None):
+    """the test's own layout for LZSS / LZH units.  items: (case, room, in_off mod 16, out_off mod 16).  Every unit gets its own
+    copy of the stream at the residue asked for (unless in_offs / arena say where the streams are), LZ_BELOW bytes below its room
+    and LZ_GUARD bytes behind it that belong to nobody -> (units, arena, bytes of output)"""
+    if in_offs is None:
+        in_offs, pos = [], 0
+        for c, _room, ri, _ro in items:
+            pos = ((pos + 15) & ~15) + ri
+            in_offs.append(pos); pos += len(c.stream)
+        arena = np.zeros(pos + 64, dtype=np.uint8)
+        for (c, _room, _ri, _ro), o in zip(items, in_offs):
+            arena[o:o + len(c.stream)] = np.frombuffer(c.stream, dtype=np.uint8)
+    kinds = np.array([M.KIND_LZSS if it[0].codec == "lzss" else M.KIND_KWAJ_LZH for it in items], dtype=np.uint8)
+    units, _ = M.make_units(kinds, in_offs, [len(it[0].stream) for it in items], [it[1] for it in items],
+                            window_bits=[it[0].wb for it in items])
+    pos = LZ_GUARD
+    for i, (_c, room, _ri, ro) in enumerate(items):
+        base = pos + LZ_BELOW
+        units["out_off"][i] = base + ((ro - base) % 16)
+        pos = int(units["out_off"][i]) + room + LZ_GUARD
+    return units, arena, pos
+
+
+def to_device(units, arena, out_bytes):
+    """the batch through mspack_hip_decode_batch_to_device into a device buffer full of 0xA5 -> (the buffer, results)"""
+    d = DevBuf(out_bytes, fill=0xA5)
+    res = np.zeros(len(units), dtype=M.RESULT_DTYPE)
+    u = np.ascontiguousarray(units)
+    rc = M.lib().mspack_hip_decode_batch_to_device(u.ctypes.data, len(u), arena.ctypes.data, arena.size, d.ptr, out_bytes, res.ctypes.data)
+    assert rc == 0, M.lib().mspack_hip_last_error()
+    out = d.to_host()
+    d.free()
+    return out, res
+
+
+def check_lz(cases):
+    """every case at every room and every residue, against the oracle: err, out_len (which may exceed the room), in_used, good_len,
+    flags, every byte up to min(out_len, room) -- and against the helper's plaintext.  Then the same batch into a device buffer
+    full of 0xA5: nothing but the pre-fill's spaces and those bytes may have changed in it."""
+    if not cases:
+        return
+    items = [(c,) + v for c in cases for v in lz_variants(c)]
+    units, arena, out_bytes = lz_batch(items)
+    out, res = M.decode_batch(units, arena, out_bytes)
+    want = np.full(out_bytes, 0xA5, dtype=np.uint8)
+    for i, (c, room, ri, ro) in enumerate(items):
+        e, o, r = lz_oracle(c, room)
+        what = (c.name, "room %d of %d" % (room, c.out_len), (ri, ro), res[i], e, r.out_len, r.in_used)
+        assert res["err"][i] == e == c.err and res["out_len"][i] == r.out_len == c.out_len, what
+        assert res["in_used"][i] == r.in_used and res["good_len"][i] == r.out_len and res["flags"][i] == r.flags == 0, what
+        n, oo = min(r.out_len, room), int(units["out_off"][i])
+        assert units["in_off"][i] % 16 == ri and oo % 16 == ro
+        assert out[oo:oo + n].tobytes() == o[:n] == c.plain[:n], what
+        if not (c.codec == "lzss" and c.wb > 2):          # (a refused mode writes nothing at all)
+            want[oo - LZ_BELOW:oo] = 0x20
+        want[oo:oo + n] = np.frombuffer(o[:n], dtype=np.uint8)
+    dev, res2 = to_device(units, arena, out_bytes)
+    assert np.array_equal(res2, res)
+    bad = np.flatnonzero(dev != want)
+    if bad.size:
+        i = int(np.searchsorted(units["out_off"].astype(np.int64) - LZ_BELOW, bad[0], side="right")) - 1
+        c, room, ri, ro = items[max(i, 0)]
+        raise AssertionError("byte %d of the device buffer is 0x%02X, not 0x%02X: %s, room %d, out_off %d (%d bytes differ)" % (
+            bad[0], dev[bad[0]], want[bad[0]], c.name, room, units["out_off"][max(i, 0)], bad.size))
+
+
+def check_lzss(cases):
+    check_lz(cases)
+
+
+def check_lzh(cases):
+    check_lz(cases)
+
+
 def check_all(cases):
     check_lzx([c for c in cases if c.codec == "lzx"])
     check_lzxd([c for c in cases if c.codec == "lzxd"])
     check_mszip([c for c in cases if c.codec == "mszip"])
     check_qtm([c for c in cases if c.codec == "qtm"])
+    check_lzss([c for c in cases if c.codec == "lzss"])
+    check_lzh([c for c in cases if c.codec == "lzh"])
 
 
 def test_crafted_streams_vs_oracle(built):
@@ -204,3 +304,38 @@ def test_valid_qtm_cases_200_times_in_one_batch(built):
             if marked[i]:
                 lo = o + ((c.out_len + 15) & ~15)
                 assert out[lo:lo + 4 * len(marks[j])].view(np.uint32).tolist() == want_log, (c.name, i)
+
+
+def test_valid_lzss_lzh_cases_300_times_in_one_batch(built):
+    """(both kinds interleaved in one unit table; the 300 units of a case share one copy of its stream; every third unit has ample room
+    and MSPACK_HIP_UF_CRC32 -- its in_used is the digest of tests/test_gpu_crc32.py --, the others the case's rooms in turn)"""
+    cases = [c for c in CS.lz_cases() if c.err == 0]
+    cases.sort(key=lambda c: int(zlib.crc32(c.name.encode())))          # (LZSS and LZH units mixed through the table)
+    n = 300
+    offs, pos = [], 0
+    for c in cases:
+        pos = (pos + 15) & ~15
+        offs.append(pos); pos += len(c.stream)
+    arena = np.zeros(pos + 64, dtype=np.uint8)
+    for c, o in zip(cases, offs):
+        arena[o:o + len(c.stream)] = np.frombuffer(c.stream, dtype=np.uint8)
+    items, in_offs = [], []
+    for k in range(n):                                                    # (case-minor: neighbours in the table are of other cases)
+        for j, c in enumerate(cases):
+            room = c.rooms[0] if (k * len(cases) + j) % 3 == 0 else c.rooms[k % len(c.rooms)]
+            items.append((c, room, 0, 0)); in_offs.append(offs[j])
+    units, arena, out_bytes = lz_batch(items, in_offs, arena)
+    crc = np.arange(len(units)) % 3 == 0
+    units["flags"][crc] |= M.UF_CRC32
+    assert {M.KIND_LZSS, M.KIND_KWAJ_LZH} == set(units["kind"][:16].tolist())
+    out, res = M.decode_batch(units, arena, out_bytes)
+    digest = [(zlib.crc32(c.plain) ^ 0xFFFFFFFF) & 0xFFFFFFFF for c in cases]
+    plain = [np.frombuffer(c.plain, dtype=np.uint8) for c in cases]
+    oo = units["out_off"].astype(np.int64)
+    for i, (c, room, _ri, _ro) in enumerate(items):
+        j = i % len(cases)
+        what = (c.name, i, room, res[i])
+        assert res["err"][i] == 0 and res["out_len"][i] == res["good_len"][i] == c.out_len and res["flags"][i] == 0, what
+        assert res["in_used"][i] == (digest[j] if crc[i] else c.props["in_used"]), what
+        m = min(room, c.out_len)
+        assert np.array_equal(out[oo[i]:oo[i] + m], plain[j][:m]), what

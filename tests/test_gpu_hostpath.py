@@ -21,30 +21,47 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 class DevBuf:
-    """a device buffer through the HIP runtime the library itself is linked with (torch brings its own copy of the
-    runtime, which cannot initialise in a process where /opt/rocm's already has)"""
+    """a device buffer filled with one byte value, through the HIP runtime the library itself is linked with (torch brings its own copy
+    of the runtime, which cannot initialise in a process where /opt/rocm's already has); where the library loaded is the wavefront
+    emulator's build, through the doors that one exports (tests/emu/emu_runtime.cpp emu_dev_*)"""
 
-    def __init__(self, nbytes):
+    def __init__(self, nbytes, fill=0):
         import ctypes as C
-        M.lib()
+        L = M.lib()
+        self.n = nbytes
+        self.emu = L if hasattr(L, "emu_dev_alloc") else None
+        if self.emu is not None:
+            L.emu_dev_alloc.restype = C.c_void_p
+            L.emu_dev_alloc.argtypes = [C.c_size_t, C.c_int]
+            L.emu_dev_read.restype = None
+            L.emu_dev_read.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+            L.emu_dev_free.argtypes = [C.c_void_p]
+            self.ptr = L.emu_dev_alloc(nbytes, fill)
+            assert self.ptr
+            return
         self.hip = C.CDLL("libamdhip64.so")
         self.hip.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
         self.hip.hipMemset.argtypes = [C.c_void_p, C.c_int, C.c_size_t]
         self.hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
         self.hip.hipFree.argtypes = [C.c_void_p]
-        self.n = nbytes
         p = C.c_void_p()
         assert self.hip.hipMalloc(C.byref(p), nbytes) == 0
         self.ptr = p.value
-        assert self.hip.hipMemset(self.ptr, 0, nbytes) == 0
+        assert self.hip.hipMemset(self.ptr, fill, nbytes) == 0
 
     def to_host(self):
         out = np.empty(self.n, dtype=np.uint8)
-        assert self.hip.hipMemcpy(out.ctypes.data, self.ptr, self.n, 2) == 0          # hipMemcpyDeviceToHost
+        if self.emu is not None:
+            self.emu.emu_dev_read(out.ctypes.data, self.ptr, self.n)
+        else:
+            assert self.hip.hipMemcpy(out.ctypes.data, self.ptr, self.n, 2) == 0      # hipMemcpyDeviceToHost
         return out
 
     def free(self):
-        self.hip.hipFree(self.ptr)
+        if self.emu is not None:
+            self.emu.emu_dev_free(self.ptr)
+        else:
+            self.hip.hipFree(self.ptr)
 
 
 def mixed_batch(n_each=40, seed=11):

@@ -79,6 +79,7 @@ def test_lzss_kernel_vs_oracle(built):
     for i, s in enumerate(streams):
         e, o, r = oracle_lzss(s, modes[i], caps[i])
         assert res["err"][i] == e == 0 and res["out_len"][i] == r.out_len, (i, res[i], r.out_len)
+        assert res["in_used"][i] == r.in_used and res["good_len"][i] == r.out_len, (i, res[i], r.in_used)
         assert out[units["out_off"][i]:units["out_off"][i] + r.out_len].tobytes() == o, i
 
 
@@ -98,6 +99,7 @@ def test_kwaj_lzh_kernel_vs_oracle(built):
     for i, s in enumerate(streams):
         e, o, r = oracle_kwaj_lzh(s, caps[i])
         assert res["err"][i] == e and res["out_len"][i] == r.out_len, (i, res[i], e, r.out_len)
+        assert res["in_used"][i] == r.in_used and res["good_len"][i] == r.out_len, (i, res[i], r.in_used)
         assert out[units["out_off"][i]:units["out_off"][i] + r.out_len].tobytes() == o, i
 
 
@@ -137,3 +139,59 @@ def test_files_vs_reference_host_logic_cpu(built, hostlogic, name):
     """the same goldens through the same driver code (csrc/host/szdd_kwaj.c) on the CPU stand-in for the batch ABI (LZSS / LZH
     units decoded by the oracle): header parsing, the one-unit batch, room handling -- host logic only"""
     check_file(name, L=hostlogic)
+
+
+# ---- files around the hand-built streams of tests/crafted_streams.py (tests/golden/szdd_kwaj_crafted.json) ----------------------
+def crafted_file_cases():
+    """-> [(name, kind (0 SZDD / 1 KWAJ), file bytes)]: both maximum expansions (run_unit's room formulas), sources in the pre-fill,
+    KWAJ methods 2 and 3 (a 16-bit code; a token out of the padding), stated lengths smaller and larger than what the stream gives"""
+    import crafted_streams as CS
+    Z = {c.name: c for c in CS.lz_cases()}
+    szdd = lambda c, n=None: CS.szdd_container(c.stream, c.out_len if n is None else n)
+    qbasic = lambda c, n=None: CS.szdd_container(c.stream, c.out_len if n is None else n, qbasic=True)
+    kwaj = lambda c, method, n=None: CS.kwaj_container(c.stream, method, c.out_len if n is None else n)
+    c = Z["lzh_one_bit_trees_17_bytes_a_byte"]
+    return [
+        ("szdd_maximum_expansion", 0, szdd(Z["lzss_maximum_expansion_680_bytes_in_mode0"])),
+        ("szdd_maximum_expansion_one_group", 0, szdd(Z["lzss_maximum_expansion_17_bytes_in_mode0"])),
+        ("kwaj_lzh_maximum_expansion", 1, kwaj(c, 3)),
+        ("szdd_source_in_the_prefill", 0, szdd(Z["lzss_first_item_is_a_match_at_distance_4096_mode0"])),
+        ("szdd_qbasic_source_in_the_prefill", 0, qbasic(Z["lzss_first_item_is_a_match_at_distance_18_mode2"])),
+        ("szdd_source_from_the_prefill_into_data", 0, szdd(Z["lzss_source_from_the_prefill_into_data_mode0"])),
+        ("szdd_qbasic_every_control_byte", 0, qbasic(Z["lzss_every_control_byte_mode2"])),
+        ("kwaj_method_2_every_control_byte", 1, kwaj(Z["lzss_every_control_byte_mode2"], 2)),
+        ("kwaj_method_2_every_distance", 1, kwaj(Z["lzss_every_distance_at_length_3_mode2"], 2)),
+        ("kwaj_method_3_sixteen_bit_code", 1, kwaj(Z["lzh_literal_codes_of_every_length_1_to_16"], 3)),
+        ("kwaj_method_3_token_in_the_padding", 1, kwaj(Z["lzh_end_with_5_spare_bits_a_token_in_the_padding"], 3)),
+        ("kwaj_method_3_refused_tree", 1, kwaj(Z["lzh_tree_3_oversubscribed_long_codes_only"], 3)),
+        ("szdd_stated_length_smaller", 0, szdd(Z["lzss_overlapping_matches_mode0"], 10)),
+        ("szdd_stated_length_larger", 0, szdd(Z["lzss_overlapping_matches_mode0"], 100000)),
+        ("kwaj_method_3_stated_length_smaller", 1, kwaj(Z["lzh_every_match_length_in_both_tables"], 3, 7)),
+        ("kwaj_method_3_stated_length_larger", 1, kwaj(Z["lzh_every_match_length_in_both_tables"], 3, 1 << 20)),
+    ]
+
+
+_GC = os.path.join(HERE, "golden", "szdd_kwaj_crafted.json")
+GC = {e["name"]: e for e in json.load(open(_GC))} if os.path.exists(_GC) else {}
+
+
+def check_crafted_file(name, L=None):
+    _n, kind, blob = {c[0]: c for c in crafted_file_cases()}[name]
+    g = GC[name]
+    assert hashlib.md5(blob).hexdigest() == g["blob_md5"]
+    assert sig(api.szdd_kwaj_extract(kind, blob, L=L)) == g["ok"]
+
+
+def test_crafted_goldens_are_all_there():
+    assert sorted(GC) == sorted(c[0] for c in crafted_file_cases()) and len(GC) >= 12
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", sorted(GC))
+def test_crafted_files_vs_reference(built, name):
+    check_crafted_file(name)
+
+
+@pytest.mark.parametrize("name", sorted(GC))
+def test_crafted_files_vs_reference_host_logic_cpu(built, hostlogic, name):
+    check_crafted_file(name, L=hostlogic)
