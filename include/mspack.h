@@ -168,6 +168,7 @@ struct mscabd_file {
 /* extensions of this library (ids >= 100; the reference answers MSPACK_ERR_ARGS to them) */
 #define MSCABD_PARAM_HIP_DEVICES  (100)  /* GPUs to shard a batch over (default 1)               */
 #define MSCABD_PARAM_HIP_CACHE_MB (101)  /* decoded-folder cache budget in MiB (default 2048)    */
+#define MSCABD_PARAM_HIP_MD5      (102)  /* 1: batches carry one MD5 digest unit per file, for mspack_cabd_md5() (default 0) */
 
 struct mscab_decompressor {
   struct mscabd_cabinet * (*open) (struct mscab_decompressor *self, const char *filename);
@@ -202,6 +203,28 @@ struct mscab_decompressor {
  * With at least two folders on one device the batch runs as a job: the call returns at once and each extract() waits for
  * its own folder only.  Closing a cabinet while the batch runs takes its folders out of it; the other cabinets' stay. */
 extern int mspack_cabd_prefetch(struct mscab_decompressor *self, struct mscabd_cabinet **cabs, int n_cabs);
+
+/* The MD5 of a file: extract() with the writes replaced by a hash -- what `cabextract -t` and package verifiers do with the bytes.
+ *   returns   the code extract(file, ...) would return at this point of this decompressor's life, and it COUNTS as that call for
+ *             everything that follows: the decompressor's sticky state (a later extract() of the same folder sees what it would
+ *             see after an extract() here), Quantum's held-back bytes, the salvage rules, and the lines said through
+ *             sys->message -- the same lines, in this call.  It opens no output file and never calls sys->write.
+ *   digest    with MSPACK_ERR_OK the MD5 (RFC 1321) of exactly the bytes extract() would have handed to sys->write; with any
+ *             other code sixteen zero bytes.  last_error() answers the same.  A NULL argument: MSPACK_ERR_ARGS.
+ * With MSCABD_PARAM_HIP_MD5 set to 1 (before the batch is built: the cabinet's first extract() / md5() / mspack_cabd_prefetch())
+ * and a batch provider that reports MSPACK_HIP_FEAT_MD5, the batch that decodes the folders carries one digest unit per file and
+ * the digests are kept with the folders: md5() of a file that is good as a whole answers from there.  Everything else is hashed
+ * on the host: the param off, stored folders (hashed as they stream), files whose call hands over something other than their
+ * plain range (a failing call, what Quantum held back), and files too long for one lane of the device (DESIGN.md section 5;
+ * MSPACK_HIP_MD5_RATIO).  The digests are the same either way.
+ * The price of the param: digest units are through only when the whole batch is, so a batch that carries some does not run as a
+ * job -- mspack_cabd_prefetch() and a cabinet's first extract() / md5() then return when every folder of the batch is decoded and
+ * its slowest digest lane has ended, instead of at once / when their own folder is through.  Leave the param off for callers
+ * that extract. */
+extern int mspack_cabd_md5(struct mscab_decompressor *self, struct mscabd_file *file, unsigned char digest[16]);
+/* diagnostics: how many successful mspack_cabd_md5() calls of this process were answered from a digest taken on the device
+ * (counts[0]) and how many were hashed on the host (counts[1]); counts may be NULL; reset != 0 clears them after reading. */
+extern void mspack_cabd_md5_counts(unsigned long long counts[2], int reset);
 
 /* ---- CHM ---------------------------------------------------------------------------------------------- */
 struct mschm_decompressor;

@@ -45,6 +45,23 @@ extern "C" {
                                        per block part into the batch that decodes the folders: the bytes are in HBM anyway, and
                                        it compares with the CFDATA headers (cabd.c:1411-1417) when the results are back        */
 
+#define MSPACK_HIP_KIND_MD5      8   /* a digest unit: the MD5 (RFC 1321) of the bytes [out_off, out_off + out_len) of the OUTPUT arena as they
+                                       lie there once every decoding unit of the batch has stored its output (E8 and resume passes
+                                       included; units that fail too: the digest is of whatever is there).  Decodes nothing: in_len
+                                       must be 0, in_off is ignored, MSPACK_HIP_UF_CRC32 is rejected, every other flag is ignored;
+                                       out_len 0 to 2^32-1.  The range may cover part of a decoding unit's region, several regions
+                                       and the padding between them; ranges of different digest units may overlap.  Only reads the
+                                       arena: every byte and every other unit's result are those of the batch without it.  Result:
+                                       err 0, flags 0, and the sixteen digest bytes in RFC 1321's order in the sixteen bytes of
+                                       out_len, in_used, good_len, in_next (A, B, C, D little-endian): memcpy(digest,
+                                       &result.out_len, 16).  What "the bytes that lie there" are depends on the entry point: the
+                                       device-resident entry and _to_device hash the caller's device buffer as it is; the entry points
+                                       with a HOST output hash the device's copy of the arena, which holds what THIS call's decoding
+                                       units stored (and LZX DELTA reference data) and nothing of the caller's host buffer -- bytes
+                                       of a range that no unit of the call wrote (padding between units, a batch of digest units
+                                       alone) are unspecified there, and so is a digest over them (err is still 0).  One lane per range (MD5 is one chain per message): the device wins
+                                       with many ranges at once.  Ask mspack_hip_features() & MSPACK_HIP_FEAT_MD5 first       */
+
 #define MSPACK_HIP_MASK_FRAME_TABLES 0x80000000u   /* mspack_hip_decode_batch_device(kind_mask): see there */
 #define MSPACK_HIP_MASK_CRC32        0x40000000u   /* mspack_hip_decode_batch_device(kind_mask): units may carry MSPACK_HIP_UF_CRC32 */
 
@@ -167,6 +184,7 @@ const char *mspack_hip_last_error(void);
 /* capability word: what this provider of the batch ABI can do beyond version 0.3 (a driver that may be linked against
  * another provider declares the function weak and treats its absence as 0) */
 #define MSPACK_HIP_FEAT_CRC32 1u        /* MSPACK_HIP_UF_CRC32 / MSPACK_HIP_MASK_CRC32 */
+#define MSPACK_HIP_FEAT_MD5   2u        /* MSPACK_HIP_KIND_MD5 */
 unsigned mspack_hip_features(void);
 
 /* ---- device-resident batch decode (the hot path proper) ---------------------------------------
@@ -192,6 +210,9 @@ unsigned mspack_hip_features(void);
  *                units of other kinds are skipped); 0 = all three codecs.
  *                MSPACK_HIP_MASK_CRC32 set = units may carry MSPACK_HIP_UF_CRC32: only then is the digest pass launched
  *                behind the codecs (two more launches; flagged units of a kind the mask leaves out get no digest worth reading)
+ *                bit MSPACK_HIP_KIND_MD5 set = digest units may be present: only then is the MD5 pass launched, behind everything
+ *                else on the stream (one more launch; 0 still means "all codecs" and launches no digest pass; a mask of this bit
+ *                alone launches the MD5 pass only)
  * MSZIP units need 32768 bytes of slack after out_len in their output region.
  * Units with a frame / block table: the parse wavefronts store literals into the unit's output region (for MSZIP incl. its
  * slack) before the unit is known to decode; the first result.out_len bytes are the decoded data, the rest of the region
@@ -218,6 +239,11 @@ size_t mspack_hip_frame_scratch_bytes(size_t n_frames_total);
  * DMA that need not wait for the other streams; a buffer that cannot be registered is copied the ordinary way (MSPACK_HIP_PIN_OUT=0: always).
  * `units[i].frame_base` is filled in by the call.  Synchronous.  Bytes of the output arena
  * BETWEEN units that lie inside a copied span (alignment padding, the MSZIP slack) are unspecified afterwards.
+ * Digest units (MSPACK_HIP_KIND_MD5) are kept out of the chunk cutting; their pass runs once per device, behind the last chunk's
+ * launches and before the results go back -- over the device's copy of the output arena, which holds what this call's decoding
+ * units stored (bytes of a range that no unit of the call wrote are unspecified).  mspack_hip_job_wait_unit() on a digest unit
+ * returns when the batch is through.  mspack_hip_decode_batch_multi never cuts its shards inside a digest range (at worst it
+ * makes fewer shards); a digest unit goes to the shard that holds its range.
  * Thread-safe; calls that target the same device are serialised. */
 int mspack_hip_decode_batch(mspack_hip_unit *units, size_t n_units, const void *in, size_t in_bytes,
                             void *out, size_t out_bytes, mspack_hip_result *results);

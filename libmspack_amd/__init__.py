@@ -15,11 +15,15 @@ HIP_SO = os.environ.get("MSPACK_HIP_SO", os.path.join(HERE, "libmspack_hip.so"))
 CORPUS_SO = os.path.join(HERE, "libmspack_corpus.so")
 
 KIND_MSZIP, KIND_QUANTUM, KIND_LZX, KIND_LZX_DELTA, KIND_LZSS, KIND_KWAJ_LZH = 1, 2, 3, 4, 5, 6
+KIND_XORSUM = 7
+KIND_MD5 = 8                 # a digest unit: the MD5 of out[out_off : out_off + out_len] once the batch's decoding units have stored
 F_E8_APPLIED, F_LOOKAHEAD_READ, F_INTEL_HEADER, F_BLOCK_OPEN, F_FRAMES_ADOPTED = 1, 2, 4, 16, 32
 UF_MSZIP_REPAIR = 1
 UF_CRC32 = 128               # result.in_used = CRC-32 (OAB flavour: zlib.crc32(out[:out_len]) ^ 0xFFFFFFFF) of the decoded bytes
 MASK_CRC32 = 0x40000000      # decode_batch_device(kind_mask): launch the digest pass
 FEAT_CRC32 = 1
+FEAT_MD5 = 2
+MASK_MD5 = 1 << KIND_MD5     # decode_batch_device(kind_mask): launch the MD5 pass
 ERR_OK, ERR_ARGS, ERR_OPEN, ERR_READ, ERR_WRITE, ERR_SEEK, ERR_NOMEMORY, ERR_SIGNATURE, \
     ERR_DATAFORMAT, ERR_CHECKSUM, ERR_CRUNCH, ERR_DECRUNCH = range(12)
 
@@ -175,6 +179,33 @@ def decode_batch(units, in_arena, out_bytes, n_devices=1, refs=None):
                                        out.ctypes.data, out.size, res.ctypes.data)
     _check(rc, "mspack_hip_decode_batch")
     return out, res
+
+
+def md5_units(ranges):
+    """digest units (KIND_MD5) for (out_off, out_len) ranges of the output arena"""
+    u = np.zeros(len(ranges), dtype=UNIT_DTYPE)
+    u["kind"] = KIND_MD5
+    u["out_off"] = [int(r[0]) for r in ranges]
+    u["out_len"] = [int(r[1]) for r in ranges]
+    return u
+
+
+def result_digests(res):
+    """the sixteen digest bytes of digest units' results (out_len, in_used, good_len, in_next) -> list of bytes"""
+    raw = np.ascontiguousarray(res).view(np.uint8).reshape(len(res), RESULT_DTYPE.itemsize)
+    return [raw[i, 8:24].tobytes() for i in range(len(res))]
+
+
+def decode_batch_md5(units, in_arena, out_bytes, ranges, n_devices=1, refs=None):
+    """decode_batch with one digest unit per (out_off, out_len) range appended to the batch
+    -> (out, the decoding units' results, the ranges' MD5 digests as bytes)"""
+    n = len(units)
+    both = np.concatenate([np.ascontiguousarray(units, dtype=UNIT_DTYPE), md5_units(ranges)])
+    out, res = decode_batch(both, in_arena, out_bytes, n_devices=n_devices, refs=refs)
+    bad = res[n:][res["err"][n:] != 0]
+    if len(bad):
+        raise MspackHipError("a digest unit failed: %r" % (bad[0],))
+    return out, res[:n], result_digests(res[n:])
 
 
 # ---- corpus generators (test / bench infrastructure) ---------------------------------------------

@@ -103,7 +103,7 @@ MschmDecompressor._fields_ = [
 ]
 
 MSCABD_PARAM_SEARCHBUF, MSCABD_PARAM_FIXMSZIP, MSCABD_PARAM_DECOMPBUF, MSCABD_PARAM_SALVAGE = 0, 1, 2, 3
-MSCABD_PARAM_HIP_DEVICES, MSCABD_PARAM_HIP_CACHE_MB = 100, 101
+MSCABD_PARAM_HIP_DEVICES, MSCABD_PARAM_HIP_CACHE_MB, MSCABD_PARAM_HIP_MD5 = 100, 101, 102
 MSPACK_ERR_OK, MSPACK_ERR_ARGS = 0, 1
 
 
@@ -120,9 +120,20 @@ def _setup(L=None):
     L.mspack_destroy_chm_decompressor.argtypes = [_P(MschmDecompressor)]
     L.mspack_cabd_prefetch.restype = C.c_int
     L.mspack_cabd_prefetch.argtypes = [_P(MscabDecompressor), _P(_P(MscabdCabinet)), C.c_int]
+    L.mspack_cabd_md5.restype = C.c_int
+    L.mspack_cabd_md5.argtypes = [_P(MscabDecompressor), _P(MscabdFile), C.c_void_p]
+    L.mspack_cabd_md5_counts.restype = None
+    L.mspack_cabd_md5_counts.argtypes = [C.c_void_p, C.c_int]
     L.mspack_version.argtypes = [C.c_int]
     L.mspack_sys_selftest_internal.argtypes = [C.c_int]
     return L
+
+
+def cabd_md5_counts(reset=False, L=None):
+    """mspack_cabd_md5_counts (mspack.h): successful md5() calls of this process answered (from a device digest, by the host's MD5)"""
+    c = (C.c_ulonglong * 2)()
+    _setup(L).mspack_cabd_md5_counts(c, int(reset))
+    return int(c[0]), int(c[1])
 
 
 class MspackSystem(C.Structure):
@@ -263,6 +274,16 @@ class Cab:
         finally:
             os.unlink(out)
 
+    def set_param(self, param, value):
+        return self.d.contents.set_param(self.d, param, value)
+
+    def md5(self, i):
+        """mspack_cabd_md5 (mspack.h): extract(i) with the writes replaced by a hash -> (err, the sixteen digest bytes; zeros unless
+        err == 0).  set_param(MSCABD_PARAM_HIP_MD5, 1) before the first call lets the batch take the digests on the device"""
+        d = (C.c_ubyte * 16)()
+        err = self.L.mspack_cabd_md5(self.d, self._files[i], d)
+        return err, bytes(d)
+
     def close(self):
         if self.cab:
             self.d.contents.close(self.d, self.cab); self.cab = None
@@ -344,6 +365,15 @@ class CabSet:
                         folders.index(C.addressof(fo.contents)) if fo else -1,
                         fo.contents.num_blocks if fo else 0))
         return out
+
+    def set_param(self, param, value):
+        return self.d.contents.set_param(self.d, param, value)
+
+    def md5(self, fptr):
+        """mspack_cabd_md5 (mspack.h) of a file of file_ptrs() -> (err, the sixteen digest bytes)"""
+        d = (C.c_ubyte * 16)()
+        err = self.L.mspack_cabd_md5(self.d, fptr, d)
+        return err, bytes(d)
 
     def extract(self, fptr):
         if self.mem:

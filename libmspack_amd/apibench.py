@@ -32,6 +32,8 @@ def lib():
             fn.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint, C.POINTER(Stats)]
         L.mspk_api_bench_cabs.restype = C.c_int
         L.mspk_api_bench_cabs.argtypes = [C.c_void_p, C.c_void_p, C.c_uint, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(Stats)]
+        L.mspk_api_bench_cabs_md5.restype = C.c_int
+        L.mspk_api_bench_cabs_md5.argtypes = [C.c_void_p, C.c_void_p, C.c_uint, C.c_int, C.c_int, C.c_void_p, C.c_uint, C.POINTER(Stats)]
         L.mspk_api_cab_run.restype = C.c_int
         L.mspk_api_cab_run.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]
@@ -77,6 +79,21 @@ def run_cabs(images, out_cap, prefetch, L=None):
     st = Stats()
     rc = L.mspk_api_bench_cabs(blob.ctypes.data, offs.ctypes.data, len(images), int(bool(prefetch)), out.ctypes.data, int(out_cap), C.byref(st))
     return rc, out[:st.bytes_out], {k: getattr(st, k) for k, _t in Stats._fields_}
+
+
+def run_cabs_md5(images, prefetch, hip_md5, max_files=65536, L=None):
+    """mspack_cabd_md5() of every file of these cabinet images on one decompressor (mspk_api_bench_cabs_md5), MSCABD_PARAM_HIP_MD5 =
+    hip_md5.  -> (rc, [digest bytes per file], stats dict)"""
+    L = L or lib()
+    offs = np.zeros(len(images) + 1, dtype=np.uint64)
+    offs[1:] = np.cumsum([len(i) for i in images])
+    blob = np.frombuffer(b"".join(bytes(i) for i in images), dtype=np.uint8)
+    dg = np.zeros(16 * max_files, dtype=np.uint8)
+    st = Stats()
+    rc = L.mspk_api_bench_cabs_md5(blob.ctypes.data, offs.ctypes.data, len(images), int(bool(prefetch)), int(hip_md5), dg.ctypes.data,
+                                   max_files, C.byref(st))
+    n = min(st.n_files, max_files)
+    return rc, [dg[16 * i:16 * i + 16].tobytes() for i in range(n)], {k: getattr(st, k) for k, _t in Stats._fields_}
 
 
 def build_small_cabs(M, n=4096, ub=32768, plain=None):

@@ -230,6 +230,65 @@ int mspk_api_bench_cabs(const unsigned char *images, const unsigned long long *o
   return rc;
 }
 
+/* the same cabinets, every file's MD5 through mspack_cabd_md5() instead of extract() (tools/md5_bench.py): hip_md5 = the value of
+ * MSCABD_PARAM_HIP_MD5; digests receives sixteen bytes per file, in call order (at most max_files of them).  One image with
+ * prefetch == 0 is "one cabinet": its first md5() forms the batch. */
+int mspk_api_bench_cabs_md5(const unsigned char *images, const unsigned long long *offs, unsigned int n_cabs, int prefetch, int hip_md5,
+                            unsigned char *digests, unsigned int max_files, mspk_api_stats *st)
+{
+  struct mem_sys ms;
+  struct mscab_decompressor *d;
+  struct mscabd_cabinet **cabs;
+  char (*names)[12];
+  unsigned int k;
+  double t0, t1;
+  int rc = 0;
+  memset(st, 0, sizeof(*st));
+  mem_sys_init(&ms, images, (size_t) offs[n_cabs], NULL, 0);
+  ms.many_offs = offs; ms.n_many = n_cabs;
+  cabs = (struct mscabd_cabinet **) calloc(n_cabs ? n_cabs : 1, sizeof(*cabs));
+  names = (char (*)[12]) calloc(n_cabs ? n_cabs : 1, sizeof(*names));
+  if (!cabs || !names) { free(cabs); free(names); return -1; }
+  mspack_hip_host_path_stats(NULL, 1);
+  t0 = now_s();
+  if (!(d = mspack_create_cab_decompressor(&ms.sys))) { free(cabs); free(names); return -1; }
+  if (d->set_param(d, MSCABD_PARAM_HIP_MD5, hip_md5)) rc = -4;
+  t1 = now_s();
+  for (k = 0; k < n_cabs && !rc; k++) {
+    snprintf(names[k], sizeof(names[k]), "c%u", k);
+    if (!(cabs[k] = d->open(d, names[k]))) { st->first_error = d->last_error(d); rc = -2; }
+  }
+  st->open_s = now_s() - t1;
+  if (!rc && prefetch) {
+    const double e0 = now_s();
+    const int err = mspack_cabd_prefetch(d, cabs, (int) n_cabs);
+    st->first_extract_s = now_s() - e0;
+    if (err) { st->first_error = err; rc = -3; }
+  }
+  for (k = 0; k < n_cabs && !rc; k++) {
+    struct mscabd_file *f;
+    for (f = cabs[k]->files; f; f = f->next) {
+      unsigned char dg[16];
+      const double e0 = now_s();
+      const int err = mspack_cabd_md5(d, f, dg);
+      if (st->n_files == 0 && !prefetch) st->first_extract_s = now_s() - e0;
+      if (err) { if (!st->n_errors) st->first_error = err; st->n_errors++; }
+      if (digests && st->n_files < max_files) memcpy(digests + 16 * (size_t) st->n_files, dg, 16);
+      st->bytes_out += f->length;
+      st->n_files++;
+    }
+  }
+  for (k = 0; k < n_cabs; k++) if (cabs[k]) d->close(d, cabs[k]);
+  mspack_destroy_cab_decompressor(d);
+  {
+    const unsigned long long hashed = st->bytes_out;
+    finish(&ms, st, t0);
+    st->bytes_out = hashed;                 /* (nothing was written: the bytes the digests cover) */
+  }
+  free(cabs); free(names);
+  return rc;
+}
+
 /* one CHM image: open, extract every file of the directory in list order */
 int mspk_api_bench_chm(const unsigned char *chm, size_t chm_len, unsigned char *out, size_t out_cap,
                        unsigned long long *offsets, unsigned int max_files, mspk_api_stats *st)

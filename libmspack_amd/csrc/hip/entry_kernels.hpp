@@ -573,3 +573,16 @@ void mspack_crc32(const mspack_hip_unit *units, const u32 *order, u32 n_units, u
   if (!crc_unit_wanted(u)) return;
   crc_unit_segments(u, out_arena, &results[ui], y, segs_y, &sh);
 }
+
+// MSPACK_HIP_KIND_MD5 (md5_kernel.hpp): one digest unit per LANE, launched behind everything that stores into the output arena --
+// stream order is the only ordering.  Lanes whose unit is of another kind leave at once.
+__global__ __launch_bounds__(64)
+void mspack_md5(const mspack_hip_unit *units, const u32 *order, u32 n_units, const u8 *out_arena, u64 out_bytes, mspack_hip_result *results)
+{
+  const u32 j = blockIdx.x * 64u + threadIdx.x;
+  if (j >= n_units) return;
+  const u32 ui = order ? order[j] : j;
+  const mspack_hip_unit u = units[ui];
+  if (u.kind != MSPACK_HIP_KIND_MD5) return;
+  md5_unit(u, out_arena, out_bytes, &results[ui]);
+}

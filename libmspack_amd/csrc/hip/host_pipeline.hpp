@@ -337,6 +337,13 @@ static int issue_chunks(PipeCall &pc, CopyBack &cb)
       TRY(launch_kind(k, pc.d_units, pc.d_order + c.order_off[k], c.order_n[k], d_in, d_out, pc.d_res, cx.d_fm.p, plan.n_frames, c.fm_lo, c.fm_n, st,
                       c.has_ftab, (unsigned) ci, plan.n_rec_slots, one));
     if (c.crc_n) TRY(launch_crc32(pc.d_units, pc.d_order + c.crc_off, c.crc_n, c.crc_max, d_out, pc.d_res, st));      // behind every codec's store of its results
+    if (plan.n_md5 && ci + 1 == plan.chunks.size()) {
+      // the digest units' pass: once, on the last chunk's stream, behind every chunk's launches -- the bytes it reads are all stored
+      const size_t m0 = n_sel - plan.n_md5;
+      if (!one) for (size_t cj = 0; cj < ci; cj++) TRY(hipStreamWaitEvent(st, cx.ev_done[cj], 0));
+      TRY(launch_md5(pc.d_units, pc.d_order + plan.md5_off, plan.n_md5, d_out, pc.out_span, pc.d_res, st));
+      TRY(hipMemcpyAsync(pc.h_res + m0, pc.d_res + m0, plan.n_md5 * sizeof(mspack_hip_result), hipMemcpyDeviceToHost, st));
+    }
     TRY(hipMemcpyAsync(pc.h_res + c.a, pc.d_res + c.a, (c.b - c.a) * sizeof(mspack_hip_result), hipMemcpyDeviceToHost, st));
     if (!one) { TRY(hipEventRecord(cx.ev_done[ci], st)); cb.issued.store(ci + 1, std::memory_order_release); }
   }
@@ -458,6 +465,7 @@ static int pipeline_on_current_device(int dev, mspack_hip_unit *units, const uin
     if (pg) {
       std::lock_guard<std::mutex> lk(pg->mu);
       for (size_t ci = 0; ci < plan.chunks.size(); ci++) for (size_t i = plan.chunks[ci].a; i < plan.chunks[ci].b; i++) pg->chunk_of[plan.idx[i]] = (uint32_t) ci;
+      for (size_t i = plan.local.size() - plan.n_md5; i < plan.local.size(); i++) pg->chunk_of[plan.idx[i]] = (uint32_t) plan.chunks.size();      // (digest units: when the batch is through)
       pg->planned = true;
       pg->cv.notify_all();
     }
@@ -556,35 +564,10 @@ int mspack_hip_decode_batch_multi(mspack_hip_unit *units, size_t n_units, const 
   if (force_shards) n_shards = env_int("MSPACK_HIP_FORCE_SHARDS", 2, 1, MSPK_MAX_DEV);
   if (n_shards <= 1 || n_units < 2) return mspack_hip_decode_batch(units, n_units, in, in_bytes, out, out_bytes, results);
   if (n_devices < 1) { snprintf(g_err, sizeof(g_err), "no HIP device"); return -1; }
-  // static sharding, no inter-device traffic: units in arena order are cut into n_shards CONTIGUOUS ranges of
-  // about equal compressed size, so that every device stages one contiguous span of each arena
-  std::vector<uint32_t> idx(n_units);
-  for (size_t i = 0; i < n_units; i++) idx[i] = (uint32_t) i;
-  std::stable_sort(idx.begin(), idx.end(), [&](uint32_t a, uint32_t b) { return units[a].in_off < units[b].in_off; });
-  uint64_t total = 0;
-  for (size_t i = 0; i < n_units; i++) total += (uint64_t) units[i].in_len + (units[i].out_len >> 2) + 256u;
-  std::vector<std::vector<uint32_t>> shard(n_shards);
-  {
-    uint64_t acc = 0; int s = 0;
-    for (size_t i = 0; i < n_units; i++) {
-      shard[s].push_back(idx[i]);
-      acc += (uint64_t) units[idx[i]].in_len + (units[idx[i]].out_len >> 2) + 256u;
-      if (s + 1 < n_shards && acc * n_shards >= total * (uint64_t)(s + 1)) s++;
-    }
-  }
-  // every shard copies its whole output span back with one copy -- valid only if the spans do not interleave, i.e. if
-  // the outputs ascend with the inputs over the WHOLE batch; otherwise the shards copy back unit by unit
+  // static sharding, no inter-device traffic: plan_shards (host_plan.hpp)
+  std::vector<std::vector<uint32_t>> shard;
   bool ascending = true;
-  {
-    uint64_t prev_hi = 0;
-    for (size_t i = 0; i < n_units && ascending; i++) {
-      const mspack_hip_unit &u = units[idx[i]];
-      if (u.kind == MSPACK_HIP_KIND_XORSUM) continue;       // (no output)
-      const uint64_t lo = u.out_off - std::min<uint64_t>(u.out_off, unit_below(u)), hi = u.out_off + u.out_len + unit_above(u);
-      if (lo < prev_hi) ascending = false;
-      prev_hi = std::max(prev_hi, hi);
-    }
-  }
+  if (!plan_shards(units, n_units, n_shards, shard, ascending)) return mspack_hip_decode_batch(units, n_units, in, in_bytes, out, out_bytes, results);
   std::vector<int> rcs(n_shards, 0);
   std::vector<std::array<char, 256>> errs(n_shards);
   std::vector<std::thread> th;

@@ -1,5 +1,5 @@
 // host_plan.hpp -- the host path's chunk planner: from the caller's unit table to a BatchPlan (units in arena order, frame-slot
-// numbers, chunks with their spans, per-kind launch lists and CRC lists, the units rebased to the spans).  Pure arithmetic: no HIP
+// numbers, chunks with their spans, per-kind launch lists and CRC lists, the digest units' list, the units rebased to the spans).  Pure arithmetic: no HIP
 // call, no global, no environment variable, no lock -- only <mspack_hip.h> and standard headers, so a test includes this file alone
 // (tests/hostcheck/plan_check.cpp).  The knobs come in as a PlanKnobs (host_pipeline.hpp fills one from the environment).
 #pragma once
@@ -61,7 +61,10 @@ struct PlanKnobs {
   std::vector<uint64_t> weights;                    // the first shares spelled out (sweeps)
 };
 // what plan_batch computes.  local[i] is unit idx[i] of the caller's table, offsets relative to in_lo / out_lo; the chunks are
-// ranges of local[]; order holds every chunk's per-kind lists and its CRC list (indices into local[])
+// ranges of local[]; order holds every chunk's per-kind lists and its CRC list (indices into local[]).
+// Digest units (MSPACK_HIP_KIND_MD5) read no input and own no output: they stand BEHIND the chunks in local[] -- indices
+// [n - n_md5, n), no chunk holds them, no per-kind list, no weight in the cutting -- and order[md5_off .. md5_off + n_md5) lists
+// them longest range first (one lane each: lanes of similar length next to each other) for the one pass behind the last chunk
 struct BatchPlan {
   std::vector<uint32_t> idx;
   std::vector<mspack_hip_unit> local;
@@ -69,6 +72,7 @@ struct BatchPlan {
   std::vector<Chunk> chunks;
   uint64_t in_lo, in_hi, out_lo, out_hi, in_sum;
   size_t n_frames, n_rec_slots, n_crc;              // n_crc: units that want a digest (MSPACK_HIP_UF_CRC32)
+  size_t n_md5 = 0, md5_off = 0;                    // the digest units: how many, their list's place in order
   bool monotone, has_qtm;
 };
 
@@ -81,6 +85,12 @@ static int plan_units(mspack_hip_unit *units, const uint32_t *sel, size_t n_sel,
   idx.resize(n_sel);
   for (size_t i = 0; i < n_sel; i++) idx[i] = sel ? sel[i] : (uint32_t) i;
   std::stable_sort(idx.begin(), idx.end(), [&](uint32_t x, uint32_t y) { return units[x].in_off < units[y].in_off; });
+  // (digest units behind everything else, in the caller's order: their in_off means nothing)
+  {
+    const auto mid = std::stable_partition(idx.begin(), idx.end(), [&](uint32_t x) { return units[x].kind != MSPACK_HIP_KIND_MD5; });
+    std::sort(mid, idx.end());
+    p.n_md5 = (size_t)(idx.end() - mid);
+  }
   local.resize(n_sel);
   bool monotone = !per_unit_back;
   uint64_t in_lo = ~0ull, in_hi = 0, out_lo = ~0ull, out_hi = 0, prev_hi = 0, in_sum = 0;
@@ -90,12 +100,20 @@ static int plan_units(mspack_hip_unit *units, const uint32_t *sel, size_t n_sel,
     u = units[idx[i]];
     if (u.kind != MSPACK_HIP_KIND_LZX_DELTA && !(u.kind == MSPACK_HIP_KIND_LZX && (u.flags & MSPACK_HIP_UF_LZX_LOG)) &&
         !(u.kind == MSPACK_HIP_KIND_QUANTUM && (u.flags & MSPACK_HIP_UF_QTM_MARKS))) u.ref_len = 0;
-    if (u.kind > MSPACK_HIP_KIND_XORSUM) { snprintf(errbuf, errcap, "unit %u: unknown kind %u", idx[i], u.kind); return -1; }
+    if (u.kind > MSPACK_HIP_KIND_MD5) { snprintf(errbuf, errcap, "unit %u: unknown kind %u", idx[i], u.kind); return -1; }
     if (u.kind == MSPACK_HIP_KIND_XORSUM) {                // reads its input, owns no output
       if (u.flags & MSPACK_HIP_UF_CRC32) { snprintf(errbuf, errcap, "unit %u: a checksum unit decodes nothing to take a CRC-32 of", idx[i]); return -1; }
       if (u.out_len) { snprintf(errbuf, errcap, "unit %u: a checksum unit has no output", idx[i]); return -1; }
       if (u.in_off + u.in_len > in_bytes) { snprintf(errbuf, errcap, "unit outside arena"); return -1; }
       in_lo = std::min<uint64_t>(in_lo, u.in_off); in_hi = std::max<uint64_t>(in_hi, u.in_off + u.in_len);
+      continue;
+    }
+    if (u.kind == MSPACK_HIP_KIND_MD5) {                   // reads a range of the output arena, owns nothing
+      if (u.flags & MSPACK_HIP_UF_CRC32) { snprintf(errbuf, errcap, "unit %u: a digest unit decodes nothing to take a CRC-32 of", idx[i]); return -1; }
+      if (u.in_len) { snprintf(errbuf, errcap, "unit %u: a digest unit reads no input (in_len must be 0)", idx[i]); return -1; }
+      if (u.out_off > out_bytes || u.out_len > out_bytes - u.out_off) { snprintf(errbuf, errcap, "unit %u: a digest unit's range leaves the output arena", idx[i]); return -1; }
+      u.in_off = 0; u.flags = 0;
+      if (u.out_len) { out_lo = std::min<uint64_t>(out_lo, u.out_off); out_hi = std::max<uint64_t>(out_hi, u.out_off + u.out_len); }
       continue;
     }
     // kind 0 = "no codec": the unit is carried along, no kernel takes it, its result says MSPACK_ERR_ARGS
@@ -128,6 +146,7 @@ static int plan_units(mspack_hip_unit *units, const uint32_t *sel, size_t n_sel,
     }
     if (pass == 0) n_rec_slots = n_frames;
   }
+  if (in_lo > in_hi) in_lo = in_hi = 0;                // (digest units only: nothing is read)
   in_lo &= ~15ull;                                     // keep the units' alignment
   if (out_lo > out_hi) out_lo = out_hi = 0;            // (checksum units only: nothing is written)
   if (dev_out) out_lo = 0;                             // the caller's device buffer is addressed as is
@@ -140,7 +159,7 @@ static int plan_units(mspack_hip_unit *units, const uint32_t *sel, size_t n_sel,
 static void plan_chunks(bool to_host, const PlanKnobs &kn, BatchPlan &p)
 {
   const std::vector<mspack_hip_unit> &local = p.local;
-  const size_t n_sel = local.size();
+  const size_t n_sel = local.size() - p.n_md5;          // (the digest units stand behind the chunks)
   const bool monotone = p.monotone;
   const uint64_t in_sum = p.in_sum;
   // chunks: arena-contiguous runs of units; enough of them to overlap the copies with the decode, each
@@ -199,6 +218,7 @@ static void plan_chunks(bool to_host, const PlanKnobs &kn, BatchPlan &p)
         Chunk c; c.a = a; c.b = i + 1; upto += w[chunks.size()]; chunks.push_back(c); a = i + 1;
       }
     }
+    if (chunks.empty()) { Chunk c; c.a = c.b = 0; chunks.push_back(c); }      // (digest units only: one chunk that holds nothing)
   }
 }
 
@@ -210,7 +230,7 @@ static void plan_lists(BatchPlan &p)
   const size_t n_sel = local.size(), n_crc = p.n_crc;
   const uint64_t out_lo = p.out_lo;
   std::vector<uint32_t> &order = p.order;
-  order.assign(n_sel + n_crc, 0u);
+  order.assign(n_sel + n_crc, 0u);                     // (the digest units are in no per-kind list: their own list fills the room)
   size_t op = 0;
   uint64_t ci_prev_hi = out_lo == ~0ull ? 0 : out_lo;
   for (Chunk &c : chunks) {
@@ -230,6 +250,7 @@ static void plan_lists(BatchPlan &p)
       c.out_hi = std::max<uint64_t>(c.out_hi, u.out_off + u.out_len + unit_above(u));
     }
     if (c.out_lo > c.out_hi) c.out_lo = c.out_hi = (ci_prev_hi);         // (a chunk of checksum units only: an empty span)
+    if (c.in_lo > c.in_hi) c.in_lo = c.in_hi = p.in_lo;                  // (the chunk that holds nothing)
     ci_prev_hi = c.out_hi;
     if (c.fm_lo == ~(size_t) 0) c.fm_lo = 0;
     c.in_lo &= ~15ull;
@@ -250,6 +271,10 @@ static void plan_lists(BatchPlan &p)
         }
     c.crc_n = op - c.crc_off;
   }
+  // the digest units' list: longest range first
+  p.md5_off = op;
+  for (size_t i = n_sel - p.n_md5; i < n_sel; i++) order[op++] = (uint32_t) i;
+  std::stable_sort(order.begin() + p.md5_off, order.begin() + op, [&](uint32_t x, uint32_t y) { return local[x].out_len > local[y].out_len; });
 }
 
 // `sel` lists the unit indices of the batch (NULL = all n_sel units).  to_host: the outputs go back to the caller's host buffer;
@@ -265,8 +290,77 @@ static int plan_batch(mspack_hip_unit *units, const uint32_t *sel, size_t n_sel,
   const uint64_t in_lo = p.in_lo, out_lo = p.out_lo;
   for (size_t i = 0; i < n_sel; i++) {
     { uint64_t tl, th; if (unit_side_table(local[i], tl, th)) local[i].in_chunk -= (uint32_t)(in_lo >> 2); }      // in_lo is a multiple of 16
+    if (local[i].kind == MSPACK_HIP_KIND_MD5) { if (local[i].out_len) local[i].out_off -= out_lo; else local[i].out_off = 0; continue; }
     local[i].in_off -= in_lo;
     if (local[i].kind != MSPACK_HIP_KIND_XORSUM) local[i].out_off -= out_lo;
   }
   return 0;
+}
+
+// mspack_hip_decode_batch_multi's cut: which units go to which of n_shards shards (indices into units[], arena order within a shard).
+// false: the batch cannot be cut (digest units over outputs that interleave) -- one device takes it whole.
+static bool plan_shards(const mspack_hip_unit *units, size_t n_units, int n_shards, std::vector<std::vector<uint32_t>> &shard, bool &ascending)
+{
+  // static sharding, no inter-device traffic: units in arena order are cut into n_shards CONTIGUOUS ranges of
+  // about equal compressed size, so that every device stages one contiguous span of each arena
+  std::vector<uint32_t> idx(n_units);
+  for (size_t i = 0; i < n_units; i++) idx[i] = (uint32_t) i;
+  std::stable_sort(idx.begin(), idx.end(), [&](uint32_t a, uint32_t b) { return units[a].in_off < units[b].in_off; });
+  uint64_t total = 0;
+  for (size_t i = 0; i < n_units; i++) if (units[i].kind != MSPACK_HIP_KIND_MD5) total += (uint64_t) units[i].in_len + (units[i].out_len >> 2) + 256u;
+  // every shard copies its whole output span back with one copy -- valid only if the spans do not interleave, i.e. if
+  // the outputs ascend with the inputs over the WHOLE batch; otherwise the shards copy back unit by unit
+  ascending = true;
+  {
+    uint64_t prev_hi = 0;
+    for (size_t i = 0; i < n_units && ascending; i++) {
+      const mspack_hip_unit &u = units[idx[i]];
+      if (u.kind == MSPACK_HIP_KIND_XORSUM || u.kind == MSPACK_HIP_KIND_MD5) continue;       // (no output)
+      const uint64_t lo = u.out_off - std::min<uint64_t>(u.out_off, unit_below(u)), hi = u.out_off + u.out_len + unit_above(u);
+      if (lo < prev_hi) ascending = false;
+      prev_hi = std::max(prev_hi, hi);
+    }
+  }
+  // Digest units: a shard's device holds only what the shard's units stored, so no cut may fall inside a digest range and a
+  // digest unit goes to the shard that holds its range.  With outputs that ascend a range covers the regions of CONSECUTIVE units
+  // (positions [first, last] of idx): the cuts behind first .. last - 1 are barred; the cuts that stay are taken as before -- at
+  // worst there are fewer shards.  (Outputs that interleave: no cut says where a range lies -- one shard.)
+  std::vector<uint32_t> md5s;
+  for (size_t i = 0; i < n_units; i++) if (units[i].kind == MSPACK_HIP_KIND_MD5) md5s.push_back((uint32_t) i);
+  if (!md5s.empty() && !ascending) return false;
+  std::vector<uint8_t> barred(n_units, 0);
+  std::vector<size_t> md5_first(md5s.size(), (size_t) -1);
+  if (!md5s.empty()) {
+    struct Region { uint64_t lo, hi; size_t pos; };
+    std::vector<Region> dec;                                // the units that own output, ascending and disjoint
+    for (size_t i = 0; i < n_units; i++) {
+      const mspack_hip_unit &u = units[idx[i]];
+      if (u.kind == MSPACK_HIP_KIND_XORSUM || u.kind == MSPACK_HIP_KIND_MD5) continue;
+      dec.push_back(Region{ u.out_off - std::min<uint64_t>(u.out_off, unit_below(u)), u.out_off + u.out_len + unit_above(u), i });
+    }
+    for (size_t m = 0; m < md5s.size(); m++) {
+      const mspack_hip_unit &d = units[md5s[m]];
+      const uint64_t dlo = d.out_off, dhi = d.out_off + d.out_len;
+      // the first region that ends behind dlo, the first that begins at or behind dhi: what lies between them meets the range
+      const size_t a = (size_t)(std::upper_bound(dec.begin(), dec.end(), dlo, [](uint64_t v, const Region &r) { return v < r.hi; }) - dec.begin());
+      const size_t b = (size_t)(std::lower_bound(dec.begin(), dec.end(), dhi, [](const Region &r, uint64_t v) { return r.lo < v; }) - dec.begin());
+      if (d.out_len == 0 || a >= b) continue;
+      md5_first[m] = dec[a].pos;
+      for (size_t i = dec[a].pos; i < dec[b - 1].pos; i++) barred[i] = 1;
+    }
+  }
+  shard.assign((size_t) n_shards, std::vector<uint32_t>());
+  std::vector<int> shard_of(n_units, 0);                    // by position in idx
+  {
+    uint64_t acc = 0; int s = 0;
+    for (size_t i = 0; i < n_units; i++) {
+      if (units[idx[i]].kind == MSPACK_HIP_KIND_MD5) continue;
+      shard[s].push_back(idx[i]);
+      shard_of[i] = s;
+      acc += (uint64_t) units[idx[i]].in_len + (units[idx[i]].out_len >> 2) + 256u;
+      if (s + 1 < n_shards && acc * n_shards >= total * (uint64_t)(s + 1) && !barred[i]) s++;
+    }
+  }
+  for (size_t m = 0; m < md5s.size(); m++) shard[md5_first[m] == (size_t) -1 ? 0 : shard_of[md5_first[m]]].push_back(md5s[m]);
+  return true;
 }

@@ -1,5 +1,5 @@
 // launch.hpp -- the launch layer and the device-resident C ABI: the thread's error text, launch<> (a kernel launch whose status is
-// returned), the launch-level environment knobs, launch_kind (one codec's launches over a compact unit list), launch_crc32, the
+// returned), the launch-level environment knobs, launch_kind (one codec's launches over a compact unit list), launch_crc32, launch_md5, the
 // analysis builds' debug exports, version / features / device functions, mspack_hip_decode_batch_device and _time_batch_device.
 #pragma once
 #include <mutex>
@@ -198,6 +198,17 @@ static hipError_t launch_crc32(const mspack_hip_unit *d_units, const uint32_t *d
   LK(launch(mspack_crc32, dim3((unsigned)(n * segs_y)), dim3(64), st, d_units, d_order, (u32) n, segs_y, (const u8 *) d_out, d_results));
   return hipSuccess;
 }
+// the MD5 pass over the digest units order[0..n) (or, order == NULL, over every unit: lanes of other kinds leave): one lane each
+static hipError_t launch_md5(const mspack_hip_unit *d_units, const uint32_t *d_order, size_t n, const void *d_out, size_t out_bytes,
+                             mspack_hip_result *d_results, hipStream_t st)
+{
+  if (n == 0) return hipSuccess;
+#ifdef MSPACK_HOST_CHECK      /* tests/hostcheck runs no kernel and its stand-in for a launch computes no digest */
+  return hipErrorInvalidValue;
+#endif
+  LK(launch(mspack_md5, dim3((unsigned)((n + 63) / 64)), dim3(64), st, d_units, d_order, (u32) n, (const u8 *) d_out, (u64) out_bytes, d_results));
+  return hipSuccess;
+}
 #undef LK
 
 extern "C" {
@@ -237,7 +248,7 @@ int mspack_hip_debug_pipe_phases(unsigned long long *out32) {
 #endif
 const char *mspack_hip_version(void) { return "mspack-hip 0.4 (gfx950; LZX/LZX-DELTA/Quantum/MSZIP batch decode)"; }
 const char *mspack_hip_last_error(void) { return g_err; }
-unsigned mspack_hip_features(void) { return MSPACK_HIP_FEAT_CRC32; }
+unsigned mspack_hip_features(void) { return MSPACK_HIP_FEAT_CRC32 | MSPACK_HIP_FEAT_MD5; }
 
 int mspack_hip_device_count(void) {
   int n = 0;
@@ -257,7 +268,7 @@ int mspack_hip_decode_batch_device(const mspack_hip_unit *d_units, const uint32_
 {
   (void) in_bytes;
   if (n_units == 0) return 0;
-  if ((kind_mask & 0xFEu) == 0) kind_mask |= 0xFEu;     // bit k = units of kind k may be present
+  if ((kind_mask & 0x1FEu) == 0) kind_mask |= 0xFEu;    // bit k = units of kind k may be present; none = every codec (and no digest units)
   // the caller's unit table lives on the device, so the kinds cannot be compacted here: every codec in the
   // mask gets the whole grid and blocks of other kinds leave at once.  Callers with mixed batches pass one
   // order list per codec and a one-bit mask (what the host-buffer entry points below do).
@@ -268,6 +279,9 @@ int mspack_hip_decode_batch_device(const mspack_hip_unit *d_units, const uint32_
   // (the flags are on the device too: the digest pass is launched only when the caller says some unit may carry MSPACK_HIP_UF_CRC32)
   if (kind_mask & MSPACK_HIP_MASK_CRC32)
     CK(launch_crc32(d_units, d_order, n_units, std::min<uint64_t>(out_bytes, 0xFFFFFFFFu), d_out, d_results, (hipStream_t) stream));
+  // the MD5 pass, behind everything that stores into the arena: only when the caller says digest units may be present
+  if (kind_mask & (1u << MSPACK_HIP_KIND_MD5))
+    CK(launch_md5(d_units, d_order, n_units, d_out, out_bytes, d_results, (hipStream_t) stream));
   return 0;
 }
 

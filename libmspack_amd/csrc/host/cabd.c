@@ -24,6 +24,7 @@
 #include <stdlib.h>
 #include <stdio.h>
 #include "host_common.h"
+#include "md5.h"
 
 #define CAB_BLOCKMAX   32768u
 #define CAB_INPUTMAX   (CAB_BLOCKMAX + 6144u)
@@ -82,7 +83,12 @@ struct folder_p {
    * again; folder_settle() waits for the unit and takes its result over */
   struct cab_batch *job;
   size_t job_k;
+  /* MSCABD_PARAM_HIP_MD5: the digests the folder's batch took of its files (mspack_hip.h: MSPACK_HIP_KIND_MD5), in list order;
+   * md5_hint: where the last lookup ended (files are mostly asked for in list order) */
+  struct file_md5 *md5s;
+  unsigned int n_md5s, md5_hint;
 };
+struct file_md5 { unsigned int offset, length; unsigned char d[16]; };
 struct cab_p {
   struct mscabd_cabinet base;
   int block_resv;
@@ -114,7 +120,9 @@ struct cabd_p {
   struct mspack_system *system;
   int error, read_error;
   int searchbuf_size, fix_mszip, buf_size, salvage;
-  int devices, cache_mb;
+  int devices, cache_mb, hip_md5;
+  struct mspack_md5 *sink;            /* mspack_cabd_md5 is running: what extract() would write goes here instead of a file */
+  const unsigned char *sink_kept;     /* ... or the call's bytes were exactly a file whose digest the batch has taken: that one */
   unsigned int list_stamp;            /* mspack_cabd_prefetch: one number per call, to tell a folder list that is named twice */
   /* stored (uncompressed) folders need no codec and are streamed exactly like the reference does it,
    * including what a later extract() sees after a failed one (cabd.c:1283-1345, 1530-1541) */
@@ -184,6 +192,7 @@ static void free_folder_cache(struct mspack_system *sys, struct folder_p *f) {
   sys->free(f->rep); f->rep = NULL; f->rep_n = 0;
   sys->free(f->rep_ck); f->rep_ck = NULL; f->ck_n = 0;
   sys->free(f->marks); f->marks = NULL; f->n_marks = 0; f->mark_log = NULL;
+  sys->free(f->md5s); f->md5s = NULL; f->n_md5s = 0; f->md5_hint = 0;
 }
 
 /* ---- headers (reference cabd.c:317-628) ------------------------------------------------------------- */
@@ -692,12 +701,14 @@ static int stored_read(struct cabd_p *self, unsigned char *buf, int bytes) {
 }
 
 /* produce `bytes` more bytes of the folder; out == NULL skips (the offset still advances) */
+static struct mspack_file *const MD5_SINK = (struct mspack_file *) &MD5_SINK;      /* (mspack_cabd_md5: "the output file", never handed to the system) */
 static int stored_run(struct cabd_p *self, unsigned int bytes, struct mspack_file *out, unsigned char *buf) {
   while (bytes > 0) {
     int run = (bytes > (unsigned int) self->buf_size) ? self->buf_size : (int) bytes;
     if (stored_read(self, buf, run) != run) return MSPACK_ERR_READ;
     self->st_offset += (unsigned int) run;
-    if (out && self->system->write(out, buf, run) != run) return MSPACK_ERR_WRITE;
+    if (out && self->sink) mspack_md5_update(self->sink, buf, (size_t) run);
+    else if (out && self->system->write(out, buf, run) != run) return MSPACK_ERR_WRITE;
     bytes -= (unsigned int) run;
   }
   return MSPACK_ERR_OK;
@@ -716,7 +727,8 @@ static int stored_extract(struct cabd_p *self, struct folder_p *fol, struct msca
     self->st_active = 1; self->st_offset = 0;
     self->read_error = MSPACK_ERR_OK;                     /* lasts for the lifetime of a decompressor */
   }
-  if (!(fh = sys->open(sys, filename, MSPACK_SYS_OPEN_WRITE))) return self->error = MSPACK_ERR_OPEN;
+  if (self->sink) fh = MD5_SINK;
+  else if (!(fh = sys->open(sys, filename, MSPACK_SYS_OPEN_WRITE))) return self->error = MSPACK_ERR_OPEN;
   self->error = MSPACK_ERR_OK;
   if (filelen) {
     if (!(buf = (unsigned char *) sys->alloc(sys, (size_t) self->buf_size))) self->error = MSPACK_ERR_NOMEMORY;
@@ -731,7 +743,7 @@ static int stored_extract(struct cabd_p *self, struct folder_p *fol, struct msca
       sys->free(buf);
     }
   }
-  sys->close(fh);
+  if (fh != MD5_SINK) sys->close(fh);
   return self->error;
 }
 
@@ -766,7 +778,35 @@ struct gathered {
   int frames_ok;
   size_t marks_off; unsigned int n_marks;       /* Quantum: the folder's request boundaries as a table in the arena (gather_marks) */
   unsigned int *marks;
+  size_t md_lo, md_n;                           /* MSCABD_PARAM_HIP_MD5: the folder's files' digest units, counted from the batch's first */
 };
+
+/* MSCABD_PARAM_HIP_MD5: which files get a digest unit.  The device hashes one range per LANE (MD5 is one chain per message), so
+ * one lane is much slower than a host core and the pass takes as long as its longest range; the host hashes everything at its
+ * one-core rate.  A file longer than ratio x (all digest-range bytes of the batch), ratio = lane rate / host rate, would hold the
+ * batch longer than the host takes for everything: it gets no unit and is hashed on the host.  The compiled default comes from the
+ * two rates measured on an MI355X box -- one lane 67 MB/s, this file's MD5 on one core 637 MB/s, three runs: 0.1051, 0.1052, 0.1055
+ * (profiles/md5_digest.txt) --; MSPACK_HIP_MD5_RATIO overrides it (read once;
+ * 0: no file gets a unit). */
+#define MD5_RATIO_DEFAULT 0.10
+extern unsigned mspack_hip_features(void) __attribute__((weak));
+static double md5_ratio(void)
+{
+  /* (read once, in parts per million; plain C has no dynamic initialiser for a static: the first callers all compute the same
+   * value, and it is published and read with atomic accesses, so two decompressors on two threads do not race) */
+  static long long ppm = -1;
+  long long v = __atomic_load_n(&ppm, __ATOMIC_RELAXED);
+  if (v < 0) {
+    const char *e = getenv("MSPACK_HIP_MD5_RATIO");
+    const double r = e ? atof(e) : MD5_RATIO_DEFAULT;
+    v = r <= 0.0 ? 0 : (r >= 1e6 ? 1000000000000ll : (long long)(r * 1e6 + 0.5));
+    __atomic_store_n(&ppm, v, __ATOMIC_RELAXED);
+  }
+  return (double) v * 1e-6;
+}
+/* diagnostics (mspack.h: mspack_cabd_md5_counts): successful md5() calls answered from a digest the batch took on the device / hashed
+ * on the host, over all decompressors of the process */
+static unsigned long long g_md5_counts[2];
 
 /* The request boundaries a Quantum folder's files imply -- cabd_extract asks its codec for the bytes in front of a file, then for
  * the file (cabd.c:1195-1218): requests end where files begin and where they end.  Ascending, without duplicates, inside
@@ -972,6 +1012,19 @@ static void batch_take_folder(struct cab_batch *B, size_t k)
       fp->total += res[k].in_next; fp->good_len = fp->total; fp->written = fp->total;
     }
     sys->free(fp->marks); fp->marks = NULL; fp->n_marks = 0; fp->mark_log = NULL;
+    sys->free(fp->md5s); fp->md5s = NULL; fp->n_md5s = 0; fp->md5_hint = 0;
+    if (gs[k].md_n && (fp->md5s = (struct file_md5 *) sys->alloc(sys, gs[k].md_n * sizeof(*fp->md5s)))) {
+      /* the digests the batch took of the folder's files: kept with the folder */
+      const size_t m0 = B->n + B->ck.n + gs[k].md_lo;
+      size_t j;
+      for (j = 0; j < gs[k].md_n; j++) {
+        if (res[m0 + j].err != MSPACK_ERR_OK) continue;
+        fp->md5s[fp->n_md5s].offset = (unsigned int)(units[m0 + j].out_off - units[k].out_off);
+        fp->md5s[fp->n_md5s].length = units[m0 + j].out_len;
+        memcpy(fp->md5s[fp->n_md5s].d, &res[m0 + j].out_len, 16);
+        fp->n_md5s++;
+      }
+    }
     if (units[k].flags & MSPACK_HIP_UF_QTM_MARKS) {
       fp->marks = gs[k].marks; fp->n_marks = gs[k].n_marks; gs[k].marks = NULL;
       fp->mark_log = out_arena + units[k].out_off + (((size_t) gs[k].total + 15) & ~(size_t) 15);
@@ -1010,6 +1063,8 @@ static int decode_cabinets(struct cabd_p *self, struct cab_p **cabs, size_t n_ca
   size_t n = 0, k, c, out_bytes = 0, budget = (size_t) self->cache_mb << 20, nu;
   size_t kept = used;                                   /* what the folders this call decodes have taken of the budget */
   int err = MSPACK_ERR_OK, rc, again = 0;
+  const int dev_md5 = self->hip_md5 && mspack_hip_features && (mspack_hip_features() & MSPACK_HIP_FEAT_MD5) && md5_ratio() > 0.0;
+  size_t md_cap = 0, nmd = 0;                           /* digest units: at most one per file of the gathered folders; those made */
 
   size_t n_qtm_files = 0;                               /* files in Quantum folders: two marks each at most (gather_marks) */
   for (c = 0; c < n_cabs; c++) {
@@ -1051,21 +1106,23 @@ static int decode_cabinets(struct cabd_p *self, struct cab_p **cabs, size_t n_ca
     gs[n].n_marks = 0; gs[n].marks = NULL; gs[n].marks_off = 0;
     if ((fo->comp_type & 0x0F) == MSCAB_COMP_QUANTUM) gather_marks(sys, fp->data.cab, &gs[n], &A);
     used += est;
+    gs[n].md_lo = 0; gs[n].md_n = 0;
+    if (dev_md5) md_cap += fp->file_count;
     n++;
   }
   if (!err && !arena_room(sys, &A, 64)) err = MSPACK_ERR_NOMEMORY;
   /* (a list that could not grow: the parts it holds are still verified with the batch, the others were verified while they were read) */
   nu = n + ck.n;
   if (!err) {
-    units = (mspack_hip_unit *) sys->alloc(sys, (nu ? nu : 1) * sizeof(*units));
-    res = (mspack_hip_result *) sys->alloc(sys, (nu ? nu : 1) * sizeof(*res));
+    units = (mspack_hip_unit *) sys->alloc(sys, (nu + md_cap ? nu + md_cap : 1) * sizeof(*units));
+    res = (mspack_hip_result *) sys->alloc(sys, (nu + md_cap ? nu + md_cap : 1) * sizeof(*res));
     if (!units || !res) err = MSPACK_ERR_NOMEMORY;
   }
   if (err) { for (k = 0; k < n; k++) { sys->free(gs[k].boff); sys->free(gs[k].marks); } sys->free(gs); sys->free(units); sys->free(res); sys->free(ck.p); mspack_arena_free(sys, A.p); return err; }
   memset(A.p + A.len, 0, 64);
 
   /* the units: where gather_folder put their input, one stretch of the output arena each */
-  memset(units, 0, nu * sizeof(*units));
+  memset(units, 0, (nu + md_cap) * sizeof(*units));
   for (k = 0; k < ck.n; k++) {                             /* the block parts' checksums (mspack_hip.h: MSPACK_HIP_KIND_XORSUM) */
     units[n + k].kind = MSPACK_HIP_KIND_XORSUM;
     units[n + k].in_off = ck.p[k].off; units[n + k].in_len = ck.p[k].len;
@@ -1094,6 +1151,32 @@ static int decode_cabinets(struct cabd_p *self, struct cab_p **cabs, size_t n_ca
       if (4 * (size_t) gs[k].n_marks + 16 > 32768) out_bytes += (4 * (size_t) gs[k].n_marks + 15) & ~(size_t) 15;
     }
   }
+  if (md_cap) {
+    /* one digest unit per file that lies inside what its folder's blocks hold, beside the marks gather_marks collected; the
+     * long ones are left to the host (md5_ratio) */
+    double sum = 0.0;
+    int pass;
+    for (pass = 0; pass < 2; pass++)
+      for (k = 0; k < n; k++) {
+        struct folder_p *fp = gs[k].fol;
+        struct mscabd_file *f;
+        size_t i = 0;
+        if (units[k].kind == 0) continue;
+        if (pass) gs[k].md_lo = nmd;
+        for (f = fp->first_file; f && i < fp->file_count; f = f->next) {
+          if ((struct folder_p *) f->folder != fp) continue;
+          i++;
+          if (!f->length || f->offset > gs[k].total || f->length > gs[k].total - f->offset) continue;
+          if (!pass) { sum += (double) f->length; continue; }
+          if ((double) f->length > md5_ratio() * sum) continue;
+          units[nu + nmd].kind = MSPACK_HIP_KIND_MD5;
+          units[nu + nmd].out_off = units[k].out_off + f->offset; units[nu + nmd].out_len = f->length;
+          nmd++;
+        }
+        if (pass) gs[k].md_n = nmd - gs[k].md_lo;
+      }
+    nu += nmd;
+  }
   out_arena = (unsigned char *) mspack_arena_alloc(sys, out_bytes + 64);
   if (!out_arena) err = MSPACK_ERR_NOMEMORY;
   else {
@@ -1109,7 +1192,8 @@ static int decode_cabinets(struct cabd_p *self, struct cab_p **cabs, size_t n_ca
        * the caller writes the file while the other folders are decoded and copied back, and every later extract() waits for its
        * own folder only (folder_settle).  Everything the batch reads and writes belongs to it until then: struct cab_batch. */
       struct cab_batch *J = NULL;
-      if (n >= 2 && self->devices <= 1 && (J = (struct cab_batch *) sys->alloc(sys, sizeof(*J)))) {
+      /* (digest units are through when the whole batch is: a batch that carries some is waited for here) */
+      if (n >= 2 && self->devices <= 1 && !nmd && (J = (struct cab_batch *) sys->alloc(sys, sizeof(*J)))) {
         *J = B; J->pinned = pinned;
         if ((J->store = (struct out_store *) sys->alloc(sys, sizeof(*J->store)))) {
           J->store->base = out_arena; J->store->refs = 1;             /* (the batch's own hold on the arena) */
@@ -1244,6 +1328,17 @@ static unsigned int qtm_mark(const struct folder_p *fp, unsigned int pos)
   return (lo < fp->n_marks && fp->marks[lo] == pos) ? rd_le32(fp->mark_log + 4 * (size_t) lo) : 0;
 }
 
+/* the digest the folder's batch took of the file at [offset, offset + length), or NULL */
+static const unsigned char *kept_md5(struct folder_p *fp, unsigned int offset, unsigned int length)
+{
+  unsigned int i, at = fp->md5_hint;
+  for (i = 0; i < fp->n_md5s; i++, at++) {
+    if (at >= fp->n_md5s) at = 0;
+    if (fp->md5s[at].offset == offset && fp->md5s[at].length == length) { fp->md5_hint = at + 1; return fp->md5s[at].d; }
+  }
+  return NULL;
+}
+
 /* can the reference produce bytes [0, end) of this folder, and with which error if not? */
 static int folder_status(struct folder_p *fp, unsigned int end, int read_error, int *failed)
 {
@@ -1356,7 +1451,8 @@ static int cabd_extract(struct mscab_decompressor *base, struct mscabd_file *fil
     self->live_folder = fol; self->live_offset = 0; self->live_failed = 0; self->live_err = MSPACK_ERR_OK;
   }
 
-  if (!(fh = sys->open(sys, filename, MSPACK_SYS_OPEN_WRITE))) return self->error = MSPACK_ERR_OPEN;
+  if (self->sink) fh = MD5_SINK;
+  else if (!(fh = sys->open(sys, filename, MSPACK_SYS_OPEN_WRITE))) return self->error = MSPACK_ERR_OPEN;
   self->error = MSPACK_ERR_OK;
   /* What the codec would have said on the way: mszipd in repair mode reports every block it repairs when it decodes it
    * (mszipd.c:420-433), i.e. when the first byte of that block is asked for -- by this file, or by the skip to its offset.
@@ -1417,7 +1513,12 @@ static int cabd_extract(struct mscab_decompressor *base, struct mscabd_file *fil
           if (have > filelen) have = filelen;
           wrote_to = file->offset + have;
         }
-        if (write_slice(sys, fh, fol->dec + file->offset, have) != MSPACK_ERR_OK) err = MSPACK_ERR_WRITE;
+        if (self->sink) {
+          /* (mspack_cabd_md5: the whole file, good -- the digest the batch took of it if it did; else these bytes are hashed) */
+          if (!failed && have == filelen && (self->sink_kept = kept_md5(fol, file->offset, filelen)) != NULL) ;
+          else mspack_md5_update(self->sink, fol->dec + file->offset, have);
+        }
+        else if (write_slice(sys, fh, fol->dec + file->offset, have) != MSPACK_ERR_OK) err = MSPACK_ERR_WRITE;
       }
     }
     self->error = err;
@@ -1429,8 +1530,39 @@ static int cabd_extract(struct mscab_decompressor *base, struct mscabd_file *fil
     }
     else self->live_offset = file->offset + filelen;
   }
-  sys->close(fh);
+  if (fh != MD5_SINK) sys->close(fh);
   return self->error;
+}
+
+/* mspack.h: extract() with the writes replaced by a hash */
+int mspack_cabd_md5(struct mscab_decompressor *base, struct mscabd_file *file, unsigned char digest[16])
+{
+  struct cabd_p *self = (struct cabd_p *) base;
+  struct mspack_md5 m;
+  int err;
+  if (digest) memset(digest, 0, 16);
+  if (!self) return MSPACK_ERR_ARGS;
+  if (!file || !digest) return self->error = MSPACK_ERR_ARGS;
+  mspack_md5_init(&m);
+  self->sink = &m; self->sink_kept = NULL;
+  err = cabd_extract(base, file, NULL);
+  self->sink = NULL;
+  if (err == MSPACK_ERR_OK) {
+    if (self->sink_kept) memcpy(digest, self->sink_kept, 16);
+    else mspack_md5_final(&m, digest);
+    __atomic_fetch_add(&g_md5_counts[self->sink_kept ? 0 : 1], 1ull, __ATOMIC_RELAXED);
+  }
+  self->sink_kept = NULL;
+  return err;
+}
+
+void mspack_cabd_md5_counts(unsigned long long counts[2], int reset)
+{
+  int i;
+  for (i = 0; i < 2; i++) {
+    if (counts) counts[i] = __atomic_load_n(&g_md5_counts[i], __ATOMIC_RELAXED);
+    if (reset) __atomic_store_n(&g_md5_counts[i], 0ull, __ATOMIC_RELAXED);
+  }
 }
 
 static int cabd_param(struct mscab_decompressor *base, int param, int value)
@@ -1444,6 +1576,7 @@ static int cabd_param(struct mscab_decompressor *base, int param, int value)
   case MSCABD_PARAM_SALVAGE:   self->salvage = value; break;
   case MSCABD_PARAM_HIP_DEVICES:  if (value < 1) return MSPACK_ERR_ARGS; self->devices = value; break;
   case MSCABD_PARAM_HIP_CACHE_MB: if (value < 1) return MSPACK_ERR_ARGS; self->cache_mb = value; break;
+  case MSCABD_PARAM_HIP_MD5:      if (value != 0 && value != 1) return MSPACK_ERR_ARGS; self->hip_md5 = value; break;
   default: return MSPACK_ERR_ARGS;
   }
   return MSPACK_ERR_OK;
@@ -1504,7 +1637,7 @@ struct mscab_decompressor *mspack_create_cab_decompressor(struct mspack_system *
   self->system = sys;
   self->error = MSPACK_ERR_OK; self->read_error = MSPACK_ERR_OK;
   self->searchbuf_size = 32768; self->fix_mszip = 0; self->buf_size = 4096; self->salvage = 0;
-  self->devices = 1; self->cache_mb = 2048; self->list_stamp = 0;
+  self->devices = 1; self->cache_mb = 2048; self->list_stamp = 0; self->hip_md5 = 0; self->sink = NULL; self->sink_kept = NULL;
   memset(&self->st, 0, sizeof(self->st)); self->st_offset = 0; self->st_active = 0; self->last_folder = NULL;
   self->msg_folder = NULL; self->msg_offset = 0; self->msg_next = 0; self->msg_next_ck = 0;
   self->live_folder = NULL; self->live_offset = 0; self->live_failed = 0; self->live_err = MSPACK_ERR_OK;
