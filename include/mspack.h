@@ -168,7 +168,14 @@ struct mscabd_file {
 /* extensions of this library (ids >= 100; the reference answers MSPACK_ERR_ARGS to them) */
 #define MSCABD_PARAM_HIP_DEVICES  (100)  /* GPUs to shard a batch over (default 1)               */
 #define MSCABD_PARAM_HIP_CACHE_MB (101)  /* decoded-folder cache budget in MiB (default 2048)    */
-#define MSCABD_PARAM_HIP_MD5      (102)  /* 1: batches carry one MD5 digest unit per file, for mspack_cabd_md5() (default 0) */
+#define MSCABD_PARAM_HIP_MD5      (102)  /* 1: batches carry one MD5 digest unit per file, for mspack_cabd_md5() (default 0); bit 1
+                                            (MSPACK_DIGEST_MD5) of MSCABD_PARAM_HIP_DIGESTS: either one reads and writes it */
+#define MSCABD_PARAM_HIP_DIGESTS  (103)  /* a mask of MSPACK_DIGEST_*: the algorithms the batches carry digest units for, per file, for
+                                            mspack_cabd_digest() (0 to 7, default 0; other values: MSPACK_ERR_ARGS) */
+/* digest algorithms (mspack_cabd_digest, MSCABD_PARAM_HIP_DIGESTS) */
+#define MSPACK_DIGEST_MD5     (1)        /* RFC 1321, 16 bytes */
+#define MSPACK_DIGEST_SHA1    (2)        /* FIPS 180-4, 20 bytes */
+#define MSPACK_DIGEST_SHA256  (4)        /* FIPS 180-4, 32 bytes */
 
 struct mscab_decompressor {
   struct mscabd_cabinet * (*open) (struct mscab_decompressor *self, const char *filename);
@@ -225,6 +232,29 @@ extern int mspack_cabd_md5(struct mscab_decompressor *self, struct mscabd_file *
 /* diagnostics: how many successful mspack_cabd_md5() calls of this process were answered from a digest taken on the device
  * (counts[0]) and how many were hashed on the host (counts[1]); counts may be NULL; reset != 0 clears them after reading. */
 extern void mspack_cabd_md5_counts(unsigned long long counts[2], int reset);
+
+/* A digest of a file, by algorithm: mspack_cabd_md5() for MD5, SHA-1 and SHA-256 -- what package verifiers of cabinets check today
+ * (Authenticode catalogs, update manifests, driver packages).  Everything said of mspack_cabd_md5() holds: the return codes, what the
+ * call counts as for the decompressor's sticky state, the lines said through sys->message, no output file, no sys->write.
+ *   alg         MSPACK_DIGEST_MD5, _SHA1 or _SHA256 -- one of them; anything else: MSPACK_ERR_ARGS
+ *   digest      with MSPACK_ERR_OK the algorithm's 16, 20 or 32 bytes in the standard's byte order; with any other code that many
+ *               zero bytes (if they fit)
+ *   digest_cap  the room at digest; below the algorithm's length: MSPACK_ERR_ARGS, nothing written
+ * With the algorithm's bit set in MSCABD_PARAM_HIP_DIGESTS (before the batch is built, as for MSCABD_PARAM_HIP_MD5) and a batch provider
+ * that reports the algorithm's feature bit (MSPACK_HIP_FEAT_MD5 / _SHA1 / _SHA256), the batch carries one digest unit per file and
+ * algorithm -- for SHA-1 and SHA-256 with the unit that takes the digest's bytes beyond sixteen behind it (mspack_hip.h:
+ * MSPACK_HIP_KIND_DIGEST_MORE) -- and the digests are kept with the folders.  Everything else is hashed on the host by plain-C
+ * SHA-1 / SHA-256 with identical results: the bit off, stored folders, failing or partial files, a provider without the feature bit
+ * (or without mspack_hip_features() at all), and files too long for one lane of the device -- per algorithm, by that algorithm's
+ * own ratio (MSPACK_HIP_SHA1_RATIO, MSPACK_HIP_SHA256_RATIO beside MSPACK_HIP_MD5_RATIO).
+ * As with MSCABD_PARAM_HIP_MD5, a batch that carries digest units of any algorithm does not run as a job: it is waited for as a
+ * whole.  Leave the bits off for callers that extract. */
+extern int mspack_cabd_digest(struct mscab_decompressor *self, struct mscabd_file *file, int alg, unsigned char *digest, size_t digest_cap);
+/* mspack_cabd_md5_counts() per algorithm (an unknown alg: zeros) */
+extern void mspack_cabd_digest_counts(int alg, unsigned long long counts[2], int reset);
+/* the value set_param() last stored for a parameter (the defaults before that); MSCABD_PARAM_HIP_MD5 answers bit 1 of
+ * MSCABD_PARAM_HIP_DIGESTS.  MSPACK_ERR_ARGS for an unknown parameter or a NULL argument. */
+extern int mspack_cabd_get_param(struct mscab_decompressor *self, int param, int *value);
 
 /* ---- CHM ---------------------------------------------------------------------------------------------- */
 struct mschm_decompressor;

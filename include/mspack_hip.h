@@ -62,6 +62,27 @@ extern "C" {
                                        alone) are unspecified there, and so is a digest over them (err is still 0).  One lane per range (MD5 is one chain per message): the device wins
                                        with many ranges at once.  Ask mspack_hip_features() & MSPACK_HIP_FEAT_MD5 first       */
 
+/* Kinds 9 to 15 are not defined (an entry point that meets one answers "unknown kind"); digests other than MD5 are numbered from 16. */
+#define MSPACK_HIP_KIND_SHA1    16   /* a digest unit like MSPACK_HIP_KIND_MD5, every convention of it (the range [out_off, out_off + out_len) of the
+                                       OUTPUT arena behind all decoding, in_len 0, MSPACK_HIP_UF_CRC32 rejected, overlapping ranges,
+                                       the arena only read, which bytes "lie there" per entry point, err 0 and flags 0): the SHA-1
+                                       (FIPS 180-4) of the range, 20 bytes.  A WIDE digest: see MSPACK_HIP_KIND_DIGEST_MORE.  Ask
+                                       mspack_hip_features() & MSPACK_HIP_FEAT_SHA1 first                                        */
+#define MSPACK_HIP_KIND_SHA256  17   /* the same with SHA-256 (FIPS 180-4), 32 bytes; MSPACK_HIP_FEAT_SHA256                          */
+#define MSPACK_HIP_KIND_DIGEST_MORE 18 /* the TAIL of a wide digest.  A result has sixteen bytes to spare, so a SHA-1 / SHA-256 unit
+                                       ("head") at units[i] needs units[i + 1] to be a unit of this kind with in_len == 0 and
+                                       out_len == 0 (in_off, out_off and the flags are ignored).  The digest comes back in the
+                                       standard's byte order (FIPS 180-4: big-endian words): bytes 0 to 15 in out_len, in_used,
+                                       good_len, in_next of results[i] -- memcpy(d, &results[i].out_len, 16) --, the remaining 4
+                                       (SHA-1) or 16 (SHA-256) bytes in results[i + 1] from out_len on -- memcpy(d + 16,
+                                       &results[i + 1].out_len, 4 or 16).  The head's lane writes the tail's result: err 0, flags 0,
+                                       the words it does not use 0; nothing else ever writes it.  A head without its tail (the last
+                                       unit of the table, or followed by a unit of another kind or a tail that names bytes) and a
+                                       tail without a head in front of it are errors: the host entry points refuse the batch before
+                                       anything touches the device (mspack_hip_last_error() says which unit); the device-resident
+                                       entry answers MSPACK_ERR_ARGS in that unit's result and reads nothing.  A head whose range
+                                       leaves out_bytes answers MSPACK_ERR_ARGS as an MD5 unit does (its tail's result is then all 0) */
+
 #define MSPACK_HIP_MASK_FRAME_TABLES 0x80000000u   /* mspack_hip_decode_batch_device(kind_mask): see there */
 #define MSPACK_HIP_MASK_CRC32        0x40000000u   /* mspack_hip_decode_batch_device(kind_mask): units may carry MSPACK_HIP_UF_CRC32 */
 
@@ -185,6 +206,8 @@ const char *mspack_hip_last_error(void);
  * another provider declares the function weak and treats its absence as 0) */
 #define MSPACK_HIP_FEAT_CRC32 1u        /* MSPACK_HIP_UF_CRC32 / MSPACK_HIP_MASK_CRC32 */
 #define MSPACK_HIP_FEAT_MD5   2u        /* MSPACK_HIP_KIND_MD5 */
+#define MSPACK_HIP_FEAT_SHA1   4u       /* MSPACK_HIP_KIND_SHA1 (and MSPACK_HIP_KIND_DIGEST_MORE) */
+#define MSPACK_HIP_FEAT_SHA256 8u       /* MSPACK_HIP_KIND_SHA256 (and MSPACK_HIP_KIND_DIGEST_MORE) */
 unsigned mspack_hip_features(void);
 
 /* ---- device-resident batch decode (the hot path proper) ---------------------------------------
@@ -213,6 +236,9 @@ unsigned mspack_hip_features(void);
  *                bit MSPACK_HIP_KIND_MD5 set = digest units may be present: only then is the MD5 pass launched, behind everything
  *                else on the stream (one more launch; 0 still means "all codecs" and launches no digest pass; a mask of this bit
  *                alone launches the MD5 pass only)
+ *                bit MSPACK_HIP_KIND_SHA1 (16) / MSPACK_HIP_KIND_SHA256 (17) set = heads of that algorithm (with their tails) may
+ *                be present: only then is that algorithm's pass launched, one launch each, behind everything else on the stream
+ *                like the MD5 pass; a mask of digest bits alone launches those passes only
  * MSZIP units need 32768 bytes of slack after out_len in their output region.
  * Units with a frame / block table: the parse wavefronts store literals into the unit's output region (for MSZIP incl. its
  * slack) before the unit is known to decode; the first result.out_len bytes are the decoded data, the rest of the region
@@ -239,11 +265,12 @@ size_t mspack_hip_frame_scratch_bytes(size_t n_frames_total);
  * DMA that need not wait for the other streams; a buffer that cannot be registered is copied the ordinary way (MSPACK_HIP_PIN_OUT=0: always).
  * `units[i].frame_base` is filled in by the call.  Synchronous.  Bytes of the output arena
  * BETWEEN units that lie inside a copied span (alignment padding, the MSZIP slack) are unspecified afterwards.
- * Digest units (MSPACK_HIP_KIND_MD5) are kept out of the chunk cutting; their pass runs once per device, behind the last chunk's
+ * Digest units (MSPACK_HIP_KIND_MD5, _SHA1, _SHA256 and their _DIGEST_MORE tails) are kept out of the chunk cutting; their passes
+ * (one per algorithm) run once per device, behind the last chunk's
  * launches and before the results go back -- over the device's copy of the output arena, which holds what this call's decoding
  * units stored (bytes of a range that no unit of the call wrote are unspecified).  mspack_hip_job_wait_unit() on a digest unit
- * returns when the batch is through.  mspack_hip_decode_batch_multi never cuts its shards inside a digest range (at worst it
- * makes fewer shards); a digest unit goes to the shard that holds its range.
+ * or a tail returns when the batch is through.  mspack_hip_decode_batch_multi never cuts its shards inside a digest range (at worst it
+ * makes fewer shards); a digest unit goes to the shard that holds its range, a tail to its head's shard.
  * Thread-safe; calls that target the same device are serialised. */
 int mspack_hip_decode_batch(mspack_hip_unit *units, size_t n_units, const void *in, size_t in_bytes,
                             void *out, size_t out_bytes, mspack_hip_result *results);

@@ -17,6 +17,9 @@ CORPUS_SO = os.path.join(HERE, "libmspack_corpus.so")
 KIND_MSZIP, KIND_QUANTUM, KIND_LZX, KIND_LZX_DELTA, KIND_LZSS, KIND_KWAJ_LZH = 1, 2, 3, 4, 5, 6
 KIND_XORSUM = 7
 KIND_MD5 = 8                 # a digest unit: the MD5 of out[out_off : out_off + out_len] once the batch's decoding units have stored
+KIND_SHA1, KIND_SHA256 = 16, 17   # wide digest units (20 / 32 bytes): each needs a KIND_DIGEST_MORE unit right behind it in the table
+KIND_DIGEST_MORE = 18            # ... whose result takes the digest's bytes beyond sixteen
+DIGEST_BYTES = {KIND_MD5: 16, KIND_SHA1: 20, KIND_SHA256: 32}
 F_E8_APPLIED, F_LOOKAHEAD_READ, F_INTEL_HEADER, F_BLOCK_OPEN, F_FRAMES_ADOPTED = 1, 2, 4, 16, 32
 UF_MSZIP_REPAIR = 1
 UF_CRC32 = 128               # result.in_used = CRC-32 (OAB flavour: zlib.crc32(out[:out_len]) ^ 0xFFFFFFFF) of the decoded bytes
@@ -24,6 +27,8 @@ MASK_CRC32 = 0x40000000      # decode_batch_device(kind_mask): launch the digest
 FEAT_CRC32 = 1
 FEAT_MD5 = 2
 MASK_MD5 = 1 << KIND_MD5     # decode_batch_device(kind_mask): launch the MD5 pass
+FEAT_SHA1, FEAT_SHA256 = 4, 8
+MASK_SHA1, MASK_SHA256 = 1 << KIND_SHA1, 1 << KIND_SHA256     # ... the SHA-1 / the SHA-256 pass
 ERR_OK, ERR_ARGS, ERR_OPEN, ERR_READ, ERR_WRITE, ERR_SEEK, ERR_NOMEMORY, ERR_SIGNATURE, \
     ERR_DATAFORMAT, ERR_CHECKSUM, ERR_CRUNCH, ERR_DECRUNCH = range(12)
 
@@ -194,6 +199,38 @@ def result_digests(res):
     """the sixteen digest bytes of digest units' results (out_len, in_used, good_len, in_next) -> list of bytes"""
     raw = np.ascontiguousarray(res).view(np.uint8).reshape(len(res), RESULT_DTYPE.itemsize)
     return [raw[i, 8:24].tobytes() for i in range(len(res))]
+
+
+def digest_units(ranges, kinds):
+    """digest units for (out_off, out_len) ranges, kinds[i] = KIND_MD5 / KIND_SHA1 / KIND_SHA256 (or one kind for all): a wide head
+    is followed by its KIND_DIGEST_MORE unit -> (the units, the index of every range's head in them)"""
+    if isinstance(kinds, int):
+        kinds = [kinds] * len(ranges)
+    rows, heads = [], []
+    for (o, n), k in zip(ranges, kinds):
+        heads.append(len(rows))
+        rows.append((k, int(o), int(n)))
+        if k != KIND_MD5:
+            rows.append((KIND_DIGEST_MORE, 0, 0))
+    u = np.zeros(len(rows), dtype=UNIT_DTYPE)
+    u["kind"] = [r[0] for r in rows]
+    u["out_off"] = [r[1] for r in rows]
+    u["out_len"] = [r[2] for r in rows]
+    return u, np.array(heads, dtype=np.int64)
+
+
+def result_wide_digests(res, units):
+    """tail-aware unpacking: the digests of the heads among `units` out of their results `res` (same length) -> list of bytes in
+    table order: sixteen bytes of a head's result, and for a wide head the first 4 / 16 of the sixteen of the next unit's"""
+    raw = np.ascontiguousarray(res).view(np.uint8).reshape(len(res), RESULT_DTYPE.itemsize)
+    out = []
+    for i, k in enumerate(int(x) for x in units["kind"]):
+        if k in DIGEST_BYTES:
+            d = raw[i, 8:24].tobytes()
+            if k != KIND_MD5 and i + 1 < len(res):          # (a head without a tail is an error its result says)
+                d += raw[i + 1, 8:8 + DIGEST_BYTES[k] - 16].tobytes()
+            out.append(d)
+    return out
 
 
 def decode_batch_md5(units, in_arena, out_bytes, ranges, n_devices=1, refs=None):

@@ -103,7 +103,9 @@ MschmDecompressor._fields_ = [
 ]
 
 MSCABD_PARAM_SEARCHBUF, MSCABD_PARAM_FIXMSZIP, MSCABD_PARAM_DECOMPBUF, MSCABD_PARAM_SALVAGE = 0, 1, 2, 3
-MSCABD_PARAM_HIP_DEVICES, MSCABD_PARAM_HIP_CACHE_MB, MSCABD_PARAM_HIP_MD5 = 100, 101, 102
+MSCABD_PARAM_HIP_DEVICES, MSCABD_PARAM_HIP_CACHE_MB, MSCABD_PARAM_HIP_MD5, MSCABD_PARAM_HIP_DIGESTS = 100, 101, 102, 103
+MSPACK_DIGEST_MD5, MSPACK_DIGEST_SHA1, MSPACK_DIGEST_SHA256 = 1, 2, 4
+DIGEST_BYTES = {MSPACK_DIGEST_MD5: 16, MSPACK_DIGEST_SHA1: 20, MSPACK_DIGEST_SHA256: 32}
 MSPACK_ERR_OK, MSPACK_ERR_ARGS = 0, 1
 
 
@@ -124,6 +126,12 @@ def _setup(L=None):
     L.mspack_cabd_md5.argtypes = [_P(MscabDecompressor), _P(MscabdFile), C.c_void_p]
     L.mspack_cabd_md5_counts.restype = None
     L.mspack_cabd_md5_counts.argtypes = [C.c_void_p, C.c_int]
+    L.mspack_cabd_digest.restype = C.c_int
+    L.mspack_cabd_digest.argtypes = [_P(MscabDecompressor), _P(MscabdFile), C.c_int, C.c_void_p, C.c_size_t]
+    L.mspack_cabd_digest_counts.restype = None
+    L.mspack_cabd_digest_counts.argtypes = [C.c_int, C.c_void_p, C.c_int]
+    L.mspack_cabd_get_param.restype = C.c_int
+    L.mspack_cabd_get_param.argtypes = [_P(MscabDecompressor), C.c_int, _P(C.c_int)]
     L.mspack_version.argtypes = [C.c_int]
     L.mspack_sys_selftest_internal.argtypes = [C.c_int]
     return L
@@ -134,6 +142,26 @@ def cabd_md5_counts(reset=False, L=None):
     c = (C.c_ulonglong * 2)()
     _setup(L).mspack_cabd_md5_counts(c, int(reset))
     return int(c[0]), int(c[1])
+
+
+def cabd_digest_counts(alg, reset=False, L=None):
+    """mspack_cabd_digest_counts (mspack.h): successful digest() calls of algorithm alg answered (from a device digest, by the host)"""
+    c = (C.c_ulonglong * 2)()
+    _setup(L).mspack_cabd_digest_counts(int(alg), c, int(reset))
+    return int(c[0]), int(c[1])
+
+
+def _digest(L, d, fptr, alg, cap=None):
+    n = DIGEST_BYTES.get(alg, 32) if cap is None else cap
+    buf = (C.c_ubyte * max(n, 1))()
+    err = L.mspack_cabd_digest(d, fptr, alg, buf, n)
+    return err, bytes(buf)[:n]
+
+
+def _get_param(L, d, param):
+    v = C.c_int(-1)
+    err = L.mspack_cabd_get_param(d, param, C.byref(v))
+    return err, v.value
 
 
 class MspackSystem(C.Structure):
@@ -284,6 +312,16 @@ class Cab:
         err = self.L.mspack_cabd_md5(self.d, self._files[i], d)
         return err, bytes(d)
 
+    def get_param(self, param):
+        """mspack_cabd_get_param (mspack.h) -> (err, value)"""
+        return _get_param(self.L, self.d, param)
+
+    def digest(self, i, alg, cap=None):
+        """mspack_cabd_digest (mspack.h): extract(i) with the writes replaced by a hash of algorithm alg (MSPACK_DIGEST_*) -> (err, the
+        16 / 20 / 32 digest bytes; zeros unless err == 0).  set_param(MSCABD_PARAM_HIP_DIGESTS, mask) before the first call lets the
+        batch take the digests on the device.  cap: the digest_cap handed over instead of the algorithm's length"""
+        return _digest(self.L, self.d, self._files[i], alg, cap)
+
     def close(self):
         if self.cab:
             self.d.contents.close(self.d, self.cab); self.cab = None
@@ -374,6 +412,10 @@ class CabSet:
         d = (C.c_ubyte * 16)()
         err = self.L.mspack_cabd_md5(self.d, fptr, d)
         return err, bytes(d)
+
+    def digest(self, fptr, alg, cap=None):
+        """mspack_cabd_digest (mspack.h) of a file of file_ptrs() -> (err, the digest bytes)"""
+        return _digest(self.L, self.d, fptr, alg, cap)
 
     def extract(self, fptr):
         if self.mem:

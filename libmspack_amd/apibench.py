@@ -34,6 +34,8 @@ def lib():
         L.mspk_api_bench_cabs.argtypes = [C.c_void_p, C.c_void_p, C.c_uint, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(Stats)]
         L.mspk_api_bench_cabs_md5.restype = C.c_int
         L.mspk_api_bench_cabs_md5.argtypes = [C.c_void_p, C.c_void_p, C.c_uint, C.c_int, C.c_int, C.c_void_p, C.c_uint, C.POINTER(Stats)]
+        L.mspk_api_bench_cabs_digest.restype = C.c_int
+        L.mspk_api_bench_cabs_digest.argtypes = [C.c_void_p, C.c_void_p, C.c_uint, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_uint, C.POINTER(Stats)]
         L.mspk_api_cab_run.restype = C.c_int
         L.mspk_api_cab_run.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]
@@ -94,6 +96,22 @@ def run_cabs_md5(images, prefetch, hip_md5, max_files=65536, L=None):
                                    max_files, C.byref(st))
     n = min(st.n_files, max_files)
     return rc, [dg[16 * i:16 * i + 16].tobytes() for i in range(n)], {k: getattr(st, k) for k, _t in Stats._fields_}
+
+
+def run_cabs_digest(images, prefetch, hip_digests, alg, max_files=65536, L=None):
+    """mspack_cabd_digest(alg) of every file of these cabinet images on one decompressor (mspk_api_bench_cabs_digest),
+    MSCABD_PARAM_HIP_DIGESTS = hip_digests.  -> (rc, [digest bytes per file], stats dict)"""
+    L = L or lib()
+    nd = {1: 16, 2: 20, 4: 32}[alg]
+    offs = np.zeros(len(images) + 1, dtype=np.uint64)
+    offs[1:] = np.cumsum([len(i) for i in images])
+    blob = np.frombuffer(b"".join(bytes(i) for i in images), dtype=np.uint8)
+    dg = np.zeros(32 * max_files, dtype=np.uint8)
+    st = Stats()
+    rc = L.mspk_api_bench_cabs_digest(blob.ctypes.data, offs.ctypes.data, len(images), int(bool(prefetch)), int(hip_digests), int(alg),
+                                      dg.ctypes.data, max_files, C.byref(st))
+    n = min(st.n_files, max_files)
+    return rc, [dg[32 * i:32 * i + nd].tobytes() for i in range(n)], {k: getattr(st, k) for k, _t in Stats._fields_}
 
 
 def build_small_cabs(M, n=4096, ub=32768, plain=None):

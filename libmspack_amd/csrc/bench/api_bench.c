@@ -233,8 +233,22 @@ int mspk_api_bench_cabs(const unsigned char *images, const unsigned long long *o
 /* the same cabinets, every file's MD5 through mspack_cabd_md5() instead of extract() (tools/md5_bench.py): hip_md5 = the value of
  * MSCABD_PARAM_HIP_MD5; digests receives sixteen bytes per file, in call order (at most max_files of them).  One image with
  * prefetch == 0 is "one cabinet": its first md5() forms the batch. */
+static int cabs_digest_run(const unsigned char *images, const unsigned long long *offs, unsigned int n_cabs, int prefetch, int param, int value,
+                           int alg, unsigned int stride, unsigned char *digests, unsigned int max_files, mspk_api_stats *st);
 int mspk_api_bench_cabs_md5(const unsigned char *images, const unsigned long long *offs, unsigned int n_cabs, int prefetch, int hip_md5,
                             unsigned char *digests, unsigned int max_files, mspk_api_stats *st)
+{
+  return cabs_digest_run(images, offs, n_cabs, prefetch, MSCABD_PARAM_HIP_MD5, hip_md5, MSPACK_DIGEST_MD5, 16, digests, max_files, st);
+}
+/* ... and through mspack_cabd_digest() with algorithm alg (tools/digest_bench.py): hip_digests = the value of MSCABD_PARAM_HIP_DIGESTS;
+ * digests receives 32 bytes per file (the algorithm's 16, 20 or 32, then zeros) */
+int mspk_api_bench_cabs_digest(const unsigned char *images, const unsigned long long *offs, unsigned int n_cabs, int prefetch, int hip_digests,
+                               int alg, unsigned char *digests, unsigned int max_files, mspk_api_stats *st)
+{
+  return cabs_digest_run(images, offs, n_cabs, prefetch, MSCABD_PARAM_HIP_DIGESTS, hip_digests, alg, 32, digests, max_files, st);
+}
+static int cabs_digest_run(const unsigned char *images, const unsigned long long *offs, unsigned int n_cabs, int prefetch, int param, int value,
+                           int alg, unsigned int stride, unsigned char *digests, unsigned int max_files, mspk_api_stats *st)
 {
   struct mem_sys ms;
   struct mscab_decompressor *d;
@@ -252,7 +266,7 @@ int mspk_api_bench_cabs_md5(const unsigned char *images, const unsigned long lon
   mspack_hip_host_path_stats(NULL, 1);
   t0 = now_s();
   if (!(d = mspack_create_cab_decompressor(&ms.sys))) { free(cabs); free(names); return -1; }
-  if (d->set_param(d, MSCABD_PARAM_HIP_MD5, hip_md5)) rc = -4;
+  if (d->set_param(d, param, value)) rc = -4;
   t1 = now_s();
   for (k = 0; k < n_cabs && !rc; k++) {
     snprintf(names[k], sizeof(names[k]), "c%u", k);
@@ -268,12 +282,12 @@ int mspk_api_bench_cabs_md5(const unsigned char *images, const unsigned long lon
   for (k = 0; k < n_cabs && !rc; k++) {
     struct mscabd_file *f;
     for (f = cabs[k]->files; f; f = f->next) {
-      unsigned char dg[16];
+      unsigned char dg[32];
       const double e0 = now_s();
-      const int err = mspack_cabd_md5(d, f, dg);
+      const int err = (memset(dg, 0, sizeof(dg)), mspack_cabd_digest(d, f, alg, dg, sizeof(dg)));
       if (st->n_files == 0 && !prefetch) st->first_extract_s = now_s() - e0;
       if (err) { if (!st->n_errors) st->first_error = err; st->n_errors++; }
-      if (digests && st->n_files < max_files) memcpy(digests + 16 * (size_t) st->n_files, dg, 16);
+      if (digests && st->n_files < max_files) memcpy(digests + stride * (size_t) st->n_files, dg, stride);
       st->bytes_out += f->length;
       st->n_files++;
     }

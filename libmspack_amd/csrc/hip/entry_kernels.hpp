@@ -586,3 +586,31 @@ void mspack_md5(const mspack_hip_unit *units, const u32 *order, u32 n_units, con
   if (u.kind != MSPACK_HIP_KIND_MD5) return;
   md5_unit(u, out_arena, out_bytes, &results[ui]);
 }
+
+// MSPACK_HIP_KIND_SHA1 / _SHA256 (sha_kernel.hpp): one head per LANE, one kernel per algorithm -- lanes of one wave never run
+// different hash functions --, launched like mspack_md5 behind everything that stores into the output arena.  order[0 .. n_list)
+// names the lanes' units in a table of n_table (a head's tail is units[ui + 1]); lanes whose unit is of another kind leave at once
+// (a tail met here, the device-resident entry only, is checked for its head).
+template <int KIND>
+__device__ __forceinline__ void sha_entry(const mspack_hip_unit *units, const u32 *order, u32 n_list, u32 n_table, const u8 *out_arena, u64 out_bytes,
+                                          mspack_hip_result *results)
+{
+  const u32 j = blockIdx.x * 64u + threadIdx.x;
+  if (j >= n_list) return;
+  const u32 ui = order ? order[j] : j;
+  if (ui >= n_table) return;
+  const mspack_hip_unit u = units[ui];
+  if (u.kind == MSPACK_HIP_KIND_DIGEST_MORE) { sha_tail_unit(units, ui, results); return; }
+  if (u.kind != KIND) return;
+  sha_unit<KIND>(units, ui, n_table, u, out_arena, out_bytes, results);
+}
+__global__ __launch_bounds__(64)
+void mspack_sha1(const mspack_hip_unit *units, const u32 *order, u32 n_list, u32 n_table, const u8 *out_arena, u64 out_bytes, mspack_hip_result *results)
+{
+  sha_entry<MSPACK_HIP_KIND_SHA1>(units, order, n_list, n_table, out_arena, out_bytes, results);
+}
+__global__ __launch_bounds__(64)
+void mspack_sha256(const mspack_hip_unit *units, const u32 *order, u32 n_list, u32 n_table, const u8 *out_arena, u64 out_bytes, mspack_hip_result *results)
+{
+  sha_entry<MSPACK_HIP_KIND_SHA256>(units, order, n_list, n_table, out_arena, out_bytes, results);
+}

@@ -337,12 +337,15 @@ static int issue_chunks(PipeCall &pc, CopyBack &cb)
       TRY(launch_kind(k, pc.d_units, pc.d_order + c.order_off[k], c.order_n[k], d_in, d_out, pc.d_res, cx.d_fm.p, plan.n_frames, c.fm_lo, c.fm_n, st,
                       c.has_ftab, (unsigned) ci, plan.n_rec_slots, one));
     if (c.crc_n) TRY(launch_crc32(pc.d_units, pc.d_order + c.crc_off, c.crc_n, c.crc_max, d_out, pc.d_res, st));      // behind every codec's store of its results
-    if (plan.n_md5 && ci + 1 == plan.chunks.size()) {
-      // the digest units' pass: once, on the last chunk's stream, behind every chunk's launches -- the bytes it reads are all stored
-      const size_t m0 = n_sel - plan.n_md5;
+    if (plan.n_dig && ci + 1 == plan.chunks.size()) {
+      // the digest units' passes, one per algorithm: once, on the last chunk's stream, behind every chunk's launches -- the bytes
+      // they read are all stored.  The results that go back are the heads' and the tails'
+      const size_t m0 = n_sel - plan.n_dig;
       if (!one) for (size_t cj = 0; cj < ci; cj++) TRY(hipStreamWaitEvent(st, cx.ev_done[cj], 0));
       TRY(launch_md5(pc.d_units, pc.d_order + plan.md5_off, plan.n_md5, d_out, pc.out_span, pc.d_res, st));
-      TRY(hipMemcpyAsync(pc.h_res + m0, pc.d_res + m0, plan.n_md5 * sizeof(mspack_hip_result), hipMemcpyDeviceToHost, st));
+      TRY(launch_sha1(pc.d_units, pc.d_order + plan.sha1_off, plan.n_sha1, n_sel, d_out, pc.out_span, pc.d_res, st));
+      TRY(launch_sha256(pc.d_units, pc.d_order + plan.sha256_off, plan.n_sha256, n_sel, d_out, pc.out_span, pc.d_res, st));
+      TRY(hipMemcpyAsync(pc.h_res + m0, pc.d_res + m0, plan.n_dig * sizeof(mspack_hip_result), hipMemcpyDeviceToHost, st));
     }
     TRY(hipMemcpyAsync(pc.h_res + c.a, pc.d_res + c.a, (c.b - c.a) * sizeof(mspack_hip_result), hipMemcpyDeviceToHost, st));
     if (!one) { TRY(hipEventRecord(cx.ev_done[ci], st)); cb.issued.store(ci + 1, std::memory_order_release); }
@@ -465,7 +468,7 @@ static int pipeline_on_current_device(int dev, mspack_hip_unit *units, const uin
     if (pg) {
       std::lock_guard<std::mutex> lk(pg->mu);
       for (size_t ci = 0; ci < plan.chunks.size(); ci++) for (size_t i = plan.chunks[ci].a; i < plan.chunks[ci].b; i++) pg->chunk_of[plan.idx[i]] = (uint32_t) ci;
-      for (size_t i = plan.local.size() - plan.n_md5; i < plan.local.size(); i++) pg->chunk_of[plan.idx[i]] = (uint32_t) plan.chunks.size();      // (digest units: when the batch is through)
+      for (size_t i = plan.local.size() - plan.n_dig; i < plan.local.size(); i++) pg->chunk_of[plan.idx[i]] = (uint32_t) plan.chunks.size();      // (digest units and tails: when the batch is through)
       pg->planned = true;
       pg->cv.notify_all();
     }

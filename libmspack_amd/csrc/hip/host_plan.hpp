@@ -49,6 +49,10 @@ static inline bool unit_side_table(const mspack_hip_unit &u, uint64_t &lo, uint6
   }
   return false;
 }
+// digest units: the heads (MD5; SHA-1 and SHA-256, whose results go on in the next unit's) and the tails of the wide ones
+static inline bool unit_is_wide_head(const mspack_hip_unit &u) { return u.kind == MSPACK_HIP_KIND_SHA1 || u.kind == MSPACK_HIP_KIND_SHA256; }
+static inline bool unit_is_digest_head(const mspack_hip_unit &u) { return u.kind == MSPACK_HIP_KIND_MD5 || unit_is_wide_head(u); }
+static inline bool unit_is_digest(const mspack_hip_unit &u) { return unit_is_digest_head(u) || u.kind == MSPACK_HIP_KIND_DIGEST_MORE; }
 static inline size_t unit_frames(const mspack_hip_unit &u) {
   if (u.kind == MSPACK_HIP_KIND_LZX || u.kind == MSPACK_HIP_KIND_LZX_DELTA) return (size_t) u.out_len / 32768u + 1u;
   if (u.kind == MSPACK_HIP_KIND_MSZIP && unit_has_ftab(u)) return ((size_t) u.out_len + 32767u) / 32768u;   // one per CFDATA block
@@ -62,9 +66,11 @@ struct PlanKnobs {
 };
 // what plan_batch computes.  local[i] is unit idx[i] of the caller's table, offsets relative to in_lo / out_lo; the chunks are
 // ranges of local[]; order holds every chunk's per-kind lists and its CRC list (indices into local[]).
-// Digest units (MSPACK_HIP_KIND_MD5) read no input and own no output: they stand BEHIND the chunks in local[] -- indices
-// [n - n_md5, n), no chunk holds them, no per-kind list, no weight in the cutting -- and order[md5_off .. md5_off + n_md5) lists
-// them longest range first (one lane each: lanes of similar length next to each other) for the one pass behind the last chunk
+// Digest units (MSPACK_HIP_KIND_MD5, _SHA1, _SHA256 and the wide ones' _DIGEST_MORE tails) read no input and own no output: they
+// stand BEHIND the chunks in local[] -- indices [n - n_dig, n), in the caller's order, so a head keeps its tail at i + 1; no chunk
+// holds them, no per-kind list, no weight in the cutting -- and order holds three consecutive lists of HEADS, one per algorithm
+// (MD5 at md5_off, SHA-1 at sha1_off, SHA-256 at sha256_off), each longest range first (one lane each: lanes of similar length next
+// to each other) for that algorithm's one pass behind the last chunk
 struct BatchPlan {
   std::vector<uint32_t> idx;
   std::vector<mspack_hip_unit> local;
@@ -72,7 +78,9 @@ struct BatchPlan {
   std::vector<Chunk> chunks;
   uint64_t in_lo, in_hi, out_lo, out_hi, in_sum;
   size_t n_frames, n_rec_slots, n_crc;              // n_crc: units that want a digest (MSPACK_HIP_UF_CRC32)
-  size_t n_md5 = 0, md5_off = 0;                    // the digest units: how many, their list's place in order
+  size_t n_md5 = 0, md5_off = 0;                    // the MD5 units: how many, their list's place in order
+  size_t n_sha1 = 0, sha1_off = 0, n_sha256 = 0, sha256_off = 0;      // the SHA-1 / SHA-256 heads likewise
+  size_t n_dig = 0;                                 // every digest unit, tails included: local[n - n_dig .. n)
   bool monotone, has_qtm;
 };
 
@@ -87,9 +95,10 @@ static int plan_units(mspack_hip_unit *units, const uint32_t *sel, size_t n_sel,
   std::stable_sort(idx.begin(), idx.end(), [&](uint32_t x, uint32_t y) { return units[x].in_off < units[y].in_off; });
   // (digest units behind everything else, in the caller's order: their in_off means nothing)
   {
-    const auto mid = std::stable_partition(idx.begin(), idx.end(), [&](uint32_t x) { return units[x].kind != MSPACK_HIP_KIND_MD5; });
+    const auto mid = std::stable_partition(idx.begin(), idx.end(), [&](uint32_t x) { return !unit_is_digest(units[x]); });
     std::sort(mid, idx.end());
-    p.n_md5 = (size_t)(idx.end() - mid);
+    p.n_dig = (size_t)(idx.end() - mid);
+    p.n_md5 = p.n_sha1 = p.n_sha256 = 0;
   }
   local.resize(n_sel);
   bool monotone = !per_unit_back;
@@ -100,7 +109,7 @@ static int plan_units(mspack_hip_unit *units, const uint32_t *sel, size_t n_sel,
     u = units[idx[i]];
     if (u.kind != MSPACK_HIP_KIND_LZX_DELTA && !(u.kind == MSPACK_HIP_KIND_LZX && (u.flags & MSPACK_HIP_UF_LZX_LOG)) &&
         !(u.kind == MSPACK_HIP_KIND_QUANTUM && (u.flags & MSPACK_HIP_UF_QTM_MARKS))) u.ref_len = 0;
-    if (u.kind > MSPACK_HIP_KIND_MD5) { snprintf(errbuf, errcap, "unit %u: unknown kind %u", idx[i], u.kind); return -1; }
+    if (u.kind > MSPACK_HIP_KIND_MD5 && !unit_is_digest(u)) { snprintf(errbuf, errcap, "unit %u: unknown kind %u", idx[i], u.kind); return -1; }
     if (u.kind == MSPACK_HIP_KIND_XORSUM) {                // reads its input, owns no output
       if (u.flags & MSPACK_HIP_UF_CRC32) { snprintf(errbuf, errcap, "unit %u: a checksum unit decodes nothing to take a CRC-32 of", idx[i]); return -1; }
       if (u.out_len) { snprintf(errbuf, errcap, "unit %u: a checksum unit has no output", idx[i]); return -1; }
@@ -108,10 +117,26 @@ static int plan_units(mspack_hip_unit *units, const uint32_t *sel, size_t n_sel,
       in_lo = std::min<uint64_t>(in_lo, u.in_off); in_hi = std::max<uint64_t>(in_hi, u.in_off + u.in_len);
       continue;
     }
-    if (u.kind == MSPACK_HIP_KIND_MD5) {                   // reads a range of the output arena, owns nothing
+    if (u.kind == MSPACK_HIP_KIND_DIGEST_MORE) {           // a wide digest's tail: names nothing, stands right behind its head
+      // (the digest units are in table order here: neighbours in the table are neighbours in this list)
+      if (i == n_sel - p.n_dig || idx[i - 1] + 1u != idx[i] || !unit_is_wide_head(local[i - 1])) {
+        snprintf(errbuf, errcap, "unit %u: an MSPACK_HIP_KIND_DIGEST_MORE unit without a SHA-1 / SHA-256 unit in front of it", idx[i]); return -1;
+      }
+      if (u.in_len || u.out_len) { snprintf(errbuf, errcap, "unit %u: an MSPACK_HIP_KIND_DIGEST_MORE unit names no bytes (in_len and out_len must be 0)", idx[i]); return -1; }
+      u.in_off = 0; u.out_off = 0; u.flags = 0;
+      continue;
+    }
+    if (unit_is_digest_head(u)) {                          // reads a range of the output arena, owns nothing
       if (u.flags & MSPACK_HIP_UF_CRC32) { snprintf(errbuf, errcap, "unit %u: a digest unit decodes nothing to take a CRC-32 of", idx[i]); return -1; }
       if (u.in_len) { snprintf(errbuf, errcap, "unit %u: a digest unit reads no input (in_len must be 0)", idx[i]); return -1; }
       if (u.out_off > out_bytes || u.out_len > out_bytes - u.out_off) { snprintf(errbuf, errcap, "unit %u: a digest unit's range leaves the output arena", idx[i]); return -1; }
+      if (unit_is_wide_head(u)) {                          // its result goes on in the next unit's
+        if (!sel && (size_t) idx[i] + 1u >= n_sel) { snprintf(errbuf, errcap, "unit %u: a wide digest unit is the table's last unit (its MSPACK_HIP_KIND_DIGEST_MORE unit is missing)", idx[i]); return -1; }
+        if (i + 1 >= n_sel || idx[i + 1] != idx[i] + 1u || units[idx[i + 1]].kind != MSPACK_HIP_KIND_DIGEST_MORE) {
+          snprintf(errbuf, errcap, "unit %u: a wide digest unit must be followed by an MSPACK_HIP_KIND_DIGEST_MORE unit", idx[i]); return -1;
+        }
+      }
+      (u.kind == MSPACK_HIP_KIND_MD5 ? p.n_md5 : u.kind == MSPACK_HIP_KIND_SHA1 ? p.n_sha1 : p.n_sha256)++;
       u.in_off = 0; u.flags = 0;
       if (u.out_len) { out_lo = std::min<uint64_t>(out_lo, u.out_off); out_hi = std::max<uint64_t>(out_hi, u.out_off + u.out_len); }
       continue;
@@ -159,7 +184,7 @@ static int plan_units(mspack_hip_unit *units, const uint32_t *sel, size_t n_sel,
 static void plan_chunks(bool to_host, const PlanKnobs &kn, BatchPlan &p)
 {
   const std::vector<mspack_hip_unit> &local = p.local;
-  const size_t n_sel = local.size() - p.n_md5;          // (the digest units stand behind the chunks)
+  const size_t n_sel = local.size() - p.n_dig;          // (the digest units stand behind the chunks)
   const bool monotone = p.monotone;
   const uint64_t in_sum = p.in_sum;
   // chunks: arena-contiguous runs of units; enough of them to overlap the copies with the decode, each
@@ -271,10 +296,14 @@ static void plan_lists(BatchPlan &p)
         }
     c.crc_n = op - c.crc_off;
   }
-  // the digest units' list: longest range first
-  p.md5_off = op;
-  for (size_t i = n_sel - p.n_md5; i < n_sel; i++) order[op++] = (uint32_t) i;
-  std::stable_sort(order.begin() + p.md5_off, order.begin() + op, [&](uint32_t x, uint32_t y) { return local[x].out_len > local[y].out_len; });
+  // the digest units' lists, one per algorithm, heads only: longest range first
+  const unsigned dig_kind[3] = { MSPACK_HIP_KIND_MD5, MSPACK_HIP_KIND_SHA1, MSPACK_HIP_KIND_SHA256 };
+  size_t *const dig_off[3] = { &p.md5_off, &p.sha1_off, &p.sha256_off };
+  for (int a = 0; a < 3; a++) {
+    *dig_off[a] = op;
+    for (size_t i = n_sel - p.n_dig; i < n_sel; i++) if (local[i].kind == dig_kind[a]) order[op++] = (uint32_t) i;
+    std::stable_sort(order.begin() + *dig_off[a], order.begin() + op, [&](uint32_t x, uint32_t y) { return local[x].out_len > local[y].out_len; });
+  }
 }
 
 // `sel` lists the unit indices of the batch (NULL = all n_sel units).  to_host: the outputs go back to the caller's host buffer;
@@ -290,7 +319,7 @@ static int plan_batch(mspack_hip_unit *units, const uint32_t *sel, size_t n_sel,
   const uint64_t in_lo = p.in_lo, out_lo = p.out_lo;
   for (size_t i = 0; i < n_sel; i++) {
     { uint64_t tl, th; if (unit_side_table(local[i], tl, th)) local[i].in_chunk -= (uint32_t)(in_lo >> 2); }      // in_lo is a multiple of 16
-    if (local[i].kind == MSPACK_HIP_KIND_MD5) { if (local[i].out_len) local[i].out_off -= out_lo; else local[i].out_off = 0; continue; }
+    if (unit_is_digest(local[i])) { if (local[i].out_len) local[i].out_off -= out_lo; else local[i].out_off = 0; continue; }
     local[i].in_off -= in_lo;
     if (local[i].kind != MSPACK_HIP_KIND_XORSUM) local[i].out_off -= out_lo;
   }
@@ -307,7 +336,7 @@ static bool plan_shards(const mspack_hip_unit *units, size_t n_units, int n_shar
   for (size_t i = 0; i < n_units; i++) idx[i] = (uint32_t) i;
   std::stable_sort(idx.begin(), idx.end(), [&](uint32_t a, uint32_t b) { return units[a].in_off < units[b].in_off; });
   uint64_t total = 0;
-  for (size_t i = 0; i < n_units; i++) if (units[i].kind != MSPACK_HIP_KIND_MD5) total += (uint64_t) units[i].in_len + (units[i].out_len >> 2) + 256u;
+  for (size_t i = 0; i < n_units; i++) if (!unit_is_digest(units[i])) total += (uint64_t) units[i].in_len + (units[i].out_len >> 2) + 256u;
   // every shard copies its whole output span back with one copy -- valid only if the spans do not interleave, i.e. if
   // the outputs ascend with the inputs over the WHOLE batch; otherwise the shards copy back unit by unit
   ascending = true;
@@ -315,7 +344,7 @@ static bool plan_shards(const mspack_hip_unit *units, size_t n_units, int n_shar
     uint64_t prev_hi = 0;
     for (size_t i = 0; i < n_units && ascending; i++) {
       const mspack_hip_unit &u = units[idx[i]];
-      if (u.kind == MSPACK_HIP_KIND_XORSUM || u.kind == MSPACK_HIP_KIND_MD5) continue;       // (no output)
+      if (u.kind == MSPACK_HIP_KIND_XORSUM || unit_is_digest(u)) continue;                   // (no output)
       const uint64_t lo = u.out_off - std::min<uint64_t>(u.out_off, unit_below(u)), hi = u.out_off + u.out_len + unit_above(u);
       if (lo < prev_hi) ascending = false;
       prev_hi = std::max(prev_hi, hi);
@@ -326,7 +355,7 @@ static bool plan_shards(const mspack_hip_unit *units, size_t n_units, int n_shar
   // (positions [first, last] of idx): the cuts behind first .. last - 1 are barred; the cuts that stay are taken as before -- at
   // worst there are fewer shards.  (Outputs that interleave: no cut says where a range lies -- one shard.)
   std::vector<uint32_t> md5s;
-  for (size_t i = 0; i < n_units; i++) if (units[i].kind == MSPACK_HIP_KIND_MD5) md5s.push_back((uint32_t) i);
+  for (size_t i = 0; i < n_units; i++) if (unit_is_digest(units[i])) md5s.push_back((uint32_t) i);
   if (!md5s.empty() && !ascending) return false;
   std::vector<uint8_t> barred(n_units, 0);
   std::vector<size_t> md5_first(md5s.size(), (size_t) -1);
@@ -335,7 +364,7 @@ static bool plan_shards(const mspack_hip_unit *units, size_t n_units, int n_shar
     std::vector<Region> dec;                                // the units that own output, ascending and disjoint
     for (size_t i = 0; i < n_units; i++) {
       const mspack_hip_unit &u = units[idx[i]];
-      if (u.kind == MSPACK_HIP_KIND_XORSUM || u.kind == MSPACK_HIP_KIND_MD5) continue;
+      if (u.kind == MSPACK_HIP_KIND_XORSUM || unit_is_digest(u)) continue;
       dec.push_back(Region{ u.out_off - std::min<uint64_t>(u.out_off, unit_below(u)), u.out_off + u.out_len + unit_above(u), i });
     }
     for (size_t m = 0; m < md5s.size(); m++) {
@@ -354,13 +383,18 @@ static bool plan_shards(const mspack_hip_unit *units, size_t n_units, int n_shar
   {
     uint64_t acc = 0; int s = 0;
     for (size_t i = 0; i < n_units; i++) {
-      if (units[idx[i]].kind == MSPACK_HIP_KIND_MD5) continue;
+      if (unit_is_digest(units[idx[i]])) continue;
       shard[s].push_back(idx[i]);
       shard_of[i] = s;
       acc += (uint64_t) units[idx[i]].in_len + (units[idx[i]].out_len >> 2) + 256u;
       if (s + 1 < n_shards && acc * n_shards >= total * (uint64_t)(s + 1) && !barred[i]) s++;
     }
   }
-  for (size_t m = 0; m < md5s.size(); m++) shard[md5_first[m] == (size_t) -1 ? 0 : shard_of[md5_first[m]]].push_back(md5s[m]);
+  // (a wide digest's tail goes where its head went: md5s is in table order, so the head is the entry before it)
+  for (size_t m = 0, at = 0; m < md5s.size(); m++) {
+    const bool tail = units[md5s[m]].kind == MSPACK_HIP_KIND_DIGEST_MORE && m && md5s[m - 1] + 1u == md5s[m] && unit_is_wide_head(units[md5s[m - 1]]);
+    if (!tail) at = md5_first[m] == (size_t) -1 ? 0 : (size_t) shard_of[md5_first[m]];
+    shard[at].push_back(md5s[m]);
+  }
   return true;
 }

@@ -1,5 +1,6 @@
 // launch.hpp -- the launch layer and the device-resident C ABI: the thread's error text, launch<> (a kernel launch whose status is
-// returned), the launch-level environment knobs, launch_kind (one codec's launches over a compact unit list), launch_crc32, launch_md5, the
+// returned), the launch-level environment knobs, launch_kind (one codec's launches over a compact unit list), launch_crc32, launch_md5, launch_sha1 /
+// launch_sha256, the
 // analysis builds' debug exports, version / features / device functions, mspack_hip_decode_batch_device and _time_batch_device.
 #pragma once
 #include <mutex>
@@ -209,6 +210,28 @@ static hipError_t launch_md5(const mspack_hip_unit *d_units, const uint32_t *d_o
   LK(launch(mspack_md5, dim3((unsigned)((n + 63) / 64)), dim3(64), st, d_units, d_order, (u32) n, (const u8 *) d_out, (u64) out_bytes, d_results));
   return hipSuccess;
 }
+// the SHA-1 / SHA-256 pass over the heads order[0..n) of a table of n_table units (or, order == NULL, over every unit: lanes of other
+// kinds leave): one lane each, one launch per algorithm
+static hipError_t launch_sha1(const mspack_hip_unit *d_units, const uint32_t *d_order, size_t n, size_t n_table, const void *d_out, size_t out_bytes,
+                              mspack_hip_result *d_results, hipStream_t st)
+{
+  if (n == 0) return hipSuccess;
+#ifdef MSPACK_HOST_CHECK
+  return hipErrorInvalidValue;
+#endif
+  LK(launch(mspack_sha1, dim3((unsigned)((n + 63) / 64)), dim3(64), st, d_units, d_order, (u32) n, (u32) n_table, (const u8 *) d_out, (u64) out_bytes, d_results));
+  return hipSuccess;
+}
+static hipError_t launch_sha256(const mspack_hip_unit *d_units, const uint32_t *d_order, size_t n, size_t n_table, const void *d_out, size_t out_bytes,
+                                mspack_hip_result *d_results, hipStream_t st)
+{
+  if (n == 0) return hipSuccess;
+#ifdef MSPACK_HOST_CHECK
+  return hipErrorInvalidValue;
+#endif
+  LK(launch(mspack_sha256, dim3((unsigned)((n + 63) / 64)), dim3(64), st, d_units, d_order, (u32) n, (u32) n_table, (const u8 *) d_out, (u64) out_bytes, d_results));
+  return hipSuccess;
+}
 #undef LK
 
 extern "C" {
@@ -248,7 +271,7 @@ int mspack_hip_debug_pipe_phases(unsigned long long *out32) {
 #endif
 const char *mspack_hip_version(void) { return "mspack-hip 0.4 (gfx950; LZX/LZX-DELTA/Quantum/MSZIP batch decode)"; }
 const char *mspack_hip_last_error(void) { return g_err; }
-unsigned mspack_hip_features(void) { return MSPACK_HIP_FEAT_CRC32 | MSPACK_HIP_FEAT_MD5; }
+unsigned mspack_hip_features(void) { return MSPACK_HIP_FEAT_CRC32 | MSPACK_HIP_FEAT_MD5 | MSPACK_HIP_FEAT_SHA1 | MSPACK_HIP_FEAT_SHA256; }
 
 int mspack_hip_device_count(void) {
   int n = 0;
@@ -268,7 +291,7 @@ int mspack_hip_decode_batch_device(const mspack_hip_unit *d_units, const uint32_
 {
   (void) in_bytes;
   if (n_units == 0) return 0;
-  if ((kind_mask & 0x1FEu) == 0) kind_mask |= 0xFEu;    // bit k = units of kind k may be present; none = every codec (and no digest units)
+  if ((kind_mask & 0x301FEu) == 0) kind_mask |= 0xFEu;  // bit k = units of kind k may be present; none = every codec (and no digest units)
   // the caller's unit table lives on the device, so the kinds cannot be compacted here: every codec in the
   // mask gets the whole grid and blocks of other kinds leave at once.  Callers with mixed batches pass one
   // order list per codec and a one-bit mask (what the host-buffer entry points below do).
@@ -282,6 +305,11 @@ int mspack_hip_decode_batch_device(const mspack_hip_unit *d_units, const uint32_
   // the MD5 pass, behind everything that stores into the arena: only when the caller says digest units may be present
   if (kind_mask & (1u << MSPACK_HIP_KIND_MD5))
     CK(launch_md5(d_units, d_order, n_units, d_out, out_bytes, d_results, (hipStream_t) stream));
+  // ... and the SHA-1 / SHA-256 passes, one launch per algorithm
+  if (kind_mask & (1u << MSPACK_HIP_KIND_SHA1))
+    CK(launch_sha1(d_units, d_order, n_units, n_units, d_out, out_bytes, d_results, (hipStream_t) stream));
+  if (kind_mask & (1u << MSPACK_HIP_KIND_SHA256))
+    CK(launch_sha256(d_units, d_order, n_units, n_units, d_out, out_bytes, d_results, (hipStream_t) stream));
   return 0;
 }
 

@@ -21,6 +21,7 @@
 // behind the ~300 dependent VALU operations of a block.
 #pragma once
 #include "wave_common.hpp"
+#include "digest_load.hpp"
 
 __device__ __forceinline__ u32 md5_rotl(u32 x, u32 s) { return __builtin_amdgcn_alignbit(x, x, 32u - s); }
 // bit-selects: where the mask bit is set take a's bit, else b's
@@ -74,54 +75,10 @@ __device__ __forceinline__ void md5_block(u32 st[4], const u32 w[16])
   st[0] += a; st[1] += b; st[2] += c; st[3] += d;
 }
 
-// blocks of the padded message of n bytes: n + 1 (0x80) + 8 (the bit length), rounded up to 64
-__device__ __forceinline__ u64 md5_blocks(u32 n) { return ((u64) n + 8u) / 64u + 1u; }
-
-// block k (of md5_blocks(n)) of the message p[0 .. n) into w[16]
-__device__ __forceinline__ void md5_load_block(const u8 *p, const u32 n, const u64 k, u32 w[16])
-{
-  const u64 o = k * 64u;                                   // the block's first byte in the message
-  const u8 *b = p + o;
-  const u32 sh = (u32)((size_t) p & 3u);
-  if (o + 64u <= (u64) n) {                                // a whole block of message bytes
-    if (((size_t) p & 15u) == 0u) {
-      const uint4 *r = (const uint4 *) b;
-#pragma unroll
-      for (int j = 0; j < 4; j++) { const uint4 v = gld(r + j); w[4 * j] = v.x; w[4 * j + 1] = v.y; w[4 * j + 2] = v.z; w[4 * j + 3] = v.w; }
-    }
-    else if (sh == 0u) {
-      const u32 *q = (const u32 *) b;
-#pragma unroll
-      for (int j = 0; j < 16; j++) w[j] = gld(q + j);
-    }
-    else {
-      const u32 *q = (const u32 *)(b - sh);               // q[0] holds the block's first 4 - sh bytes, q[16] its last sh
-      u32 lo = gld(q);
-#pragma unroll
-      for (int j = 0; j < 16; j++) { const u32 hi = gld(q + j + 1); w[j] = __builtin_amdgcn_alignbyte(hi, lo, sh); lo = hi; }
-    }
-    return;
-  }
-  // the tail: what is left of the message, 0x80, zeros; the bit length ends the last block
-  const u32 rem = (u64) n > o ? (u32)((u64) n - o) : 0u;   // message bytes in this block (< 64)
-  const bool pad_here = (u64) n >= o;                      // the 0x80 lies in this block (else it lay in the block before)
-#pragma unroll
-  for (int j = 0; j < 16; j++) {
-    const u32 at = 4u * (u32) j;                           // the word's first byte in the block
-    u32 v = 0u;
-    if (at < rem) {
-      const u32 have = rem - at;                           // message bytes from here on: 1 ..
-      const u32 *q = (const u32 *)(b + at - sh);           // the aligned dword that holds byte `at`
-      const u32 lo = gld(q);
-      const u32 hi = (sh != 0u && have > 4u - sh) ? gld(q + 1) : 0u;      // (the next one only if a byte of the range is in it)
-      v = __builtin_amdgcn_alignbyte(hi, lo, sh);
-      if (have < 4u) v = (v & ((1u << (8u * have)) - 1u)) | (0x80u << (8u * have));
-    }
-    else if (at == rem && pad_here) v = 0x80u;
-    w[j] = v;
-  }
-  if (k + 1u == md5_blocks(n)) { w[14] = n << 3; w[15] = n >> 29; }
-}
+// the loader (three alignment paths, the tail rule, the pad) is digest_load.hpp's, shared with SHA-1 and SHA-256: MD5 takes its
+// words little-endian, as they lie, and the bit length little-endian in words 14 and 15
+__device__ __forceinline__ u64 md5_blocks(u32 n) { return digest_blocks(n); }
+__device__ __forceinline__ void md5_load_block(const u8 *p, const u32 n, const u64 k, u32 w[16]) { digest_load_block<false>(p, n, k, w); }
 
 // one lane, one range: the digest of out_arena[out_off .. out_off + out_len) -> the sixteen bytes of res->out_len .. in_next
 __device__ __forceinline__ void md5_unit(const mspack_hip_unit &u, const u8 *out_arena, const u64 out_bytes, mspack_hip_result *res)

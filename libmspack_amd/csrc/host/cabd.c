@@ -25,6 +25,7 @@
 #include <stdio.h>
 #include "host_common.h"
 #include "md5.h"
+#include "sha.h"
 
 #define CAB_BLOCKMAX   32768u
 #define CAB_INPUTMAX   (CAB_BLOCKMAX + 6144u)
@@ -83,12 +84,13 @@ struct folder_p {
    * again; folder_settle() waits for the unit and takes its result over */
   struct cab_batch *job;
   size_t job_k;
-  /* MSCABD_PARAM_HIP_MD5: the digests the folder's batch took of its files (mspack_hip.h: MSPACK_HIP_KIND_MD5), in list order;
-   * md5_hint: where the last lookup ended (files are mostly asked for in list order) */
+  /* MSCABD_PARAM_HIP_DIGESTS: the digests the folder's batch took of its files (mspack_hip.h: MSPACK_HIP_KIND_MD5 / _SHA1 / _SHA256),
+   * in list order, a file's algorithms next to each other; md5_hint: where the last lookup ended (files are mostly asked for in
+   * list order) */
   struct file_md5 *md5s;
   unsigned int n_md5s, md5_hint;
 };
-struct file_md5 { unsigned int offset, length; unsigned char d[16]; };
+struct file_md5 { unsigned int offset, length; int alg; unsigned char d[32]; };      /* alg: MSPACK_DIGEST_*; d: its 16, 20 or 32 bytes */
 struct cab_p {
   struct mscabd_cabinet base;
   int block_resv;
@@ -115,13 +117,21 @@ struct blk_reader {
   int borrowed;                       /* `input` is the caller's (gather: a place in the input arena), not reader_open's */
   unsigned int i_ptr, i_end;
 };
+/* mspack_cabd_digest's hash in progress: one of the three */
+struct digest_sink { int alg; struct mspack_md5 md5; struct mspack_sha sha; };
+static void sink_update(struct digest_sink *k, const void *data, size_t n)
+{
+  if (k->alg == MSPACK_DIGEST_MD5) mspack_md5_update(&k->md5, data, n); else mspack_sha_update(&k->sha, data, n);
+}
+static int digest_bytes(int alg) { return alg == MSPACK_DIGEST_MD5 ? 16 : alg == MSPACK_DIGEST_SHA1 ? 20 : alg == MSPACK_DIGEST_SHA256 ? 32 : 0; }
+static int digest_index(int alg) { return alg == MSPACK_DIGEST_MD5 ? 0 : alg == MSPACK_DIGEST_SHA1 ? 1 : 2; }
 struct cabd_p {
   struct mscab_decompressor base;
   struct mspack_system *system;
   int error, read_error;
   int searchbuf_size, fix_mszip, buf_size, salvage;
-  int devices, cache_mb, hip_md5;
-  struct mspack_md5 *sink;            /* mspack_cabd_md5 is running: what extract() would write goes here instead of a file */
+  int devices, cache_mb, hip_digests; /* hip_digests: MSCABD_PARAM_HIP_DIGESTS, a mask of MSPACK_DIGEST_* (MSCABD_PARAM_HIP_MD5 is its bit 1) */
+  struct digest_sink *sink;           /* mspack_cabd_digest is running: what extract() would write goes here instead of a file */
   const unsigned char *sink_kept;     /* ... or the call's bytes were exactly a file whose digest the batch has taken: that one */
   unsigned int list_stamp;            /* mspack_cabd_prefetch: one number per call, to tell a folder list that is named twice */
   /* stored (uncompressed) folders need no codec and are streamed exactly like the reference does it,
@@ -707,7 +717,7 @@ static int stored_run(struct cabd_p *self, unsigned int bytes, struct mspack_fil
     int run = (bytes > (unsigned int) self->buf_size) ? self->buf_size : (int) bytes;
     if (stored_read(self, buf, run) != run) return MSPACK_ERR_READ;
     self->st_offset += (unsigned int) run;
-    if (out && self->sink) mspack_md5_update(self->sink, buf, (size_t) run);
+    if (out && self->sink) sink_update(self->sink, buf, (size_t) run);
     else if (out && self->system->write(out, buf, run) != run) return MSPACK_ERR_WRITE;
     bytes -= (unsigned int) run;
   }
@@ -778,7 +788,7 @@ struct gathered {
   int frames_ok;
   size_t marks_off; unsigned int n_marks;       /* Quantum: the folder's request boundaries as a table in the arena (gather_marks) */
   unsigned int *marks;
-  size_t md_lo, md_n;                           /* MSCABD_PARAM_HIP_MD5: the folder's files' digest units, counted from the batch's first */
+  size_t md_lo, md_n;                           /* MSCABD_PARAM_HIP_DIGESTS: the folder's files' digest units (heads and tails), counted from the batch's first */
 };
 
 /* MSCABD_PARAM_HIP_MD5: which files get a digest unit.  The device hashes one range per LANE (MD5 is one chain per message), so
@@ -789,24 +799,36 @@ struct gathered {
  * (profiles/md5_digest.txt) --; MSPACK_HIP_MD5_RATIO overrides it (read once;
  * 0: no file gets a unit). */
 #define MD5_RATIO_DEFAULT 0.10
+/* SHA-1 and SHA-256 are chains too, so the same rule holds with their own rates, measured the same way on an MI355X box, three runs
+ * each (profiles/sha_digest.txt): SHA-1 one lane 31.5 to 39.2 MB/s, csrc/host/sha.c on one core 617 MB/s --
+ * 0.0582, 0.0511, 0.0636 --; SHA-256 one lane 15.5 to 19.0 MB/s, one core 413 to 416 MB/s -- 0.0373, 0.0460, 0.0409.  The
+ * compiled defaults are the quotients rounded down; MSPACK_HIP_SHA1_RATIO / MSPACK_HIP_SHA256_RATIO override them in the same way. */
+#define SHA1_RATIO_DEFAULT 0.05
+#define SHA256_RATIO_DEFAULT 0.04
 extern unsigned mspack_hip_features(void) __attribute__((weak));
-static double md5_ratio(void)
+static double digest_ratio(int alg)
 {
   /* (read once, in parts per million; plain C has no dynamic initialiser for a static: the first callers all compute the same
    * value, and it is published and read with atomic accesses, so two decompressors on two threads do not race) */
-  static long long ppm = -1;
-  long long v = __atomic_load_n(&ppm, __ATOMIC_RELAXED);
+  static long long ppm[3] = { -1, -1, -1 };
+  static const char *const name[3] = { "MSPACK_HIP_MD5_RATIO", "MSPACK_HIP_SHA1_RATIO", "MSPACK_HIP_SHA256_RATIO" };
+  static const double dflt[3] = { MD5_RATIO_DEFAULT, SHA1_RATIO_DEFAULT, SHA256_RATIO_DEFAULT };
+  const int a = digest_index(alg);
+  long long v = __atomic_load_n(&ppm[a], __ATOMIC_RELAXED);
   if (v < 0) {
-    const char *e = getenv("MSPACK_HIP_MD5_RATIO");
-    const double r = e ? atof(e) : MD5_RATIO_DEFAULT;
+    const char *e = getenv(name[a]);
+    const double r = e ? atof(e) : dflt[a];
     v = r <= 0.0 ? 0 : (r >= 1e6 ? 1000000000000ll : (long long)(r * 1e6 + 0.5));
-    __atomic_store_n(&ppm, v, __ATOMIC_RELAXED);
+    __atomic_store_n(&ppm[a], v, __ATOMIC_RELAXED);
   }
   return (double) v * 1e-6;
 }
-/* diagnostics (mspack.h: mspack_cabd_md5_counts): successful md5() calls answered from a digest the batch took on the device / hashed
- * on the host, over all decompressors of the process */
-static unsigned long long g_md5_counts[2];
+/* the feature bit and the unit kind of an algorithm */
+static unsigned digest_feat(int alg) { return alg == MSPACK_DIGEST_MD5 ? MSPACK_HIP_FEAT_MD5 : alg == MSPACK_DIGEST_SHA1 ? MSPACK_HIP_FEAT_SHA1 : MSPACK_HIP_FEAT_SHA256; }
+static uint8_t digest_kind(int alg) { return (uint8_t)(alg == MSPACK_DIGEST_MD5 ? MSPACK_HIP_KIND_MD5 : alg == MSPACK_DIGEST_SHA1 ? MSPACK_HIP_KIND_SHA1 : MSPACK_HIP_KIND_SHA256); }
+/* diagnostics (mspack.h: mspack_cabd_md5_counts, mspack_cabd_digest_counts): per algorithm, successful digest() calls answered from a
+ * digest the batch took on the device / hashed on the host, over all decompressors of the process */
+static unsigned long long g_digest_counts[3][2];
 
 /* The request boundaries a Quantum folder's files imply -- cabd_extract asks its codec for the bytes in front of a file, then for
  * the file (cabd.c:1195-1218): requests end where files begin and where they end.  Ascending, without duplicates, inside
@@ -1018,10 +1040,18 @@ static void batch_take_folder(struct cab_batch *B, size_t k)
       const size_t m0 = B->n + B->ck.n + gs[k].md_lo;
       size_t j;
       for (j = 0; j < gs[k].md_n; j++) {
-        if (res[m0 + j].err != MSPACK_ERR_OK) continue;
+        const int kind = units[m0 + j].kind;
+        const int alg = kind == MSPACK_HIP_KIND_MD5 ? MSPACK_DIGEST_MD5 : kind == MSPACK_HIP_KIND_SHA1 ? MSPACK_DIGEST_SHA1 : MSPACK_DIGEST_SHA256;
+        if (kind == MSPACK_HIP_KIND_DIGEST_MORE || res[m0 + j].err != MSPACK_ERR_OK) continue;      /* (a tail: taken with its head) */
         fp->md5s[fp->n_md5s].offset = (unsigned int)(units[m0 + j].out_off - units[k].out_off);
         fp->md5s[fp->n_md5s].length = units[m0 + j].out_len;
+        fp->md5s[fp->n_md5s].alg = alg;
+        memset(fp->md5s[fp->n_md5s].d, 0, sizeof(fp->md5s[fp->n_md5s].d));
         memcpy(fp->md5s[fp->n_md5s].d, &res[m0 + j].out_len, 16);
+        if (alg != MSPACK_DIGEST_MD5) {                       /* bytes 16 .. of a wide digest: in the next unit's result (mspack_hip.h) */
+          if (j + 1 >= gs[k].md_n || res[m0 + j + 1].err != MSPACK_ERR_OK) continue;
+          memcpy(fp->md5s[fp->n_md5s].d + 16, &res[m0 + j + 1].out_len, (size_t) digest_bytes(alg) - 16);
+        }
         fp->n_md5s++;
       }
     }
@@ -1063,10 +1093,18 @@ static int decode_cabinets(struct cabd_p *self, struct cab_p **cabs, size_t n_ca
   size_t n = 0, k, c, out_bytes = 0, budget = (size_t) self->cache_mb << 20, nu;
   size_t kept = used;                                   /* what the folders this call decodes have taken of the budget */
   int err = MSPACK_ERR_OK, rc, again = 0;
-  const int dev_md5 = self->hip_md5 && mspack_hip_features && (mspack_hip_features() & MSPACK_HIP_FEAT_MD5) && md5_ratio() > 0.0;
-  size_t md_cap = 0, nmd = 0;                           /* digest units: at most one per file of the gathered folders; those made */
+  /* the algorithms the batch carries units for: asked for, the provider can (one without mspack_hip_features cannot), a ratio above 0 */
+  int dev_algs = 0, per_file = 0;
+  size_t md_cap = 0, nmd = 0;                           /* digest units: at most per_file per file of the gathered folders; those made */
 
   size_t n_qtm_files = 0;                               /* files in Quantum folders: two marks each at most (gather_marks) */
+  {
+    int alg;
+    for (alg = MSPACK_DIGEST_MD5; alg <= MSPACK_DIGEST_SHA256; alg <<= 1)
+      if ((self->hip_digests & alg) && mspack_hip_features && (mspack_hip_features() & digest_feat(alg)) && digest_ratio(alg) > 0.0) {
+        dev_algs |= alg; per_file += alg == MSPACK_DIGEST_MD5 ? 1 : 2;      /* (a wide digest: head and tail) */
+      }
+  }
   for (c = 0; c < n_cabs; c++) {
     struct mscabd_file *fi;
     for (fo = cabs[c]->base.folders; fo; fo = fo->next) { n++; ((struct folder_p *) fo)->file_count = 0; ((struct folder_p *) fo)->first_file = NULL; }
@@ -1107,7 +1145,7 @@ static int decode_cabinets(struct cabd_p *self, struct cab_p **cabs, size_t n_ca
     if ((fo->comp_type & 0x0F) == MSCAB_COMP_QUANTUM) gather_marks(sys, fp->data.cab, &gs[n], &A);
     used += est;
     gs[n].md_lo = 0; gs[n].md_n = 0;
-    if (dev_md5) md_cap += fp->file_count;
+    md_cap += (size_t) per_file * fp->file_count;
     n++;
   }
   if (!err && !arena_room(sys, &A, 64)) err = MSPACK_ERR_NOMEMORY;
@@ -1152,8 +1190,8 @@ static int decode_cabinets(struct cabd_p *self, struct cab_p **cabs, size_t n_ca
     }
   }
   if (md_cap) {
-    /* one digest unit per file that lies inside what its folder's blocks hold, beside the marks gather_marks collected; the
-     * long ones are left to the host (md5_ratio) */
+    /* per algorithm one digest unit (a wide one: with its tail behind it) per file that lies inside what its folder's blocks hold,
+     * beside the marks gather_marks collected; the long ones are left to the host (digest_ratio, per algorithm) */
     double sum = 0.0;
     int pass;
     for (pass = 0; pass < 2; pass++)
@@ -1168,10 +1206,16 @@ static int decode_cabinets(struct cabd_p *self, struct cab_p **cabs, size_t n_ca
           i++;
           if (!f->length || f->offset > gs[k].total || f->length > gs[k].total - f->offset) continue;
           if (!pass) { sum += (double) f->length; continue; }
-          if ((double) f->length > md5_ratio() * sum) continue;
-          units[nu + nmd].kind = MSPACK_HIP_KIND_MD5;
-          units[nu + nmd].out_off = units[k].out_off + f->offset; units[nu + nmd].out_len = f->length;
-          nmd++;
+          {
+            int alg;
+            for (alg = MSPACK_DIGEST_MD5; alg <= MSPACK_DIGEST_SHA256; alg <<= 1) {
+              if (!(dev_algs & alg) || (double) f->length > digest_ratio(alg) * sum) continue;
+              units[nu + nmd].kind = digest_kind(alg);
+              units[nu + nmd].out_off = units[k].out_off + f->offset; units[nu + nmd].out_len = f->length;
+              nmd++;
+              if (alg != MSPACK_DIGEST_MD5) units[nu + nmd++].kind = MSPACK_HIP_KIND_DIGEST_MORE;
+            }
+          }
         }
         if (pass) gs[k].md_n = nmd - gs[k].md_lo;
       }
@@ -1328,13 +1372,13 @@ static unsigned int qtm_mark(const struct folder_p *fp, unsigned int pos)
   return (lo < fp->n_marks && fp->marks[lo] == pos) ? rd_le32(fp->mark_log + 4 * (size_t) lo) : 0;
 }
 
-/* the digest the folder's batch took of the file at [offset, offset + length), or NULL */
-static const unsigned char *kept_md5(struct folder_p *fp, unsigned int offset, unsigned int length)
+/* the digest of algorithm alg the folder's batch took of the file at [offset, offset + length), or NULL */
+static const unsigned char *kept_md5(struct folder_p *fp, int alg, unsigned int offset, unsigned int length)
 {
   unsigned int i, at = fp->md5_hint;
   for (i = 0; i < fp->n_md5s; i++, at++) {
     if (at >= fp->n_md5s) at = 0;
-    if (fp->md5s[at].offset == offset && fp->md5s[at].length == length) { fp->md5_hint = at + 1; return fp->md5s[at].d; }
+    if (fp->md5s[at].offset == offset && fp->md5s[at].length == length && fp->md5s[at].alg == alg) { fp->md5_hint = at + 1; return fp->md5s[at].d; }
   }
   return NULL;
 }
@@ -1514,9 +1558,9 @@ static int cabd_extract(struct mscab_decompressor *base, struct mscabd_file *fil
           wrote_to = file->offset + have;
         }
         if (self->sink) {
-          /* (mspack_cabd_md5: the whole file, good -- the digest the batch took of it if it did; else these bytes are hashed) */
-          if (!failed && have == filelen && (self->sink_kept = kept_md5(fol, file->offset, filelen)) != NULL) ;
-          else mspack_md5_update(self->sink, fol->dec + file->offset, have);
+          /* (mspack_cabd_digest: the whole file, good -- the digest the batch took of it if it did; else these bytes are hashed) */
+          if (!failed && have == filelen && (self->sink_kept = kept_md5(fol, self->sink->alg, file->offset, filelen)) != NULL) ;
+          else sink_update(self->sink, fol->dec + file->offset, have);
         }
         else if (write_slice(sys, fh, fol->dec + file->offset, have) != MSPACK_ERR_OK) err = MSPACK_ERR_WRITE;
       }
@@ -1535,35 +1579,48 @@ static int cabd_extract(struct mscab_decompressor *base, struct mscabd_file *fil
 }
 
 /* mspack.h: extract() with the writes replaced by a hash */
-int mspack_cabd_md5(struct mscab_decompressor *base, struct mscabd_file *file, unsigned char digest[16])
+int mspack_cabd_digest(struct mscab_decompressor *base, struct mscabd_file *file, int alg, unsigned char *digest, size_t digest_cap)
 {
   struct cabd_p *self = (struct cabd_p *) base;
-  struct mspack_md5 m;
+  struct digest_sink k;
+  const int nd = digest_bytes(alg);
   int err;
-  if (digest) memset(digest, 0, 16);
+  if (digest && nd && digest_cap >= (size_t) nd) memset(digest, 0, (size_t) nd);
   if (!self) return MSPACK_ERR_ARGS;
-  if (!file || !digest) return self->error = MSPACK_ERR_ARGS;
-  mspack_md5_init(&m);
-  self->sink = &m; self->sink_kept = NULL;
+  if (!file || !digest || !nd || digest_cap < (size_t) nd) return self->error = MSPACK_ERR_ARGS;
+  k.alg = alg;
+  if (alg == MSPACK_DIGEST_MD5) mspack_md5_init(&k.md5);
+  else if (alg == MSPACK_DIGEST_SHA1) mspack_sha1_init(&k.sha);
+  else mspack_sha256_init(&k.sha);
+  self->sink = &k; self->sink_kept = NULL;
   err = cabd_extract(base, file, NULL);
   self->sink = NULL;
   if (err == MSPACK_ERR_OK) {
-    if (self->sink_kept) memcpy(digest, self->sink_kept, 16);
-    else mspack_md5_final(&m, digest);
-    __atomic_fetch_add(&g_md5_counts[self->sink_kept ? 0 : 1], 1ull, __ATOMIC_RELAXED);
+    if (self->sink_kept) memcpy(digest, self->sink_kept, (size_t) nd);
+    else if (alg == MSPACK_DIGEST_MD5) mspack_md5_final(&k.md5, digest);
+    else mspack_sha_final(&k.sha, digest);
+    __atomic_fetch_add(&g_digest_counts[digest_index(alg)][self->sink_kept ? 0 : 1], 1ull, __ATOMIC_RELAXED);
   }
   self->sink_kept = NULL;
   return err;
 }
 
-void mspack_cabd_md5_counts(unsigned long long counts[2], int reset)
+int mspack_cabd_md5(struct mscab_decompressor *base, struct mscabd_file *file, unsigned char digest[16])
+{
+  return mspack_cabd_digest(base, file, MSPACK_DIGEST_MD5, digest, 16);
+}
+
+void mspack_cabd_digest_counts(int alg, unsigned long long counts[2], int reset)
 {
   int i;
+  if (!digest_bytes(alg)) { if (counts) counts[0] = counts[1] = 0; return; }
   for (i = 0; i < 2; i++) {
-    if (counts) counts[i] = __atomic_load_n(&g_md5_counts[i], __ATOMIC_RELAXED);
-    if (reset) __atomic_store_n(&g_md5_counts[i], 0ull, __ATOMIC_RELAXED);
+    if (counts) counts[i] = __atomic_load_n(&g_digest_counts[digest_index(alg)][i], __ATOMIC_RELAXED);
+    if (reset) __atomic_store_n(&g_digest_counts[digest_index(alg)][i], 0ull, __ATOMIC_RELAXED);
   }
 }
+
+void mspack_cabd_md5_counts(unsigned long long counts[2], int reset) { mspack_cabd_digest_counts(MSPACK_DIGEST_MD5, counts, reset); }
 
 static int cabd_param(struct mscab_decompressor *base, int param, int value)
 {
@@ -1576,7 +1633,27 @@ static int cabd_param(struct mscab_decompressor *base, int param, int value)
   case MSCABD_PARAM_SALVAGE:   self->salvage = value; break;
   case MSCABD_PARAM_HIP_DEVICES:  if (value < 1) return MSPACK_ERR_ARGS; self->devices = value; break;
   case MSCABD_PARAM_HIP_CACHE_MB: if (value < 1) return MSPACK_ERR_ARGS; self->cache_mb = value; break;
-  case MSCABD_PARAM_HIP_MD5:      if (value != 0 && value != 1) return MSPACK_ERR_ARGS; self->hip_md5 = value; break;
+  case MSCABD_PARAM_HIP_MD5:      if (value != 0 && value != 1) return MSPACK_ERR_ARGS; self->hip_digests = (self->hip_digests & ~MSPACK_DIGEST_MD5) | (value ? MSPACK_DIGEST_MD5 : 0); break;
+  case MSCABD_PARAM_HIP_DIGESTS:  if (value < 0 || value > 7) return MSPACK_ERR_ARGS; self->hip_digests = value; break;
+  default: return MSPACK_ERR_ARGS;
+  }
+  return MSPACK_ERR_OK;
+}
+
+/* mspack.h: what set_param last stored */
+int mspack_cabd_get_param(struct mscab_decompressor *base, int param, int *value)
+{
+  struct cabd_p *self = (struct cabd_p *) base;
+  if (!self || !value) return MSPACK_ERR_ARGS;
+  switch (param) {
+  case MSCABD_PARAM_SEARCHBUF: *value = self->searchbuf_size; break;
+  case MSCABD_PARAM_FIXMSZIP:  *value = self->fix_mszip; break;
+  case MSCABD_PARAM_DECOMPBUF: *value = self->buf_size; break;
+  case MSCABD_PARAM_SALVAGE:   *value = self->salvage; break;
+  case MSCABD_PARAM_HIP_DEVICES:  *value = self->devices; break;
+  case MSCABD_PARAM_HIP_CACHE_MB: *value = self->cache_mb; break;
+  case MSCABD_PARAM_HIP_MD5:      *value = (self->hip_digests & MSPACK_DIGEST_MD5) ? 1 : 0; break;
+  case MSCABD_PARAM_HIP_DIGESTS:  *value = self->hip_digests; break;
   default: return MSPACK_ERR_ARGS;
   }
   return MSPACK_ERR_OK;
@@ -1637,7 +1714,7 @@ struct mscab_decompressor *mspack_create_cab_decompressor(struct mspack_system *
   self->system = sys;
   self->error = MSPACK_ERR_OK; self->read_error = MSPACK_ERR_OK;
   self->searchbuf_size = 32768; self->fix_mszip = 0; self->buf_size = 4096; self->salvage = 0;
-  self->devices = 1; self->cache_mb = 2048; self->list_stamp = 0; self->hip_md5 = 0; self->sink = NULL; self->sink_kept = NULL;
+  self->devices = 1; self->cache_mb = 2048; self->list_stamp = 0; self->hip_digests = 0; self->sink = NULL; self->sink_kept = NULL;
   memset(&self->st, 0, sizeof(self->st)); self->st_offset = 0; self->st_active = 0; self->last_folder = NULL;
   self->msg_folder = NULL; self->msg_offset = 0; self->msg_next = 0; self->msg_next_ck = 0;
   self->live_folder = NULL; self->live_offset = 0; self->live_failed = 0; self->live_err = MSPACK_ERR_OK;
