@@ -532,7 +532,9 @@ __device__ __attribute__((noinline)) void lzx_pipe_parse_tail(const mspack_hip_u
   u32 fe = (f + 1u < nreal) ? rfl(ftab[f + 1u]) : u.in_len;
   if (fe > u.in_len || fe <= fo) fe = u.in_len;
   u8 *const fout = out_arena + u.out_off + (size_t) f * LZX_FRAME;
-  const u32 edge_n = (128u - (u32)((size_t) fout & 127u)) & 127u;
+  // (rounded up to a multiple of 16 FRAME positions: the literal ring leaves as 16-byte rows of position space, and a first row
+  // at any other position wrapped past the ring's end -- out_off need not be a multiple of 16)
+  const u32 edge_n = (((128u - (u32)((size_t) fout & 127u)) & 127u) + 15u) & ~15u;
   RecWriter W;
   W.begin(pool, (u32 *) sh->pre_tab, rec->chunk);
   W.n_chunks = n_chunks;
@@ -755,7 +757,9 @@ __device__ u32 lzx_pipe_parse(const mspack_hip_unit &u, const mspack_hip_unit *u
   if (fe > u.in_len || fe <= fo) fe = u.in_len;
   u8 *const fout = out_arena + u.out_off + (size_t) f * LZX_FRAME;
   // the frame's first bytes up to the next 128-byte line: another wave may be writing that line (see lzx_parse_emit)
-  const u32 edge_n = (128u - (u32)((size_t) fout & 127u)) & 127u;
+  // (rounded up to a multiple of 16 FRAME positions: the literal ring leaves as 16-byte rows of position space, and a first row
+  // at any other position wrapped past the ring's end -- out_off need not be a multiple of 16)
+  const u32 edge_n = (((128u - (u32)((size_t) fout & 127u)) & 127u) + 15u) & ~15u;
   // ---- the frame's first block (or what is left of the block it lies in).  Round 5: a frame need not be ONE block that begins
   // where it begins (what this build's own encoder writes, and all rounds 2-4 handled here): Microsoft's encoder writes blocks of
   // megabytes (the reference's large-files cabinets: one aligned block of 8 384 624 bytes, then the next), so a frame usually

@@ -98,7 +98,14 @@ def test_some_gpu_parity_tests_on_the_emulator(built):
            "tests/test_gpu_lzx_frames.py::test_frames_other_plaintexts",
            "tests/test_gpu_lzx_log.py",            # (the reset log of units whose blocks outlive their frames: serial and with tables)
            "tests/test_gpu_hostpath.py::test_xorsum_units_vs_oracle",               # (round 5: the CFDATA checksum kernel)
-           "tests/test_gpu_lzx_frames.py::test_real_cabinet_blocks_of_megabytes"]   # (round 5: frames inside multi-frame blocks)
+           "tests/test_gpu_lzx_frames.py::test_real_cabinet_blocks_of_megabytes",   # (round 5: frames inside multi-frame blocks)
+           # the write footprint between guard bytes at every residue (tests/footprint.py): the groups of a few seconds
+           "tests/test_gpu_footprint.py::test_lzx_lengths_and_residues[tiny]",
+           "tests/test_gpu_footprint.py::test_lzx_lengths_and_residues[frame]",
+           "tests/test_gpu_footprint.py::test_lzx_e8_at_the_edge",
+           "tests/test_gpu_footprint.py::test_lzx_delta_reference_is_read_only",
+           "tests/test_gpu_footprint.py::test_qtm_windows_and_marks",
+           "tests/test_gpu_footprint.py::test_in_len_ends_the_stream"]
     env = dict(os.environ, MSPACK_HIP_SO=SO, MSPACK_EMU_PUBLISH_DELAY_US="500")
     p = subprocess.run([sys.executable, "-m", "pytest", "-q", "-x", "-m", "gpu", "-p", "no:cacheprovider"] + ids, cwd=ROOT, env=env,
                        stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=1700)

@@ -21,7 +21,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 @pytest.mark.parametrize("policy", ["2", "0"], ids=["always", "never"])
 def test_frame_and_block_parity_with_the_fold_tasks_forced_on_and_off(built, policy):
     ids = ["tests/test_gpu_lzx_frames.py", "tests/test_gpu_mszip_blocks.py", "tests/test_gpu_runs.py", "tests/test_gpu_lzx_log.py",
-           "tests/test_gpu_mszip.py::test_mszip_request_that_ends_inside_a_block", "tests/test_gpu_crafted.py"]
+           "tests/test_gpu_mszip.py::test_mszip_request_that_ends_inside_a_block", "tests/test_gpu_crafted.py",
+           "tests/test_gpu_footprint.py"]           # (fold_write_own / _early / _late under the guard-byte check)
     env = dict(os.environ, MSPACK_HIP_FOLD=policy)
     p = subprocess.run([sys.executable, "-m", "pytest", "-q", "-x", "-m", "gpu", "-p", "no:cacheprovider", "-k",
                         "not launch_paths and not headline_batch"] + ids, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=1700)
