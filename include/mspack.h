@@ -321,6 +321,39 @@ struct mschm_decompressor {
                    struct mschmd_file *f_ptr, int f_size);
 };
 
+/* extensions of this library (plain functions: the reference's mschm_decompressor has no set_param and keeps its layout) */
+#define MSCHMD_PARAM_HIP_DIGESTS (103)   /* a mask of MSPACK_DIGEST_*: the algorithms a chunk's batch carries digest units for, per file,
+                                            for mspack_chmd_digest() (0 to 7, default 0; other values: MSPACK_ERR_ARGS) */
+/* MSPACK_ERR_ARGS for an unknown parameter or a NULL argument; get_param answers what set_param last stored (the default before that) */
+extern int mspack_chmd_set_param(struct mschm_decompressor *self, int param, int value);
+extern int mspack_chmd_get_param(struct mschm_decompressor *self, int param, int *value);
+/* A digest of a file: extract() with the writes replaced by a hash, the contract of mspack_cabd_digest() above.
+ *   returns     the code extract(file, ...) would return at this point of this decompressor's life, and it COUNTS as that call for
+ *               everything that follows: the LZX decoder the reference keeps between calls is created, advanced or dropped as by
+ *               extract(), the lines said through sys->message ("file is ... bytes longer than ...", the LZX reset warning) are
+ *               said in this call, the cache of decoded chunks is used and aged.  It opens no output file and never calls
+ *               sys->write.  last_error() answers the same.
+ *   alg         MSPACK_DIGEST_MD5, _SHA1 or _SHA256 -- one of them; anything else: MSPACK_ERR_ARGS, nothing written
+ *   digest      with MSPACK_ERR_OK the algorithm's 16, 20 or 32 bytes over exactly the bytes extract() would have handed to
+ *               sys->write (a file of length 0: the digest of the empty message; files of section 0 are hashed as they are read);
+ *               with any other code that many zero bytes (if they fit)
+ *   digest_cap  the room at digest; below the algorithm's length: MSPACK_ERR_ARGS, nothing written
+ * With the algorithm's bit set in MSCHMD_PARAM_HIP_DIGESTS when a chunk of the compressed section is decoded (up to 64 MiB of reset
+ * intervals, one GPU batch) and a batch provider that reports the algorithm's feature bit, that batch carries one digest unit per
+ * algorithm for every file that lies wholly inside the chunk, and the digests are kept with the chunk, also when its bytes leave
+ * the cache.  A call is answered from there when it succeeds and hands over exactly the file's plain range as the chunk holds it.
+ * Everything else is hashed on the host with identical results: the bit off, a provider without the feature bit, failing or
+ * partial calls, damaged or table-less files (decoded serially), intervals decoded again for another E8 origin, files that cross a
+ * chunk boundary or reach past the stream's stated length, and files too long for one lane of the device (the ratios of
+ * mspack_cabd_digest: DESIGN.md section 5, MSPACK_HIP_MD5_RATIO / _SHA1_RATIO / _SHA256_RATIO).
+ * A chunk batch that carries digest units does not run as a job (as the cabinet driver's): the call that decodes the chunk returns
+ * when all of it is decoded and its slowest digest lane has ended.  Leave the bits off for callers that extract. */
+extern int mspack_chmd_digest(struct mschm_decompressor *self, struct mschmd_file *file, int alg, unsigned char *digest, size_t digest_cap);
+/* diagnostics: how many successful mspack_chmd_digest() calls of this process, of algorithm alg, were answered from a digest taken
+ * on the device (counts[0]) and how many were hashed on the host (counts[1]); counts may be NULL; reset != 0 clears them after
+ * reading; an unknown alg: zeros */
+extern void mspack_chmd_digest_counts(int alg, unsigned long long counts[2], int reset);
+
 /* ---- SZDD (reference mspack.h:1750-1790, 1876-1975) ------------------------------------------------------ */
 #define MSSZDD_FMT_NORMAL (0)
 #define MSSZDD_FMT_QBASIC (1)

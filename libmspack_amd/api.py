@@ -104,6 +104,7 @@ MschmDecompressor._fields_ = [
 
 MSCABD_PARAM_SEARCHBUF, MSCABD_PARAM_FIXMSZIP, MSCABD_PARAM_DECOMPBUF, MSCABD_PARAM_SALVAGE = 0, 1, 2, 3
 MSCABD_PARAM_HIP_DEVICES, MSCABD_PARAM_HIP_CACHE_MB, MSCABD_PARAM_HIP_MD5, MSCABD_PARAM_HIP_DIGESTS = 100, 101, 102, 103
+MSCHMD_PARAM_HIP_DIGESTS = 103
 MSPACK_DIGEST_MD5, MSPACK_DIGEST_SHA1, MSPACK_DIGEST_SHA256 = 1, 2, 4
 DIGEST_BYTES = {MSPACK_DIGEST_MD5: 16, MSPACK_DIGEST_SHA1: 20, MSPACK_DIGEST_SHA256: 32}
 MSPACK_ERR_OK, MSPACK_ERR_ARGS = 0, 1
@@ -132,6 +133,14 @@ def _setup(L=None):
     L.mspack_cabd_digest_counts.argtypes = [C.c_int, C.c_void_p, C.c_int]
     L.mspack_cabd_get_param.restype = C.c_int
     L.mspack_cabd_get_param.argtypes = [_P(MscabDecompressor), C.c_int, _P(C.c_int)]
+    L.mspack_chmd_digest.restype = C.c_int
+    L.mspack_chmd_digest.argtypes = [_P(MschmDecompressor), _P(MschmdFile), C.c_int, C.c_void_p, C.c_size_t]
+    L.mspack_chmd_digest_counts.restype = None
+    L.mspack_chmd_digest_counts.argtypes = [C.c_int, C.c_void_p, C.c_int]
+    L.mspack_chmd_set_param.restype = C.c_int
+    L.mspack_chmd_set_param.argtypes = [_P(MschmDecompressor), C.c_int, C.c_int]
+    L.mspack_chmd_get_param.restype = C.c_int
+    L.mspack_chmd_get_param.argtypes = [_P(MschmDecompressor), C.c_int, _P(C.c_int)]
     L.mspack_version.argtypes = [C.c_int]
     L.mspack_sys_selftest_internal.argtypes = [C.c_int]
     return L
@@ -151,10 +160,17 @@ def cabd_digest_counts(alg, reset=False, L=None):
     return int(c[0]), int(c[1])
 
 
-def _digest(L, d, fptr, alg, cap=None):
+def chmd_digest_counts(alg, reset=False, L=None):
+    """mspack_chmd_digest_counts (mspack.h): successful Chm.digest() calls of algorithm alg answered (from a device digest, by the host)"""
+    c = (C.c_ulonglong * 2)()
+    _setup(L).mspack_chmd_digest_counts(int(alg), c, int(reset))
+    return int(c[0]), int(c[1])
+
+
+def _digest(L, d, fptr, alg, cap=None, fn=None):
     n = DIGEST_BYTES.get(alg, 32) if cap is None else cap
     buf = (C.c_ubyte * max(n, 1))()
-    err = L.mspack_cabd_digest(d, fptr, alg, buf, n)
+    err = (fn or L.mspack_cabd_digest)(d, fptr, alg, buf, n)
     return err, bytes(buf)[:n]
 
 
@@ -531,6 +547,22 @@ class Chm:
 
     def extract(self, i):
         return self._extract_ptr(self._files[i])
+
+    def set_param(self, param, value):
+        """mspack_chmd_set_param (mspack.h)"""
+        return self.L.mspack_chmd_set_param(self.d, param, value)
+
+    def get_param(self, param):
+        """mspack_chmd_get_param (mspack.h) -> (err, value)"""
+        v = C.c_int(-1)
+        err = self.L.mspack_chmd_get_param(self.d, param, C.byref(v))
+        return err, v.value
+
+    def digest(self, i, alg, cap=None):
+        """mspack_chmd_digest (mspack.h): extract(i) with the writes replaced by a hash of algorithm alg (MSPACK_DIGEST_*) -> (err, the
+        16 / 20 / 32 digest bytes; zeros unless err == 0).  set_param(MSCHMD_PARAM_HIP_DIGESTS, mask) before the first call lets the
+        chunks' batches take the digests on the device.  cap: the digest_cap handed over instead of the algorithm's length"""
+        return _digest(self.L, self.d, self._files[i], alg, cap, fn=self.L.mspack_chmd_digest)
 
     def find(self, name):
         f = MschmdFile()

@@ -36,6 +36,8 @@ def lib():
         L.mspk_api_bench_cabs_md5.argtypes = [C.c_void_p, C.c_void_p, C.c_uint, C.c_int, C.c_int, C.c_void_p, C.c_uint, C.POINTER(Stats)]
         L.mspk_api_bench_cabs_digest.restype = C.c_int
         L.mspk_api_bench_cabs_digest.argtypes = [C.c_void_p, C.c_void_p, C.c_uint, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_uint, C.POINTER(Stats)]
+        L.mspk_api_bench_chm_digest.restype = C.c_int
+        L.mspk_api_bench_chm_digest.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_uint, C.POINTER(Stats)]
         L.mspk_api_cab_run.restype = C.c_int
         L.mspk_api_cab_run.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]
@@ -110,6 +112,19 @@ def run_cabs_digest(images, prefetch, hip_digests, alg, max_files=65536, L=None)
     st = Stats()
     rc = L.mspk_api_bench_cabs_digest(blob.ctypes.data, offs.ctypes.data, len(images), int(bool(prefetch)), int(hip_digests), int(alg),
                                       dg.ctypes.data, max_files, C.byref(st))
+    n = min(st.n_files, max_files)
+    return rc, [dg[32 * i:32 * i + nd].tobytes() for i in range(n)], {k: getattr(st, k) for k, _t in Stats._fields_}
+
+
+def run_chm_digest(image, hip_digests, alg, max_files=65536, L=None):
+    """mspack_chmd_digest(alg) of every file of one CHM image in list order (mspk_api_bench_chm_digest), MSCHMD_PARAM_HIP_DIGESTS =
+    hip_digests.  -> (rc, [digest bytes per file], stats dict)"""
+    L = L or lib()
+    nd = {1: 16, 2: 20, 4: 32}[alg]
+    image = np.frombuffer(bytes(image), dtype=np.uint8) if not isinstance(image, np.ndarray) else np.ascontiguousarray(image, dtype=np.uint8)
+    dg = np.zeros(32 * max_files, dtype=np.uint8)
+    st = Stats()
+    rc = L.mspk_api_bench_chm_digest(image.ctypes.data, image.size, int(hip_digests), int(alg), dg.ctypes.data, max_files, C.byref(st))
     n = min(st.n_files, max_files)
     return rc, [dg[32 * i:32 * i + nd].tobytes() for i in range(n)], {k: getattr(st, k) for k, _t in Stats._fields_}
 

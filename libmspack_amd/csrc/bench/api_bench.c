@@ -337,6 +337,47 @@ int mspk_api_bench_chm(const unsigned char *chm, size_t chm_len, unsigned char *
   return 0;
 }
 
+/* the same CHM, every file's digest through mspack_chmd_digest() with algorithm alg instead of extract() (tools/chm_digest_bench.py):
+ * hip_digests = the value of MSCHMD_PARAM_HIP_DIGESTS; digests receives 32 bytes per file in list order (the algorithm's 16, 20 or
+ * 32, then zeros; at most max_files of them) */
+int mspk_api_bench_chm_digest(const unsigned char *chm, size_t chm_len, int hip_digests, int alg, unsigned char *digests,
+                              unsigned int max_files, mspk_api_stats *st)
+{
+  struct mem_sys ms;
+  struct mschm_decompressor *d;
+  struct mschmd_header *h;
+  struct mschmd_file *f;
+  double t0, t1;
+  memset(st, 0, sizeof(*st));
+  mem_sys_init(&ms, chm, chm_len, NULL, 0);
+  mspack_hip_host_path_stats(NULL, 1);
+  t0 = now_s();
+  if (!(d = mspack_create_chm_decompressor(&ms.sys))) return -1;
+  if (mspack_chmd_set_param(d, MSCHMD_PARAM_HIP_DIGESTS, hip_digests)) { mspack_destroy_chm_decompressor(d); return -4; }
+  t1 = now_s();
+  h = d->open(d, "in");
+  st->open_s = now_s() - t1;
+  if (!h) { st->first_error = d->last_error(d); mspack_destroy_chm_decompressor(d); return -2; }
+  for (f = h->files; f; f = f->next) {
+    unsigned char dg[32];
+    const double e0 = now_s();
+    const int err = (memset(dg, 0, sizeof(dg)), mspack_chmd_digest(d, f, alg, dg, sizeof(dg)));
+    if (st->n_files == 0) st->first_extract_s = now_s() - e0;
+    if (err) { if (!st->n_errors) st->first_error = err; st->n_errors++; }
+    if (digests && st->n_files < max_files) memcpy(digests + 32 * (size_t) st->n_files, dg, 32);
+    st->bytes_out += (unsigned long long) f->length;
+    st->n_files++;
+  }
+  d->close(d, h);
+  mspack_destroy_chm_decompressor(d);
+  {
+    const unsigned long long hashed = st->bytes_out;
+    finish(&ms, st, t0);
+    st->bytes_out = hashed;                 /* (nothing was written: the bytes the digests cover) */
+  }
+  return 0;
+}
+
 /* the files order[0..n) of one cabinet image extracted one after another with ONE decompressor (MSCABD_PARAM_FIXMSZIP /
  * _SALVAGE as given) -- the call sequence of oracle/ref_harness.c:refh_cab_extract, for the driver tests that compare error
  * codes, bytes and the MESSAGE LOG with the real reference's.  Every extract's bytes land at out_offs[i]; msgs receives the

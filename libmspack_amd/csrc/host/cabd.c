@@ -24,8 +24,7 @@
 #include <stdlib.h>
 #include <stdio.h>
 #include "host_common.h"
-#include "md5.h"
-#include "sha.h"
+#include "host_digest.h"
 
 #define CAB_BLOCKMAX   32768u
 #define CAB_INPUTMAX   (CAB_BLOCKMAX + 6144u)
@@ -117,14 +116,6 @@ struct blk_reader {
   int borrowed;                       /* `input` is the caller's (gather: a place in the input arena), not reader_open's */
   unsigned int i_ptr, i_end;
 };
-/* mspack_cabd_digest's hash in progress: one of the three */
-struct digest_sink { int alg; struct mspack_md5 md5; struct mspack_sha sha; };
-static void sink_update(struct digest_sink *k, const void *data, size_t n)
-{
-  if (k->alg == MSPACK_DIGEST_MD5) mspack_md5_update(&k->md5, data, n); else mspack_sha_update(&k->sha, data, n);
-}
-static int digest_bytes(int alg) { return alg == MSPACK_DIGEST_MD5 ? 16 : alg == MSPACK_DIGEST_SHA1 ? 20 : alg == MSPACK_DIGEST_SHA256 ? 32 : 0; }
-static int digest_index(int alg) { return alg == MSPACK_DIGEST_MD5 ? 0 : alg == MSPACK_DIGEST_SHA1 ? 1 : 2; }
 struct cabd_p {
   struct mscab_decompressor base;
   struct mspack_system *system;
@@ -791,41 +782,7 @@ struct gathered {
   size_t md_lo, md_n;                           /* MSCABD_PARAM_HIP_DIGESTS: the folder's files' digest units (heads and tails), counted from the batch's first */
 };
 
-/* MSCABD_PARAM_HIP_MD5: which files get a digest unit.  The device hashes one range per LANE (MD5 is one chain per message), so
- * one lane is much slower than a host core and the pass takes as long as its longest range; the host hashes everything at its
- * one-core rate.  A file longer than ratio x (all digest-range bytes of the batch), ratio = lane rate / host rate, would hold the
- * batch longer than the host takes for everything: it gets no unit and is hashed on the host.  The compiled default comes from the
- * two rates measured on an MI355X box -- one lane 67 MB/s, this file's MD5 on one core 637 MB/s, three runs: 0.1051, 0.1052, 0.1055
- * (profiles/md5_digest.txt) --; MSPACK_HIP_MD5_RATIO overrides it (read once;
- * 0: no file gets a unit). */
-#define MD5_RATIO_DEFAULT 0.10
-/* SHA-1 and SHA-256 are chains too, so the same rule holds with their own rates, measured the same way on an MI355X box, three runs
- * each (profiles/sha_digest.txt): SHA-1 one lane 31.5 to 39.2 MB/s, csrc/host/sha.c on one core 617 MB/s --
- * 0.0582, 0.0511, 0.0636 --; SHA-256 one lane 15.5 to 19.0 MB/s, one core 413 to 416 MB/s -- 0.0373, 0.0460, 0.0409.  The
- * compiled defaults are the quotients rounded down; MSPACK_HIP_SHA1_RATIO / MSPACK_HIP_SHA256_RATIO override them in the same way. */
-#define SHA1_RATIO_DEFAULT 0.05
-#define SHA256_RATIO_DEFAULT 0.04
-extern unsigned mspack_hip_features(void) __attribute__((weak));
-static double digest_ratio(int alg)
-{
-  /* (read once, in parts per million; plain C has no dynamic initialiser for a static: the first callers all compute the same
-   * value, and it is published and read with atomic accesses, so two decompressors on two threads do not race) */
-  static long long ppm[3] = { -1, -1, -1 };
-  static const char *const name[3] = { "MSPACK_HIP_MD5_RATIO", "MSPACK_HIP_SHA1_RATIO", "MSPACK_HIP_SHA256_RATIO" };
-  static const double dflt[3] = { MD5_RATIO_DEFAULT, SHA1_RATIO_DEFAULT, SHA256_RATIO_DEFAULT };
-  const int a = digest_index(alg);
-  long long v = __atomic_load_n(&ppm[a], __ATOMIC_RELAXED);
-  if (v < 0) {
-    const char *e = getenv(name[a]);
-    const double r = e ? atof(e) : dflt[a];
-    v = r <= 0.0 ? 0 : (r >= 1e6 ? 1000000000000ll : (long long)(r * 1e6 + 0.5));
-    __atomic_store_n(&ppm[a], v, __ATOMIC_RELAXED);
-  }
-  return (double) v * 1e-6;
-}
-/* the feature bit and the unit kind of an algorithm */
-static unsigned digest_feat(int alg) { return alg == MSPACK_DIGEST_MD5 ? MSPACK_HIP_FEAT_MD5 : alg == MSPACK_DIGEST_SHA1 ? MSPACK_HIP_FEAT_SHA1 : MSPACK_HIP_FEAT_SHA256; }
-static uint8_t digest_kind(int alg) { return (uint8_t)(alg == MSPACK_DIGEST_MD5 ? MSPACK_HIP_KIND_MD5 : alg == MSPACK_DIGEST_SHA1 ? MSPACK_HIP_KIND_SHA1 : MSPACK_HIP_KIND_SHA256); }
+/* MSCABD_PARAM_HIP_DIGESTS: which files get a digest unit is host_digest.h's rule (digest_ratio), shared with the CHM driver */
 /* diagnostics (mspack.h: mspack_cabd_md5_counts, mspack_cabd_digest_counts): per algorithm, successful digest() calls answered from a
  * digest the batch took on the device / hashed on the host, over all decompressors of the process */
 static unsigned long long g_digest_counts[3][2];
@@ -1100,10 +1057,9 @@ static int decode_cabinets(struct cabd_p *self, struct cab_p **cabs, size_t n_ca
   size_t n_qtm_files = 0;                               /* files in Quantum folders: two marks each at most (gather_marks) */
   {
     int alg;
+    dev_algs = digest_device_algs(self->hip_digests);
     for (alg = MSPACK_DIGEST_MD5; alg <= MSPACK_DIGEST_SHA256; alg <<= 1)
-      if ((self->hip_digests & alg) && mspack_hip_features && (mspack_hip_features() & digest_feat(alg)) && digest_ratio(alg) > 0.0) {
-        dev_algs |= alg; per_file += alg == MSPACK_DIGEST_MD5 ? 1 : 2;      /* (a wide digest: head and tail) */
-      }
+      if (dev_algs & alg) per_file += alg == MSPACK_DIGEST_MD5 ? 1 : 2;      /* (a wide digest: head and tail) */
   }
   for (c = 0; c < n_cabs; c++) {
     struct mscabd_file *fi;
@@ -1588,17 +1544,13 @@ int mspack_cabd_digest(struct mscab_decompressor *base, struct mscabd_file *file
   if (digest && nd && digest_cap >= (size_t) nd) memset(digest, 0, (size_t) nd);
   if (!self) return MSPACK_ERR_ARGS;
   if (!file || !digest || !nd || digest_cap < (size_t) nd) return self->error = MSPACK_ERR_ARGS;
-  k.alg = alg;
-  if (alg == MSPACK_DIGEST_MD5) mspack_md5_init(&k.md5);
-  else if (alg == MSPACK_DIGEST_SHA1) mspack_sha1_init(&k.sha);
-  else mspack_sha256_init(&k.sha);
+  sink_init(&k, alg);
   self->sink = &k; self->sink_kept = NULL;
   err = cabd_extract(base, file, NULL);
   self->sink = NULL;
   if (err == MSPACK_ERR_OK) {
     if (self->sink_kept) memcpy(digest, self->sink_kept, (size_t) nd);
-    else if (alg == MSPACK_DIGEST_MD5) mspack_md5_final(&k.md5, digest);
-    else mspack_sha_final(&k.sha, digest);
+    else sink_final(&k, digest);
     __atomic_fetch_add(&g_digest_counts[digest_index(alg)][self->sink_kept ? 0 : 1], 1ull, __ATOMIC_RELAXED);
   }
   self->sink_kept = NULL;

@@ -14,10 +14,17 @@
  * for E8 are re-decoded with the origin the reference would have had.
  * fast_find follows the reference: PMGI index descent, quick-reference binary
  * search inside a chunk, UTF-8 case-folded name order (chmd.c:543-898).
+ * mspack_chmd_digest (mspack.h) is extract() with another sink: the same body, the slices hashed instead of written.  With
+ * MSCHMD_PARAM_HIP_DIGESTS a chunk's batch also carries one digest unit per algorithm for every file that lies wholly inside the
+ * chunk (host_digest.h: chm_digest_plan); their answers are kept with the chunk and used for calls that hand over exactly the
+ * file's plain range.  A chunk batch that carries digest units is NOT run as a job -- digest units are through only when the whole
+ * batch is (mspack_hip.h), the decision the cabinet driver takes in decode_cabinets -- so the first call into such a chunk
+ * returns when every interval of it is decoded and its slowest digest lane has ended.
  */
 #include <stdlib.h>
 #include <stdio.h>
 #include "host_common.h"
+#include "host_digest.h"
 
 #define FRAME 32768
 
@@ -36,7 +43,11 @@ struct chm_chunk {                /* a run of reset intervals decoded in one GPU
   mspack_hip_job *job;
   mspack_hip_unit *job_units;
   unsigned int job_waited;        /* units [0, job_waited) have come through                        */
+  /* MSCHMD_PARAM_HIP_DIGESTS: the digests the chunk's batches took of its files, ascending by (offset, length, alg); dg_algs: the
+   * algorithms a batch of this chunk has carried units for.  Kept when buf is evicted; freed with section 1 */
+  struct chm_dg *dg; size_t n_dg; int dg_algs;
 };
+struct chm_dg { off_t offset, length; int alg, ok; unsigned char d[32]; };   /* alg: MSPACK_DIGEST_*; ok: the unit's result was MSPACK_ERR_OK; d: its 16, 20 or 32 bytes */
 struct chm_p {
   struct mschmd_header base;
   /* section 1 */
@@ -56,6 +67,9 @@ struct chm_p {
   size_t arena_room;              /* bytes of the arena buffer that belong to the batch decoder's input arena */
   mspack_hip_result *ires;        /* stand-alone result per interval                                */
   struct chm_chunk *chunks; unsigned int n_chunks, chunk_int; unsigned long stamp;
+  /* the section-1 files of chm->files with length > 0, ascending by offset: one walk of the list, when section 1 is set up
+   * (fast_open lists no files: none) -- what chm_digest_plan picks a chunk's digest units from */
+  struct chm_digest_file *dfiles; size_t n_dfiles;
   /* the serial span of the virtual decoder (damaged / table-less files) */
   int s_valid, s_mode; off_t s_init, s_cover; unsigned char *s_buf; mspack_hip_result s_res;
   unsigned int s_log_n, s_log_cap;     /* the serial span's reset log (MSPACK_HIP_UF_LZX_LOG): frames, counted from s_init, whose
@@ -78,7 +92,13 @@ struct chmd_p {
   struct mspack_system *system;
   int error;
   struct chm_p *v_chm; struct vdec v;
+  int hip_digests;                    /* MSCHMD_PARAM_HIP_DIGESTS: a mask of MSPACK_DIGEST_* */
+  struct digest_sink *sink;           /* mspack_chmd_digest is running: what extract() would write goes here instead of a file */
+  int sink_whole;                     /* ... and the emit step hands over exactly the file's plain range, of a call that is good so far */
+  const unsigned char *sink_kept;     /* ... and that file's digest was taken by its chunk's batch: this one */
 };
+/* per algorithm, successful mspack_chmd_digest() calls answered from a device digest / hashed on the host (mspack.h) */
+static unsigned long long g_digest_counts[3][2];
 
 static off_t read_encint(const unsigned char **p, const unsigned char *end, int *err) {
   off_t v = 0; unsigned char c = 0x80; int i = 0;
@@ -511,7 +531,9 @@ static unsigned char *read_sec0_file(struct chmd_p *self, struct mspack_file *fh
  * is the reference's own control flow, exact by construction.  E8: the translation origin is the creation
  * point (lzxd.c:712); fast results use origin 0, so intervals that applied E8 are decoded again with the
  * shifted origin when the decoder was created elsewhere. */
+#ifndef CHM_CHUNK_BYTES                    /* (tests/csrc/chm_digest_check.c is built with small chunks, to have several of them) */
 #define CHM_CHUNK_BYTES ((off_t) 64 << 20)
+#endif
 #define CHM_SERIAL_SLACK 16                 /* serial spans are decoded this many intervals past the need */
 
 static int hip_batch(mspack_hip_unit *units, size_t n, const void *in, size_t in_bytes, void *out, size_t out_bytes,
@@ -522,16 +544,85 @@ static int hip_batch(mspack_hip_unit *units, size_t n, const void *in, size_t in
                 : mspack_hip_decode_batch(units, n, in, in_bytes, out, out_bytes, res);
 }
 
-/* decode intervals [first, first+count) stand-alone; interval i's E8 origin is i*interval - e8_origin */
+static int dg_order(const void *pa, const void *pb)
+{
+  const struct chm_dg *a = (const struct chm_dg *) pa, *b = (const struct chm_dg *) pb;
+  if (a->offset != b->offset) return a->offset < b->offset ? -1 : 1;
+  if (a->length != b->length) return a->length < b->length ? -1 : 1;
+  return a->alg - b->alg;
+}
+
+/* the digests a chunk's batch took (units[0 .. n): heads and tails, out_off counted from the chunk's first byte at stream offset
+ * `lo`; res: their results) join the chunk's table.  Without memory for it they are dropped: those files are hashed on the host */
+static void chunk_keep_digests(struct mspack_system *sys, struct chm_chunk *ch, off_t lo, const mspack_hip_unit *units,
+                               const mspack_hip_result *res, size_t n, int algs)
+{
+  struct chm_dg *t = (struct chm_dg *) sys->alloc(sys, (ch->n_dg + n) * sizeof(*t));
+  size_t j;
+  if (!t) return;
+  if (ch->n_dg) memcpy(t, ch->dg, ch->n_dg * sizeof(*t));
+  sys->free(ch->dg); ch->dg = t;
+  for (j = 0; j < n; j++) {
+    const uint8_t kind = units[j].kind;
+    struct chm_dg *e = &t[ch->n_dg];
+    if (kind == MSPACK_HIP_KIND_DIGEST_MORE) continue;                  /* (a tail: taken with its head) */
+    e->alg = kind == MSPACK_HIP_KIND_MD5 ? MSPACK_DIGEST_MD5 : kind == MSPACK_HIP_KIND_SHA1 ? MSPACK_DIGEST_SHA1 : MSPACK_DIGEST_SHA256;
+    e->offset = lo + (off_t) units[j].out_off; e->length = (off_t) units[j].out_len;
+    e->ok = res[j].err == MSPACK_ERR_OK;
+    memset(e->d, 0, sizeof(e->d));
+    memcpy(e->d, &res[j].out_len, 16);
+    /* bytes 16 .. of a wide digest: in the next unit's result (mspack_hip.h) */
+    if (e->alg != MSPACK_DIGEST_MD5 && j + 1 < n) memcpy(e->d + 16, &res[j + 1].out_len, (size_t) digest_bytes(e->alg) - 16);
+    ch->n_dg++;
+  }
+  ch->dg_algs |= algs;
+  qsort(ch->dg, ch->n_dg, sizeof(*ch->dg), dg_order);
+}
+
+/* the digest of algorithm alg a batch of the chunk took of the file at [offset, offset + length), or NULL */
+static const unsigned char *chunk_digest(const struct chm_chunk *ch, off_t offset, off_t length, int alg)
+{
+  size_t lo = 0, hi = ch->n_dg;
+  struct chm_dg want;
+  want.offset = offset; want.length = length; want.alg = alg;
+  while (lo < hi) {
+    const size_t mid = lo + (hi - lo) / 2;
+    const int o = dg_order(&want, &ch->dg[mid]);
+    if (o == 0) return ch->dg[mid].ok ? ch->dg[mid].d : NULL;
+    if (o > 0) lo = mid + 1; else hi = mid;
+  }
+  return NULL;
+}
+
+/* decode intervals [first, first+count) stand-alone; interval i's E8 origin is i*interval - e8_origin.  dg_ch: the chunk these
+ * intervals are, when its files' digest units may ride in the batch (chm_digest_plan, behind the interval units) */
 static int decode_intervals(struct chmd_p *self, struct chm_p *c, unsigned int first, unsigned int count,
-                            off_t e8_origin, unsigned char *out, mspack_hip_result *res, struct chm_chunk *as_job)
+                            off_t e8_origin, unsigned char *out, mspack_hip_result *res, struct chm_chunk *as_job, struct chm_chunk *dg_ch)
 {
   struct mspack_system *sys = self->system;
-  mspack_hip_unit *units = (mspack_hip_unit *) sys->alloc(sys, (size_t) count * sizeof(*units));
+  const off_t lo = (off_t) first * c->interval_bytes;
+  const int dg_algs = dg_ch && c->n_dfiles && c->padded_len > lo ? digest_device_algs(self->hip_digests & ~dg_ch->dg_algs) : 0;
+  double ratio[3] = { 0.0, 0.0, 0.0 };
+  size_t n_dg = 0;
+  mspack_hip_unit *units;
+  mspack_hip_result *res_all = NULL;      /* with digest units: the batch's results, the intervals' copied to res afterwards */
   unsigned int k;
   int rc;
+  if (dg_algs) {
+    int alg;
+    for (alg = MSPACK_DIGEST_MD5; alg <= MSPACK_DIGEST_SHA256; alg <<= 1) ratio[digest_index(alg)] = digest_ratio(alg);
+    n_dg = chm_digest_plan(c->dfiles, c->n_dfiles, (uint64_t) lo, (uint64_t)(lo + (off_t) count * c->interval_bytes),
+                           (uint64_t) c->padded_len, dg_algs, ratio, NULL, 0);
+  }
+  units = (mspack_hip_unit *) sys->alloc(sys, ((size_t) count + n_dg) * sizeof(*units));
   if (!units) return MSPACK_ERR_NOMEMORY;
+  if (n_dg && !(res_all = (mspack_hip_result *) sys->alloc(sys, ((size_t) count + n_dg) * sizeof(*res_all)))) n_dg = 0;   /* (no memory: no units) */
   memset(units, 0, (size_t) count * sizeof(*units));
+  if (n_dg) {
+    (void) chm_digest_plan(c->dfiles, c->n_dfiles, (uint64_t) lo, (uint64_t)(lo + (off_t) count * c->interval_bytes),
+                           (uint64_t) c->padded_len, dg_algs, ratio, units + count, n_dg);
+    memset(res_all, 0, ((size_t) count + n_dg) * sizeof(*res_all));
+  }
   for (k = 0; k < count; k++) {
     uint64_t off = c->ioff[first + k];
     if (off > (uint64_t) c->arena_len) off = c->arena_len;        /* an entry beyond the file: nothing to read */
@@ -557,13 +648,18 @@ static int decode_intervals(struct chmd_p *self, struct chm_p *c, unsigned int f
   }
   /* a chunk's batch runs as a job when it can: extract() of the first file returns when the file's intervals are through,
    * and the caller writes it while the rest is decoded and copied back (one device: a sharded batch is synchronous) */
-  if (as_job && count > 1 && mspack_hip_default_devices() <= 1 &&
+  /* (digest units are through when the whole batch is: a batch that carries some is waited for here) */
+  if (as_job && !n_dg && count > 1 && mspack_hip_default_devices() <= 1 &&
       (as_job->job = mspack_hip_decode_batch_begin(units, count, c->arena, c->arena_room, out, (size_t) count * (size_t) c->interval_bytes + 64, res))) {
     as_job->job_units = units; as_job->job_waited = 0;
     return MSPACK_ERR_OK;
   }
-  rc = hip_batch(units, count, c->arena, c->arena_room, out, (size_t) count * (size_t) c->interval_bytes + 64, res);
-  sys->free(units);
+  rc = hip_batch(units, (size_t) count + n_dg, c->arena, c->arena_room, out, (size_t) count * (size_t) c->interval_bytes + 64, n_dg ? res_all : res);
+  if (n_dg && !rc) {
+    memcpy(res, res_all, (size_t) count * sizeof(*res));
+    chunk_keep_digests(sys, dg_ch, lo, units + count, res_all + count, n_dg, dg_algs);
+  }
+  sys->free(units); sys->free(res_all);
   if (rc) { sys->message(NULL, "GPU batch decode failed: %s", mspack_hip_last_error()); return MSPACK_ERR_DECRUNCH; }
   return MSPACK_ERR_OK;
 }
@@ -582,11 +678,34 @@ static int chunk_settle(struct mspack_system *sys, struct chm_chunk *ch)
 
 static void free_sec1(struct mspack_system *sys, struct chm_p *c) {
   unsigned int i;
-  if (c->chunks) for (i = 0; i < c->n_chunks; i++) { (void) chunk_settle(sys, &c->chunks[i]); mspack_arena_free(sys, c->chunks[i].buf); }
+  if (c->chunks) for (i = 0; i < c->n_chunks; i++) { (void) chunk_settle(sys, &c->chunks[i]); mspack_arena_free(sys, c->chunks[i].buf); sys->free(c->chunks[i].dg); }
   if (c->arena_pinned) { mspack_hip_unpin(c->arena); c->arena_pinned = 0; }
   sys->free(c->chunks); mspack_arena_free(sys, c->arena); sys->free(c->ioff); sys->free(c->ires); mspack_arena_free(sys, c->s_buf);
+  sys->free(c->dfiles); c->dfiles = NULL; c->n_dfiles = 0;
   c->chunks = NULL; c->arena = NULL; c->ioff = NULL; c->ires = NULL; c->s_buf = NULL; c->sec1_state = 0;
   c->n_chunks = 0; c->s_valid = 0;
+}
+
+static int dfile_order(const void *pa, const void *pb)
+{
+  const struct chm_digest_file *a = (const struct chm_digest_file *) pa, *b = (const struct chm_digest_file *) pb;
+  if (a->offset != b->offset) return a->offset < b->offset ? -1 : 1;
+  return a->length < b->length ? -1 : a->length > b->length;
+}
+
+/* c->dfiles: one walk of chm->files, once per CHM (advice for the chunks' batches: without memory for it no file gets a unit) */
+static void collect_dfiles(struct mspack_system *sys, struct chm_p *c)
+{
+  const struct mschmd_file *fi;
+  size_t n = 0;
+  for (fi = c->base.files; fi; fi = fi->next) if (fi->section && fi->section->id == 1 && fi->offset >= 0 && fi->length > 0) n++;
+  if (!n || !(c->dfiles = (struct chm_digest_file *) sys->alloc(sys, n * sizeof(*c->dfiles)))) return;
+  for (fi = c->base.files; fi; fi = fi->next)
+    if (fi->section && fi->section->id == 1 && fi->offset >= 0 && fi->length > 0) {
+      c->dfiles[c->n_dfiles].offset = (uint64_t) fi->offset; c->dfiles[c->n_dfiles].length = (uint64_t) fi->length;
+      c->n_dfiles++;
+    }
+  qsort(c->dfiles, c->n_dfiles, sizeof(*c->dfiles), dfile_order);
 }
 
 /* ControlData, the compressed stream, ResetTable and SpanInfo: everything chmd_init_decomp (chmd.c:1072-1188)
@@ -736,8 +855,10 @@ static int setup_sec1(struct chmd_p *self, struct chm_p *c, struct mspack_file *
     for (i = 0; i < c->n_chunks; i++) {
       c->chunks[i].buf = NULL; c->chunks[i].stamp = 0; c->chunks[i].res_valid = 0;
       c->chunks[i].job = NULL; c->chunks[i].job_units = NULL; c->chunks[i].job_waited = 0;
+      c->chunks[i].dg = NULL; c->chunks[i].n_dg = 0; c->chunks[i].dg_algs = 0;
     }
     if (!(c->ires = (mspack_hip_result *) sys->alloc(sys, (size_t) c->n_fast * sizeof(mspack_hip_result)))) return MSPACK_ERR_NOMEMORY;
+    collect_dfiles(sys, c);
   }
   return MSPACK_ERR_OK;
 }
@@ -794,7 +915,7 @@ static int ensure_chunk_to(struct chmd_p *self, struct chm_p *c, unsigned int k,
   /* (a chunk whose bytes will not be kept -- beyond the cache budget -- is decoded synchronously: its buffer goes at once) */
   {
     const int keep = need_buf || count * (size_t) c->interval_bytes <= ((size_t) mspack_hip_cache_mb() << 20);
-    err = decode_intervals(self, c, first, count, 0, ch->buf, &c->ires[first], keep ? ch : NULL);
+    err = decode_intervals(self, c, first, count, 0, ch->buf, &c->ires[first], keep ? ch : NULL, ch);
     if (err) { mspack_arena_free(sys, ch->buf); ch->buf = NULL; return err; }
     ch->res_valid = 1;
     if (!keep) { mspack_arena_free(sys, ch->buf); ch->buf = NULL; }
@@ -950,13 +1071,34 @@ static int vdec_decode(struct chmd_p *self, struct chm_p *c, off_t A, off_t B, o
   }
 }
 
+/* the emit step's sink: the bytes go to the output file, or into mspack_chmd_digest's hash */
+static int emit_slice(struct chmd_p *self, struct mspack_file *fh, const unsigned char *p, size_t n)
+{
+  if (self->sink) { sink_update(self->sink, p, n); return MSPACK_ERR_OK; }
+  return write_slice(self->system, fh, p, n);
+}
+
 /* write [from, to) of the uncompressed stream as the virtual decoder produced it */
 static int vdec_emit(struct chmd_p *self, struct chm_p *c, struct mspack_file *fh, off_t from, off_t to)
 {
   struct mspack_system *sys = self->system;
   struct vdec *v = &self->v;
   if (to <= from) return MSPACK_ERR_OK;
-  if (v->serial) return write_slice(sys, fh, c->s_buf + (from - v->init), (size_t)(to - from));
+  if (v->serial) return emit_slice(self, fh, c->s_buf + (from - v->init), (size_t)(to - from));
+  if (self->sink && self->sink_whole) {
+    /* mspack_chmd_digest, [from, to) is the file's plain range: the digest its chunk's batch took of it, if it did and these
+     * bytes are the fast results' (no interval of the range is decoded again with a shifted E8 origin, below).  The chunk is
+     * asked for as the loop below asks (its results, its place in the LRU), only its bytes are not needed */
+    unsigned int k = (unsigned int)(from / c->interval_bytes), k1 = (unsigned int)((to - 1) / c->interval_bytes), i;
+    if (k / c->chunk_int == k1 / c->chunk_int) {
+      struct chm_chunk *ch;
+      int err, shifted = 0;
+      if ((err = ensure_chunk_to(self, c, k, k1, 0, &ch))) return err;
+      if (v->init != 0)
+        for (i = k; i <= k1; i++) if (c->ires[i].flags & MSPACK_HIP_F_E8_APPLIED) shifted = 1;
+      if (!shifted && (self->sink_kept = chunk_digest(ch, from, to - from, self->sink->alg)) != NULL) return MSPACK_ERR_OK;
+    }
+  }
   while (from < to) {
     unsigned int k = (unsigned int)(from / c->interval_bytes), ci = k / c->chunk_int;
     unsigned int cfirst = ci * c->chunk_int, clast = cfirst + c->chunk_int - 1;   /* this chunk's intervals */
@@ -972,12 +1114,12 @@ static int vdec_emit(struct chmd_p *self, struct chm_p *c, struct mspack_file *f
       unsigned int cnt = k1 - k + 1;
       mspack_hip_result *r2 = (mspack_hip_result *) sys->alloc(sys, cnt * sizeof(*r2));
       unsigned char *tmp = (unsigned char *) mspack_arena_alloc(sys, (size_t) cnt * (size_t) c->interval_bytes + 128);
-      err = (!r2 || !tmp) ? MSPACK_ERR_NOMEMORY : decode_intervals(self, c, k, cnt, v->init, tmp, r2, NULL);
-      if (!err) err = write_slice(sys, fh, tmp + (from - (off_t) k * c->interval_bytes), (size_t)(stop - from));
+      err = (!r2 || !tmp) ? MSPACK_ERR_NOMEMORY : decode_intervals(self, c, k, cnt, v->init, tmp, r2, NULL, NULL);
+      if (!err) err = emit_slice(self, fh, tmp + (from - (off_t) k * c->interval_bytes), (size_t)(stop - from));
       sys->free(r2); mspack_arena_free(sys, tmp);
       if (err) return err;
     }
-    else if ((err = write_slice(sys, fh, ch->buf + (from - (off_t) cfirst * c->interval_bytes), (size_t)(stop - from)))) return err;
+    else if ((err = emit_slice(self, fh, ch->buf + (from - (off_t) cfirst * c->interval_bytes), (size_t)(stop - from)))) return err;
     from = stop;
   }
   return MSPACK_ERR_OK;
@@ -997,8 +1139,10 @@ static int chmd_extract(struct mschm_decompressor *base, struct mschmd_file *fil
 
   if (!(infh = sys->open(sys, c->base.filename, MSPACK_SYS_OPEN_READ))) return self->error = MSPACK_ERR_OPEN;
   if (self->v_chm != c) { self->v_chm = c; self->v.alive = 0; }
-  if (!(fh = sys->open(sys, filename, MSPACK_SYS_OPEN_WRITE))) { sys->close(infh); return self->error = MSPACK_ERR_OPEN; }
-  if (!file->length) { sys->close(fh); sys->close(infh); return self->error = MSPACK_ERR_OK; }
+  /* (mspack_chmd_digest: no output file; the lines extract() says with the output's handle are said without one) */
+  if (self->sink) fh = NULL;
+  else if (!(fh = sys->open(sys, filename, MSPACK_SYS_OPEN_WRITE))) { sys->close(infh); return self->error = MSPACK_ERR_OPEN; }
+  if (!file->length) { if (fh) sys->close(fh); sys->close(infh); return self->error = MSPACK_ERR_OK; }
   self->error = MSPACK_ERR_OK;
 
   if (file->section->id == 0) {
@@ -1010,7 +1154,8 @@ static int chmd_extract(struct mschm_decompressor *base, struct mschmd_file *fil
       while (length > 0) {
         int run = length > (off_t) sizeof(buf) ? (int) sizeof(buf) : (int) length;
         if (sys->read(infh, buf, run) != run) { self->error = MSPACK_ERR_READ; break; }
-        if (sys->write(fh, buf, run) != run) { self->error = MSPACK_ERR_WRITE; break; }
+        if (self->sink) sink_update(self->sink, buf, (size_t) run);
+        else if (sys->write(fh, buf, run) != run) { self->error = MSPACK_ERR_WRITE; break; }
         length -= run;
       }
     }
@@ -1055,6 +1200,7 @@ static int chmd_extract(struct mschm_decompressor *base, struct mschmd_file *fil
           if (good > file->offset + length) good = file->offset + length;
           if (err != MSPACK_ERR_NOMEMORY && good > file->offset) {
             if (good > v->length) good = v->length;
+            self->sink_whole = !err && length == file->length && good == file->offset + file->length;
             if ((werr = vdec_emit(self, c, fh, file->offset, good))) err = werr;
           }
         }
@@ -1064,9 +1210,59 @@ static int chmd_extract(struct mschm_decompressor *base, struct mschmd_file *fil
     }
     self->error = err;
   }
-  sys->close(fh);
+  if (fh) sys->close(fh);
   sys->close(infh);
   return self->error;
+}
+
+/* mspack.h: extract() with the writes replaced by a hash */
+int mspack_chmd_digest(struct mschm_decompressor *base, struct mschmd_file *file, int alg, unsigned char *digest, size_t digest_cap)
+{
+  struct chmd_p *self = (struct chmd_p *) base;
+  struct digest_sink k;
+  const int nd = digest_bytes(alg);
+  int err;
+  if (digest && nd && digest_cap >= (size_t) nd) memset(digest, 0, (size_t) nd);
+  if (!self) return MSPACK_ERR_ARGS;
+  if (!file || !digest || !nd || digest_cap < (size_t) nd) return self->error = MSPACK_ERR_ARGS;
+  sink_init(&k, alg);
+  self->sink = &k; self->sink_whole = 0; self->sink_kept = NULL;
+  err = chmd_extract(base, file, NULL);
+  self->sink = NULL;
+  if (err == MSPACK_ERR_OK) {
+    if (self->sink_kept) memcpy(digest, self->sink_kept, (size_t) nd);
+    else sink_final(&k, digest);
+    __atomic_fetch_add(&g_digest_counts[digest_index(alg)][self->sink_kept ? 0 : 1], 1ull, __ATOMIC_RELAXED);
+  }
+  self->sink_whole = 0; self->sink_kept = NULL;
+  return err;
+}
+
+void mspack_chmd_digest_counts(int alg, unsigned long long counts[2], int reset)
+{
+  int i;
+  if (!digest_bytes(alg)) { if (counts) counts[0] = counts[1] = 0; return; }
+  for (i = 0; i < 2; i++) {
+    if (counts) counts[i] = __atomic_load_n(&g_digest_counts[digest_index(alg)][i], __ATOMIC_RELAXED);
+    if (reset) __atomic_store_n(&g_digest_counts[digest_index(alg)][i], 0ull, __ATOMIC_RELAXED);
+  }
+}
+
+int mspack_chmd_set_param(struct mschm_decompressor *base, int param, int value)
+{
+  struct chmd_p *self = (struct chmd_p *) base;
+  if (!self) return MSPACK_ERR_ARGS;
+  if (param != MSCHMD_PARAM_HIP_DIGESTS || value < 0 || value > 7) return MSPACK_ERR_ARGS;
+  self->hip_digests = value;
+  return MSPACK_ERR_OK;
+}
+
+int mspack_chmd_get_param(struct mschm_decompressor *base, int param, int *value)
+{
+  struct chmd_p *self = (struct chmd_p *) base;
+  if (!self || !value || param != MSCHMD_PARAM_HIP_DIGESTS) return MSPACK_ERR_ARGS;
+  *value = self->hip_digests;
+  return MSPACK_ERR_OK;
 }
 
 static int chmd_error(struct mschm_decompressor *base) {
