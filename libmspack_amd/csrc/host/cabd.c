@@ -20,6 +20,9 @@
  * segments, and a CFDATA block with uncompressed size 0 continues as the first block of the next
  * segment (cabd.c:1432-1455).  search() finds embedded cabinets with the reference's acceptance
  * rules (cabd.c:656-868).
+ * mspack_cabd_digest() (mspack.h) is extract() with the writes replaced by a hash.  With MSCABD_PARAM_HIP_DIGESTS the batch also
+ * carries digest units for the files that lie inside their folders (host_digest.h: digest_emit_file); their answers are kept with
+ * the folder (digest_table_harvest) and answer the calls that hand over exactly such a file (digest_table_find).
  */
 #include <stdlib.h>
 #include <stdio.h>
@@ -84,12 +87,9 @@ struct folder_p {
   struct cab_batch *job;
   size_t job_k;
   /* MSCABD_PARAM_HIP_DIGESTS: the digests the folder's batch took of its files (mspack_hip.h: MSPACK_HIP_KIND_MD5 / _SHA1 / _SHA256),
-   * in list order, a file's algorithms next to each other; md5_hint: where the last lookup ended (files are mostly asked for in
-   * list order) */
-  struct file_md5 *md5s;
-  unsigned int n_md5s, md5_hint;
+   * by offset in the folder (host_digest.h: struct digest_table) */
+  struct digest_table dg;
 };
-struct file_md5 { unsigned int offset, length; int alg; unsigned char d[32]; };      /* alg: MSPACK_DIGEST_*; d: its 16, 20 or 32 bytes */
 struct cab_p {
   struct mscabd_cabinet base;
   int block_resv;
@@ -193,7 +193,7 @@ static void free_folder_cache(struct mspack_system *sys, struct folder_p *f) {
   sys->free(f->rep); f->rep = NULL; f->rep_n = 0;
   sys->free(f->rep_ck); f->rep_ck = NULL; f->ck_n = 0;
   sys->free(f->marks); f->marks = NULL; f->n_marks = 0; f->mark_log = NULL;
-  sys->free(f->md5s); f->md5s = NULL; f->n_md5s = 0; f->md5_hint = 0;
+  sys->free(f->dg.e); memset(&f->dg, 0, sizeof(f->dg));
 }
 
 /* ---- headers (reference cabd.c:317-628) ------------------------------------------------------------- */
@@ -702,7 +702,7 @@ static int stored_read(struct cabd_p *self, unsigned char *buf, int bytes) {
 }
 
 /* produce `bytes` more bytes of the folder; out == NULL skips (the offset still advances) */
-static struct mspack_file *const MD5_SINK = (struct mspack_file *) &MD5_SINK;      /* (mspack_cabd_md5: "the output file", never handed to the system) */
+static struct mspack_file *const DIGEST_SINK = (struct mspack_file *) &DIGEST_SINK;      /* (mspack_cabd_digest: "the output file", never handed to the system) */
 static int stored_run(struct cabd_p *self, unsigned int bytes, struct mspack_file *out, unsigned char *buf) {
   while (bytes > 0) {
     int run = (bytes > (unsigned int) self->buf_size) ? self->buf_size : (int) bytes;
@@ -728,7 +728,7 @@ static int stored_extract(struct cabd_p *self, struct folder_p *fol, struct msca
     self->st_active = 1; self->st_offset = 0;
     self->read_error = MSPACK_ERR_OK;                     /* lasts for the lifetime of a decompressor */
   }
-  if (self->sink) fh = MD5_SINK;
+  if (self->sink) fh = DIGEST_SINK;
   else if (!(fh = sys->open(sys, filename, MSPACK_SYS_OPEN_WRITE))) return self->error = MSPACK_ERR_OPEN;
   self->error = MSPACK_ERR_OK;
   if (filelen) {
@@ -744,7 +744,7 @@ static int stored_extract(struct cabd_p *self, struct folder_p *fol, struct msca
       sys->free(buf);
     }
   }
-  if (fh != MD5_SINK) sys->close(fh);
+  if (fh != DIGEST_SINK) sys->close(fh);
   return self->error;
 }
 
@@ -779,10 +779,11 @@ struct gathered {
   int frames_ok;
   size_t marks_off; unsigned int n_marks;       /* Quantum: the folder's request boundaries as a table in the arena (gather_marks) */
   unsigned int *marks;
-  size_t md_lo, md_n;                           /* MSCABD_PARAM_HIP_DIGESTS: the folder's files' digest units (heads and tails), counted from the batch's first */
+  size_t dg_lo, dg_n;                           /* MSCABD_PARAM_HIP_DIGESTS: the folder's files' digest units (heads and tails), counted from the batch's first */
 };
 
-/* MSCABD_PARAM_HIP_DIGESTS: which files get a digest unit is host_digest.h's rule (digest_ratio), shared with the CHM driver */
+/* MSCABD_PARAM_HIP_DIGESTS: the ratio rule, a file's units, the table of their answers and the digest() call's frame are host_digest.h's,
+ * shared with the CHM driver; this driver's own: the walk over the gathered folders' files with one byte sum over the whole batch */
 /* diagnostics (mspack.h: mspack_cabd_md5_counts, mspack_cabd_digest_counts): per algorithm, successful digest() calls answered from a
  * digest the batch took on the device / hashed on the host, over all decompressors of the process */
 static unsigned long long g_digest_counts[3][2];
@@ -991,26 +992,11 @@ static void batch_take_folder(struct cab_batch *B, size_t k)
       fp->total += res[k].in_next; fp->good_len = fp->total; fp->written = fp->total;
     }
     sys->free(fp->marks); fp->marks = NULL; fp->n_marks = 0; fp->mark_log = NULL;
-    sys->free(fp->md5s); fp->md5s = NULL; fp->n_md5s = 0; fp->md5_hint = 0;
-    if (gs[k].md_n && (fp->md5s = (struct file_md5 *) sys->alloc(sys, gs[k].md_n * sizeof(*fp->md5s)))) {
-      /* the digests the batch took of the folder's files: kept with the folder */
-      const size_t m0 = B->n + B->ck.n + gs[k].md_lo;
-      size_t j;
-      for (j = 0; j < gs[k].md_n; j++) {
-        const int kind = units[m0 + j].kind;
-        const int alg = kind == MSPACK_HIP_KIND_MD5 ? MSPACK_DIGEST_MD5 : kind == MSPACK_HIP_KIND_SHA1 ? MSPACK_DIGEST_SHA1 : MSPACK_DIGEST_SHA256;
-        if (kind == MSPACK_HIP_KIND_DIGEST_MORE || res[m0 + j].err != MSPACK_ERR_OK) continue;      /* (a tail: taken with its head) */
-        fp->md5s[fp->n_md5s].offset = (unsigned int)(units[m0 + j].out_off - units[k].out_off);
-        fp->md5s[fp->n_md5s].length = units[m0 + j].out_len;
-        fp->md5s[fp->n_md5s].alg = alg;
-        memset(fp->md5s[fp->n_md5s].d, 0, sizeof(fp->md5s[fp->n_md5s].d));
-        memcpy(fp->md5s[fp->n_md5s].d, &res[m0 + j].out_len, 16);
-        if (alg != MSPACK_DIGEST_MD5) {                       /* bytes 16 .. of a wide digest: in the next unit's result (mspack_hip.h) */
-          if (j + 1 >= gs[k].md_n || res[m0 + j + 1].err != MSPACK_ERR_OK) continue;
-          memcpy(fp->md5s[fp->n_md5s].d + 16, &res[m0 + j + 1].out_len, (size_t) digest_bytes(alg) - 16);
-        }
-        fp->n_md5s++;
-      }
+    sys->free(fp->dg.e); memset(&fp->dg, 0, sizeof(fp->dg));
+    if (gs[k].dg_n && (fp->dg.e = (struct digest_kept *) sys->alloc(sys, gs[k].dg_n * sizeof(*fp->dg.e)))) {
+      /* the digests the batch took of the folder's files: kept with the folder, by offset in it */
+      const size_t m0 = B->n + B->ck.n + gs[k].dg_lo;
+      digest_table_harvest(&fp->dg, units + m0, res + m0, gs[k].dg_n, units[k].out_off, 0);
     }
     if (units[k].flags & MSPACK_HIP_UF_QTM_MARKS) {
       fp->marks = gs[k].marks; fp->n_marks = gs[k].n_marks; gs[k].marks = NULL;
@@ -1051,16 +1037,9 @@ static int decode_cabinets(struct cabd_p *self, struct cab_p **cabs, size_t n_ca
   size_t kept = used;                                   /* what the folders this call decodes have taken of the budget */
   int err = MSPACK_ERR_OK, rc, again = 0;
   /* the algorithms the batch carries units for: asked for, the provider can (one without mspack_hip_features cannot), a ratio above 0 */
-  int dev_algs = 0, per_file = 0;
-  size_t md_cap = 0, nmd = 0;                           /* digest units: at most per_file per file of the gathered folders; those made */
-
+  const int dev_algs = digest_device_algs(self->hip_digests);
+  size_t dg_cap = 0, ndg = 0;                           /* digest units: at most digest_units_per_file per file of the gathered folders; those made */
   size_t n_qtm_files = 0;                               /* files in Quantum folders: two marks each at most (gather_marks) */
-  {
-    int alg;
-    dev_algs = digest_device_algs(self->hip_digests);
-    for (alg = MSPACK_DIGEST_MD5; alg <= MSPACK_DIGEST_SHA256; alg <<= 1)
-      if (dev_algs & alg) per_file += alg == MSPACK_DIGEST_MD5 ? 1 : 2;      /* (a wide digest: head and tail) */
-  }
   for (c = 0; c < n_cabs; c++) {
     struct mscabd_file *fi;
     for (fo = cabs[c]->base.folders; fo; fo = fo->next) { n++; ((struct folder_p *) fo)->file_count = 0; ((struct folder_p *) fo)->first_file = NULL; }
@@ -1100,23 +1079,23 @@ static int decode_cabinets(struct cabd_p *self, struct cab_p **cabs, size_t n_ca
     gs[n].n_marks = 0; gs[n].marks = NULL; gs[n].marks_off = 0;
     if ((fo->comp_type & 0x0F) == MSCAB_COMP_QUANTUM) gather_marks(sys, fp->data.cab, &gs[n], &A);
     used += est;
-    gs[n].md_lo = 0; gs[n].md_n = 0;
-    md_cap += (size_t) per_file * fp->file_count;
+    gs[n].dg_lo = 0; gs[n].dg_n = 0;
+    dg_cap += digest_units_per_file(dev_algs) * fp->file_count;
     n++;
   }
   if (!err && !arena_room(sys, &A, 64)) err = MSPACK_ERR_NOMEMORY;
   /* (a list that could not grow: the parts it holds are still verified with the batch, the others were verified while they were read) */
   nu = n + ck.n;
   if (!err) {
-    units = (mspack_hip_unit *) sys->alloc(sys, (nu + md_cap ? nu + md_cap : 1) * sizeof(*units));
-    res = (mspack_hip_result *) sys->alloc(sys, (nu + md_cap ? nu + md_cap : 1) * sizeof(*res));
+    units = (mspack_hip_unit *) sys->alloc(sys, (nu + dg_cap ? nu + dg_cap : 1) * sizeof(*units));
+    res = (mspack_hip_result *) sys->alloc(sys, (nu + dg_cap ? nu + dg_cap : 1) * sizeof(*res));
     if (!units || !res) err = MSPACK_ERR_NOMEMORY;
   }
   if (err) { for (k = 0; k < n; k++) { sys->free(gs[k].boff); sys->free(gs[k].marks); } sys->free(gs); sys->free(units); sys->free(res); sys->free(ck.p); mspack_arena_free(sys, A.p); return err; }
   memset(A.p + A.len, 0, 64);
 
   /* the units: where gather_folder put their input, one stretch of the output arena each */
-  memset(units, 0, (nu + md_cap) * sizeof(*units));
+  memset(units, 0, (nu + dg_cap) * sizeof(*units));
   for (k = 0; k < ck.n; k++) {                             /* the block parts' checksums (mspack_hip.h: MSPACK_HIP_KIND_XORSUM) */
     units[n + k].kind = MSPACK_HIP_KIND_XORSUM;
     units[n + k].in_off = ck.p[k].off; units[n + k].in_len = ck.p[k].len;
@@ -1145,37 +1124,29 @@ static int decode_cabinets(struct cabd_p *self, struct cab_p **cabs, size_t n_ca
       if (4 * (size_t) gs[k].n_marks + 16 > 32768) out_bytes += (4 * (size_t) gs[k].n_marks + 15) & ~(size_t) 15;
     }
   }
-  if (md_cap) {
-    /* per algorithm one digest unit (a wide one: with its tail behind it) per file that lies inside what its folder's blocks hold,
-     * beside the marks gather_marks collected; the long ones are left to the host (digest_ratio, per algorithm) */
-    double sum = 0.0;
+  if (dg_cap) {
+    /* the digest units (host_digest.h: digest_emit_file) of every file that lies inside what its folder's blocks hold, beside the
+     * marks gather_marks collected; the long ones are left to the host (digest_ratio, per algorithm, of the whole batch's bytes) */
+    double sum = 0.0, ratio[3];
     int pass;
+    digest_ratios(ratio);
     for (pass = 0; pass < 2; pass++)
       for (k = 0; k < n; k++) {
         struct folder_p *fp = gs[k].fol;
         struct mscabd_file *f;
         size_t i = 0;
         if (units[k].kind == 0) continue;
-        if (pass) gs[k].md_lo = nmd;
+        if (pass) gs[k].dg_lo = ndg;
         for (f = fp->first_file; f && i < fp->file_count; f = f->next) {
           if ((struct folder_p *) f->folder != fp) continue;
           i++;
           if (!f->length || f->offset > gs[k].total || f->length > gs[k].total - f->offset) continue;
-          if (!pass) { sum += (double) f->length; continue; }
-          {
-            int alg;
-            for (alg = MSPACK_DIGEST_MD5; alg <= MSPACK_DIGEST_SHA256; alg <<= 1) {
-              if (!(dev_algs & alg) || (double) f->length > digest_ratio(alg) * sum) continue;
-              units[nu + nmd].kind = digest_kind(alg);
-              units[nu + nmd].out_off = units[k].out_off + f->offset; units[nu + nmd].out_len = f->length;
-              nmd++;
-              if (alg != MSPACK_DIGEST_MD5) units[nu + nmd++].kind = MSPACK_HIP_KIND_DIGEST_MORE;
-            }
-          }
+          if (!pass) sum += (double) f->length;
+          else ndg += digest_emit_file(units[k].out_off + f->offset, f->length, sum, dev_algs, ratio, units + nu, ndg, dg_cap);
         }
-        if (pass) gs[k].md_n = nmd - gs[k].md_lo;
+        if (pass) gs[k].dg_n = ndg - gs[k].dg_lo;
       }
-    nu += nmd;
+    nu += ndg;
   }
   out_arena = (unsigned char *) mspack_arena_alloc(sys, out_bytes + 64);
   if (!out_arena) err = MSPACK_ERR_NOMEMORY;
@@ -1193,7 +1164,7 @@ static int decode_cabinets(struct cabd_p *self, struct cab_p **cabs, size_t n_ca
        * own folder only (folder_settle).  Everything the batch reads and writes belongs to it until then: struct cab_batch. */
       struct cab_batch *J = NULL;
       /* (digest units are through when the whole batch is: a batch that carries some is waited for here) */
-      if (n >= 2 && self->devices <= 1 && !nmd && (J = (struct cab_batch *) sys->alloc(sys, sizeof(*J)))) {
+      if (n >= 2 && self->devices <= 1 && !ndg && (J = (struct cab_batch *) sys->alloc(sys, sizeof(*J)))) {
         *J = B; J->pinned = pinned;
         if ((J->store = (struct out_store *) sys->alloc(sys, sizeof(*J->store)))) {
           J->store->base = out_arena; J->store->refs = 1;             /* (the batch's own hold on the arena) */
@@ -1328,17 +1299,6 @@ static unsigned int qtm_mark(const struct folder_p *fp, unsigned int pos)
   return (lo < fp->n_marks && fp->marks[lo] == pos) ? rd_le32(fp->mark_log + 4 * (size_t) lo) : 0;
 }
 
-/* the digest of algorithm alg the folder's batch took of the file at [offset, offset + length), or NULL */
-static const unsigned char *kept_md5(struct folder_p *fp, int alg, unsigned int offset, unsigned int length)
-{
-  unsigned int i, at = fp->md5_hint;
-  for (i = 0; i < fp->n_md5s; i++, at++) {
-    if (at >= fp->n_md5s) at = 0;
-    if (fp->md5s[at].offset == offset && fp->md5s[at].length == length && fp->md5s[at].alg == alg) { fp->md5_hint = at + 1; return fp->md5s[at].d; }
-  }
-  return NULL;
-}
-
 /* can the reference produce bytes [0, end) of this folder, and with which error if not? */
 static int folder_status(struct folder_p *fp, unsigned int end, int read_error, int *failed)
 {
@@ -1451,7 +1411,7 @@ static int cabd_extract(struct mscab_decompressor *base, struct mscabd_file *fil
     self->live_folder = fol; self->live_offset = 0; self->live_failed = 0; self->live_err = MSPACK_ERR_OK;
   }
 
-  if (self->sink) fh = MD5_SINK;
+  if (self->sink) fh = DIGEST_SINK;
   else if (!(fh = sys->open(sys, filename, MSPACK_SYS_OPEN_WRITE))) return self->error = MSPACK_ERR_OPEN;
   self->error = MSPACK_ERR_OK;
   /* What the codec would have said on the way: mszipd in repair mode reports every block it repairs when it decodes it
@@ -1515,7 +1475,7 @@ static int cabd_extract(struct mscab_decompressor *base, struct mscabd_file *fil
         }
         if (self->sink) {
           /* (mspack_cabd_digest: the whole file, good -- the digest the batch took of it if it did; else these bytes are hashed) */
-          if (!failed && have == filelen && (self->sink_kept = kept_md5(fol, self->sink->alg, file->offset, filelen)) != NULL) ;
+          if (!failed && have == filelen && (self->sink_kept = digest_table_find(&fol->dg, file->offset, filelen, self->sink->alg)) != NULL) ;
           else sink_update(self->sink, fol->dec + file->offset, have);
         }
         else if (write_slice(sys, fh, fol->dec + file->offset, have) != MSPACK_ERR_OK) err = MSPACK_ERR_WRITE;
@@ -1530,7 +1490,7 @@ static int cabd_extract(struct mscab_decompressor *base, struct mscabd_file *fil
     }
     else self->live_offset = file->offset + filelen;
   }
-  if (fh != MD5_SINK) sys->close(fh);
+  if (fh != DIGEST_SINK) sys->close(fh);
   return self->error;
 }
 
@@ -1539,38 +1499,21 @@ int mspack_cabd_digest(struct mscab_decompressor *base, struct mscabd_file *file
 {
   struct cabd_p *self = (struct cabd_p *) base;
   struct digest_sink k;
-  const int nd = digest_bytes(alg);
-  int err;
-  if (digest && nd && digest_cap >= (size_t) nd) memset(digest, 0, (size_t) nd);
+  int err = digest_call_args(file, alg, digest, digest_cap);
   if (!self) return MSPACK_ERR_ARGS;
-  if (!file || !digest || !nd || digest_cap < (size_t) nd) return self->error = MSPACK_ERR_ARGS;
+  if (err) return self->error = err;
   sink_init(&k, alg);
   self->sink = &k; self->sink_kept = NULL;
   err = cabd_extract(base, file, NULL);
   self->sink = NULL;
-  if (err == MSPACK_ERR_OK) {
-    if (self->sink_kept) memcpy(digest, self->sink_kept, (size_t) nd);
-    else sink_final(&k, digest);
-    __atomic_fetch_add(&g_digest_counts[digest_index(alg)][self->sink_kept ? 0 : 1], 1ull, __ATOMIC_RELAXED);
-  }
+  if (err == MSPACK_ERR_OK) digest_call_done(&k, self->sink_kept, digest, g_digest_counts);
   self->sink_kept = NULL;
   return err;
 }
 
-int mspack_cabd_md5(struct mscab_decompressor *base, struct mscabd_file *file, unsigned char digest[16])
-{
-  return mspack_cabd_digest(base, file, MSPACK_DIGEST_MD5, digest, 16);
-}
+int mspack_cabd_md5(struct mscab_decompressor *base, struct mscabd_file *file, unsigned char digest[16]) { return mspack_cabd_digest(base, file, MSPACK_DIGEST_MD5, digest, 16); }
 
-void mspack_cabd_digest_counts(int alg, unsigned long long counts[2], int reset)
-{
-  int i;
-  if (!digest_bytes(alg)) { if (counts) counts[0] = counts[1] = 0; return; }
-  for (i = 0; i < 2; i++) {
-    if (counts) counts[i] = __atomic_load_n(&g_digest_counts[digest_index(alg)][i], __ATOMIC_RELAXED);
-    if (reset) __atomic_store_n(&g_digest_counts[digest_index(alg)][i], 0ull, __ATOMIC_RELAXED);
-  }
-}
+void mspack_cabd_digest_counts(int alg, unsigned long long counts[2], int reset) { digest_counts_get(g_digest_counts, alg, counts, reset); }
 
 void mspack_cabd_md5_counts(unsigned long long counts[2], int reset) { mspack_cabd_digest_counts(MSPACK_DIGEST_MD5, counts, reset); }
 

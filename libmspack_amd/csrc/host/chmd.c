@@ -16,8 +16,9 @@
  * search inside a chunk, UTF-8 case-folded name order (chmd.c:543-898).
  * mspack_chmd_digest (mspack.h) is extract() with another sink: the same body, the slices hashed instead of written.  With
  * MSCHMD_PARAM_HIP_DIGESTS a chunk's batch also carries one digest unit per algorithm for every file that lies wholly inside the
- * chunk (host_digest.h: chm_digest_plan); their answers are kept with the chunk and used for calls that hand over exactly the
- * file's plain range.  A chunk batch that carries digest units is NOT run as a job -- digest units are through only when the whole
+ * chunk (host_digest.h: chm_digest_plan, over the emitter the cabinet driver uses); their answers are kept with the chunk in the
+ * table both drivers use (digest_table_harvest / digest_table_find) and answer the calls that hand over exactly the file's plain
+ * range.  A chunk batch that carries digest units is NOT run as a job -- digest units are through only when the whole
  * batch is (mspack_hip.h), the decision the cabinet driver takes in decode_cabinets -- so the first call into such a chunk
  * returns when every interval of it is decoded and its slowest digest lane has ended.
  */
@@ -43,11 +44,10 @@ struct chm_chunk {                /* a run of reset intervals decoded in one GPU
   mspack_hip_job *job;
   mspack_hip_unit *job_units;
   unsigned int job_waited;        /* units [0, job_waited) have come through                        */
-  /* MSCHMD_PARAM_HIP_DIGESTS: the digests the chunk's batches took of its files, ascending by (offset, length, alg); dg_algs: the
-   * algorithms a batch of this chunk has carried units for.  Kept when buf is evicted; freed with section 1 */
-  struct chm_dg *dg; size_t n_dg; int dg_algs;
+  /* MSCHMD_PARAM_HIP_DIGESTS: the digests the chunk's batches took of its files, by offset in the stream (host_digest.h: struct
+   * digest_table); dg_algs: the algorithms a batch of this chunk has carried units for.  Kept when buf is evicted; freed with section 1 */
+  struct digest_table dg; int dg_algs;
 };
-struct chm_dg { off_t offset, length; int alg, ok; unsigned char d[32]; };   /* alg: MSPACK_DIGEST_*; ok: the unit's result was MSPACK_ERR_OK; d: its 16, 20 or 32 bytes */
 struct chm_p {
   struct mschmd_header base;
   /* section 1 */
@@ -544,54 +544,17 @@ static int hip_batch(mspack_hip_unit *units, size_t n, const void *in, size_t in
                 : mspack_hip_decode_batch(units, n, in, in_bytes, out, out_bytes, res);
 }
 
-static int dg_order(const void *pa, const void *pb)
-{
-  const struct chm_dg *a = (const struct chm_dg *) pa, *b = (const struct chm_dg *) pb;
-  if (a->offset != b->offset) return a->offset < b->offset ? -1 : 1;
-  if (a->length != b->length) return a->length < b->length ? -1 : 1;
-  return a->alg - b->alg;
-}
-
 /* the digests a chunk's batch took (units[0 .. n): heads and tails, out_off counted from the chunk's first byte at stream offset
  * `lo`; res: their results) join the chunk's table.  Without memory for it they are dropped: those files are hashed on the host */
 static void chunk_keep_digests(struct mspack_system *sys, struct chm_chunk *ch, off_t lo, const mspack_hip_unit *units,
                                const mspack_hip_result *res, size_t n, int algs)
 {
-  struct chm_dg *t = (struct chm_dg *) sys->alloc(sys, (ch->n_dg + n) * sizeof(*t));
-  size_t j;
+  struct digest_kept *t = (struct digest_kept *) sys->alloc(sys, (ch->dg.n + n) * sizeof(*t));
   if (!t) return;
-  if (ch->n_dg) memcpy(t, ch->dg, ch->n_dg * sizeof(*t));
-  sys->free(ch->dg); ch->dg = t;
-  for (j = 0; j < n; j++) {
-    const uint8_t kind = units[j].kind;
-    struct chm_dg *e = &t[ch->n_dg];
-    if (kind == MSPACK_HIP_KIND_DIGEST_MORE) continue;                  /* (a tail: taken with its head) */
-    e->alg = kind == MSPACK_HIP_KIND_MD5 ? MSPACK_DIGEST_MD5 : kind == MSPACK_HIP_KIND_SHA1 ? MSPACK_DIGEST_SHA1 : MSPACK_DIGEST_SHA256;
-    e->offset = lo + (off_t) units[j].out_off; e->length = (off_t) units[j].out_len;
-    e->ok = res[j].err == MSPACK_ERR_OK;
-    memset(e->d, 0, sizeof(e->d));
-    memcpy(e->d, &res[j].out_len, 16);
-    /* bytes 16 .. of a wide digest: in the next unit's result (mspack_hip.h) */
-    if (e->alg != MSPACK_DIGEST_MD5 && j + 1 < n) memcpy(e->d + 16, &res[j + 1].out_len, (size_t) digest_bytes(e->alg) - 16);
-    ch->n_dg++;
-  }
+  if (ch->dg.n) memcpy(t, ch->dg.e, ch->dg.n * sizeof(*t));
+  sys->free(ch->dg.e); ch->dg.e = t;
+  digest_table_harvest(&ch->dg, units, res, n, 0, (uint64_t) lo);
   ch->dg_algs |= algs;
-  qsort(ch->dg, ch->n_dg, sizeof(*ch->dg), dg_order);
-}
-
-/* the digest of algorithm alg a batch of the chunk took of the file at [offset, offset + length), or NULL */
-static const unsigned char *chunk_digest(const struct chm_chunk *ch, off_t offset, off_t length, int alg)
-{
-  size_t lo = 0, hi = ch->n_dg;
-  struct chm_dg want;
-  want.offset = offset; want.length = length; want.alg = alg;
-  while (lo < hi) {
-    const size_t mid = lo + (hi - lo) / 2;
-    const int o = dg_order(&want, &ch->dg[mid]);
-    if (o == 0) return ch->dg[mid].ok ? ch->dg[mid].d : NULL;
-    if (o > 0) lo = mid + 1; else hi = mid;
-  }
-  return NULL;
 }
 
 /* decode intervals [first, first+count) stand-alone; interval i's E8 origin is i*interval - e8_origin.  dg_ch: the chunk these
@@ -609,8 +572,7 @@ static int decode_intervals(struct chmd_p *self, struct chm_p *c, unsigned int f
   unsigned int k;
   int rc;
   if (dg_algs) {
-    int alg;
-    for (alg = MSPACK_DIGEST_MD5; alg <= MSPACK_DIGEST_SHA256; alg <<= 1) ratio[digest_index(alg)] = digest_ratio(alg);
+    digest_ratios(ratio);
     n_dg = chm_digest_plan(c->dfiles, c->n_dfiles, (uint64_t) lo, (uint64_t)(lo + (off_t) count * c->interval_bytes),
                            (uint64_t) c->padded_len, dg_algs, ratio, NULL, 0);
   }
@@ -678,7 +640,7 @@ static int chunk_settle(struct mspack_system *sys, struct chm_chunk *ch)
 
 static void free_sec1(struct mspack_system *sys, struct chm_p *c) {
   unsigned int i;
-  if (c->chunks) for (i = 0; i < c->n_chunks; i++) { (void) chunk_settle(sys, &c->chunks[i]); mspack_arena_free(sys, c->chunks[i].buf); sys->free(c->chunks[i].dg); }
+  if (c->chunks) for (i = 0; i < c->n_chunks; i++) { (void) chunk_settle(sys, &c->chunks[i]); mspack_arena_free(sys, c->chunks[i].buf); sys->free(c->chunks[i].dg.e); }
   if (c->arena_pinned) { mspack_hip_unpin(c->arena); c->arena_pinned = 0; }
   sys->free(c->chunks); mspack_arena_free(sys, c->arena); sys->free(c->ioff); sys->free(c->ires); mspack_arena_free(sys, c->s_buf);
   sys->free(c->dfiles); c->dfiles = NULL; c->n_dfiles = 0;
@@ -855,7 +817,7 @@ static int setup_sec1(struct chmd_p *self, struct chm_p *c, struct mspack_file *
     for (i = 0; i < c->n_chunks; i++) {
       c->chunks[i].buf = NULL; c->chunks[i].stamp = 0; c->chunks[i].res_valid = 0;
       c->chunks[i].job = NULL; c->chunks[i].job_units = NULL; c->chunks[i].job_waited = 0;
-      c->chunks[i].dg = NULL; c->chunks[i].n_dg = 0; c->chunks[i].dg_algs = 0;
+      memset(&c->chunks[i].dg, 0, sizeof(c->chunks[i].dg)); c->chunks[i].dg_algs = 0;
     }
     if (!(c->ires = (mspack_hip_result *) sys->alloc(sys, (size_t) c->n_fast * sizeof(mspack_hip_result)))) return MSPACK_ERR_NOMEMORY;
     collect_dfiles(sys, c);
@@ -1096,7 +1058,7 @@ static int vdec_emit(struct chmd_p *self, struct chm_p *c, struct mspack_file *f
       if ((err = ensure_chunk_to(self, c, k, k1, 0, &ch))) return err;
       if (v->init != 0)
         for (i = k; i <= k1; i++) if (c->ires[i].flags & MSPACK_HIP_F_E8_APPLIED) shifted = 1;
-      if (!shifted && (self->sink_kept = chunk_digest(ch, from, to - from, self->sink->alg)) != NULL) return MSPACK_ERR_OK;
+      if (!shifted && (self->sink_kept = digest_table_find(&ch->dg, (uint64_t) from, (uint64_t)(to - from), self->sink->alg)) != NULL) return MSPACK_ERR_OK;
     }
   }
   while (from < to) {
@@ -1220,33 +1182,19 @@ int mspack_chmd_digest(struct mschm_decompressor *base, struct mschmd_file *file
 {
   struct chmd_p *self = (struct chmd_p *) base;
   struct digest_sink k;
-  const int nd = digest_bytes(alg);
-  int err;
-  if (digest && nd && digest_cap >= (size_t) nd) memset(digest, 0, (size_t) nd);
+  int err = digest_call_args(file, alg, digest, digest_cap);
   if (!self) return MSPACK_ERR_ARGS;
-  if (!file || !digest || !nd || digest_cap < (size_t) nd) return self->error = MSPACK_ERR_ARGS;
+  if (err) return self->error = err;
   sink_init(&k, alg);
   self->sink = &k; self->sink_whole = 0; self->sink_kept = NULL;
   err = chmd_extract(base, file, NULL);
   self->sink = NULL;
-  if (err == MSPACK_ERR_OK) {
-    if (self->sink_kept) memcpy(digest, self->sink_kept, (size_t) nd);
-    else sink_final(&k, digest);
-    __atomic_fetch_add(&g_digest_counts[digest_index(alg)][self->sink_kept ? 0 : 1], 1ull, __ATOMIC_RELAXED);
-  }
+  if (err == MSPACK_ERR_OK) digest_call_done(&k, self->sink_kept, digest, g_digest_counts);
   self->sink_whole = 0; self->sink_kept = NULL;
   return err;
 }
 
-void mspack_chmd_digest_counts(int alg, unsigned long long counts[2], int reset)
-{
-  int i;
-  if (!digest_bytes(alg)) { if (counts) counts[0] = counts[1] = 0; return; }
-  for (i = 0; i < 2; i++) {
-    if (counts) counts[i] = __atomic_load_n(&g_digest_counts[digest_index(alg)][i], __ATOMIC_RELAXED);
-    if (reset) __atomic_store_n(&g_digest_counts[digest_index(alg)][i], 0ull, __ATOMIC_RELAXED);
-  }
-}
+void mspack_chmd_digest_counts(int alg, unsigned long long counts[2], int reset) { digest_counts_get(g_digest_counts, alg, counts, reset); }
 
 int mspack_chmd_set_param(struct mschm_decompressor *base, int param, int value)
 {

@@ -1,7 +1,9 @@
-/* host_digest.h -- what the drivers' digest calls share (cabd.c: mspack_cabd_digest, chmd.c: mspack_chmd_digest): the hash in
- * progress on the host, an algorithm's length / feature bit / unit kind, the rule that decides which files are worth a digest
- * unit, and the CHM driver's planner of a chunk's digest units (a pure function: tests/csrc/chm_digest_plan_check.c includes this
- * header alone). */
+/* host_digest.h -- everything the drivers' digest calls share (cabd.c: mspack_cabd_digest, chmd.c: mspack_chmd_digest): the hash in
+ * progress on the host; an algorithm's length / feature bit / unit kind and back; the rule that decides which files are worth a
+ * digest unit; the emitter of one file's units (heads and MSPACK_HIP_KIND_DIGEST_MORE tails); the table of the digests a batch took,
+ * its harvest from the batch's results and its lookup; the frame of a digest() call and its counters; and the CHM driver's planner
+ * of a chunk's units.  All of it static inline over plain structs, the table and the planners pure functions:
+ * tests/csrc/digest_table_check.c and tests/csrc/chm_digest_plan_check.c include this header alone. */
 #ifndef MSPACK_AMD_HOST_DIGEST_H
 #define MSPACK_AMD_HOST_DIGEST_H
 #include <stdint.h>
@@ -34,6 +36,17 @@ static inline int digest_index(int alg) { return alg == MSPACK_DIGEST_MD5 ? 0 : 
 /* the feature bit and the unit kind of an algorithm */
 static inline unsigned digest_feat(int alg) { return alg == MSPACK_DIGEST_MD5 ? MSPACK_HIP_FEAT_MD5 : alg == MSPACK_DIGEST_SHA1 ? MSPACK_HIP_FEAT_SHA1 : MSPACK_HIP_FEAT_SHA256; }
 static inline uint8_t digest_kind(int alg) { return (uint8_t)(alg == MSPACK_DIGEST_MD5 ? MSPACK_HIP_KIND_MD5 : alg == MSPACK_DIGEST_SHA1 ? MSPACK_HIP_KIND_SHA1 : MSPACK_HIP_KIND_SHA256); }
+/* ... and back: the algorithm of a head's kind; 0 for every other kind (a tail's too) */
+static inline int digest_alg_of_kind(unsigned kind) { return kind == MSPACK_HIP_KIND_MD5 ? MSPACK_DIGEST_MD5 : kind == MSPACK_HIP_KIND_SHA1 ? MSPACK_DIGEST_SHA1 : kind == MSPACK_HIP_KIND_SHA256 ? MSPACK_DIGEST_SHA256 : 0; }
+/* a result has sixteen bytes to spare (mspack_hip.h): MD5 is one unit, a wide digest a head and its tail */
+static inline size_t digest_units(int alg) { return digest_bytes(alg) > 16 ? 2 : 1; }
+/* the units one file needs at most for the algorithms of the mask `algs` */
+static inline size_t digest_units_per_file(int algs)
+{
+  size_t n = 0; int alg;
+  for (alg = MSPACK_DIGEST_MD5; alg <= MSPACK_DIGEST_SHA256; alg <<= 1) if (algs & alg) n += digest_units(alg);
+  return n;
+}
 
 /* Which files get a digest unit.  The device hashes one range per LANE (MD5 is one chain per message), so
  * one lane is much slower than a host core and the pass takes as long as its longest range; the host hashes everything at its
@@ -76,13 +89,117 @@ static inline int digest_device_algs(int asked)
     if ((asked & alg) && mspack_hip_features && (mspack_hip_features() & digest_feat(alg)) && digest_ratio(alg) > 0.0) algs |= alg;
   return algs;
 }
+static inline void digest_ratios(double ratio[3]) { int alg; for (alg = MSPACK_DIGEST_MD5; alg <= MSPACK_DIGEST_SHA256; alg <<= 1) ratio[digest_index(alg)] = digest_ratio(alg); }
+
+/* ---- the digest units of one file --------------------------------------------------------------------------------------------------
+ * The file's bytes lie at [out_off, out_off + len) of the batch's output arena; `sum`: the bytes of all files of the batch that may
+ * get units.  Per algorithm of `algs` whose ratio[digest_index(alg)] x sum is not below len: the head (kind, out_off, out_len, every
+ * other field 0) and, for a wide digest, its tail (the kind alone) behind it, MD5 / SHA-1 / SHA-256 in that order.  Written to
+ * units[n ..) as far as they fit below `cap`, a head never without its tail (units == NULL: counts only).  Returns the units the
+ * file needs, fitting or not. */
+static inline size_t digest_emit_file(uint64_t out_off, uint32_t len, double sum, int algs, const double ratio[3],
+                                      mspack_hip_unit *units, size_t n, size_t cap)
+{
+  size_t made = 0; int alg;
+  for (alg = MSPACK_DIGEST_MD5; alg <= MSPACK_DIGEST_SHA256; alg <<= 1) {
+    const size_t need = digest_units(alg), at = n + made;
+    if (!(algs & alg) || (double) len > ratio[digest_index(alg)] * sum) continue;
+    if (units && at + need <= cap) {
+      memset(&units[at], 0, need * sizeof(*units));
+      units[at].kind = digest_kind(alg);
+      units[at].out_off = out_off; units[at].out_len = len;
+      if (need == 2) units[at + 1].kind = MSPACK_HIP_KIND_DIGEST_MORE;
+    }
+    made += need;
+  }
+  return made;
+}
+
+/* ---- the digests a batch took, kept ------------------------------------------------------------------------------------------------
+ * One record per head whose result -- and whose tail's -- came back MSPACK_ERR_OK, ascending by (offset, length, alg); d: the
+ * algorithm's 16, 20 or 32 bytes, zeros behind them.  The owner allocates e[]; sorts: how often a harvest found its records out
+ * of order and sorted (the planners emit ascending: normally never); next: the record behind the last one found. */
+struct digest_kept { uint64_t offset; uint32_t length; int alg; unsigned char d[32]; };
+struct digest_table { struct digest_kept *e; size_t n, next; unsigned sorts; };
+static inline int digest_kept_order(const void *pa, const void *pb)
+{
+  const struct digest_kept *a = (const struct digest_kept *) pa, *b = (const struct digest_kept *) pb;
+  if (a->offset != b->offset) return a->offset < b->offset ? -1 : 1;
+  if (a->length != b->length) return a->length < b->length ? -1 : 1;
+  return (a->alg > b->alg) - (a->alg < b->alg);
+}
+/* units[0 .. n) -- digest heads and tails -- and their results res[0 .. n) join the table, which has room for n more records; a
+ * record's offset is its head's out_off - out_base + base (the owner's origin instead of the output arena's).  Bytes 0 to 15 of a digest
+ * are the head's result from out_len on, bytes 16 .. of a wide one the NEXT unit's (mspack_hip.h): a wide head without one is dropped. */
+static inline void digest_table_harvest(struct digest_table *t, const mspack_hip_unit *units, const mspack_hip_result *res, size_t n,
+                                        uint64_t out_base, uint64_t base)
+{
+  size_t j; int ascending = 1;
+  for (j = 0; j < n; j++) {
+    const int alg = digest_alg_of_kind(units[j].kind), wide = alg && digest_units(alg) == 2;
+    struct digest_kept *e = &t->e[t->n];
+    if (!alg || res[j].err != MSPACK_ERR_OK) continue;            /* (a tail is taken with its head) */
+    if (wide && (j + 1 >= n || units[j + 1].kind != MSPACK_HIP_KIND_DIGEST_MORE || res[j + 1].err != MSPACK_ERR_OK)) continue;
+    e->offset = units[j].out_off - out_base + base; e->length = units[j].out_len; e->alg = alg;
+    memset(e->d, 0, sizeof(e->d));
+    memcpy(e->d, &res[j].out_len, 16);
+    if (wide) memcpy(e->d + 16, &res[j + 1].out_len, (size_t) digest_bytes(alg) - 16);
+    if (t->n && digest_kept_order(e - 1, e) > 0) ascending = 0;
+    t->n++;
+  }
+  if (!ascending) { qsort(t->e, t->n, sizeof(*t->e), digest_kept_order); t->sorts++; }
+}
+/* the digest of algorithm alg that was taken of the bytes [offset, offset + length), or NULL.  Files are mostly asked for in list
+ * order, one algorithm at a time: the record behind the last hit is looked at first, then a binary search */
+static inline const unsigned char *digest_table_find(struct digest_table *t, uint64_t offset, uint64_t length, int alg)
+{
+  size_t lo = 0, hi = t->n;
+  struct digest_kept want;
+  if (length > 0xFFFFFFFFu) return NULL;
+  want.offset = offset; want.length = (uint32_t) length; want.alg = alg;
+  if (t->next < t->n && !digest_kept_order(&want, &t->e[t->next])) return t->e[t->next++].d;
+  while (lo < hi) {
+    const size_t mid = lo + (hi - lo) / 2;
+    const int o = digest_kept_order(&want, &t->e[mid]);
+    if (o == 0) { t->next = mid + 1; return t->e[mid].d; }
+    if (o > 0) lo = mid + 1; else hi = mid;
+  }
+  return NULL;
+}
+
+/* ---- the frame of a digest() call (mspack.h) ---------------------------------------------------------------------------------------
+ * the arguments: a buffer that can hold the algorithm's bytes is zeroed, whatever else is wrong; MSPACK_ERR_ARGS for no file, an
+ * unknown algorithm, no buffer or one too small */
+static inline int digest_call_args(const void *file, int alg, unsigned char *digest, size_t digest_cap)
+{
+  const size_t nd = (size_t) digest_bytes(alg);
+  if (digest && nd && digest_cap >= nd) memset(digest, 0, nd); else return MSPACK_ERR_ARGS;
+  return file ? MSPACK_ERR_OK : MSPACK_ERR_ARGS;
+}
+/* a call that succeeded: the digest the batch took of the file (`kept`) or else the one hashed on the way, and the driver's counter
+ * of either -- counts[digest_index(alg)][0: from the device, 1: on the host], over all decompressors of the process */
+static inline void digest_call_done(struct digest_sink *k, const unsigned char *kept, unsigned char *digest, unsigned long long counts[3][2])
+{
+  if (kept) memcpy(digest, kept, (size_t) digest_bytes(k->alg)); else sink_final(k, digest);
+  __atomic_fetch_add(&counts[digest_index(k->alg)][kept ? 0 : 1], 1ull, __ATOMIC_RELAXED);
+}
+/* the *_digest_counts calls: the pair of one algorithm (an unknown one: zeros), optionally reset */
+static inline void digest_counts_get(unsigned long long counts[3][2], int alg, unsigned long long out[2], int reset)
+{
+  int i;
+  if (!digest_bytes(alg)) { if (out) out[0] = out[1] = 0; return; }
+  for (i = 0; i < 2; i++) {
+    if (out) out[i] = __atomic_load_n(&counts[digest_index(alg)][i], __ATOMIC_RELAXED);
+    if (reset) __atomic_store_n(&counts[digest_index(alg)][i], 0ull, __ATOMIC_RELAXED);
+  }
+}
 
 /* ---- CHM: the digest units of one chunk -------------------------------------------------------------------------------------------
  * files[0 .. n_files): the CHM's section-1 files with length > 0, ascending by offset.  The chunk decodes the stream's bytes
  * [chunk_lo, chunk_hi) into its output buffer from 0 on; the stream ends at padded_len.  Per algorithm of `algs` (a mask of
  * MSPACK_DIGEST_*) one unit -- a SHA head with its MSPACK_HIP_KIND_DIGEST_MORE tail behind it -- for every file that lies wholly in
  * [chunk_lo, min(chunk_hi, padded_len)) and is no longer than ratio[digest_index(alg)] x (the bytes of all such files), with
- * out_off = offset - chunk_lo and out_len = length; a file's algorithms next to each other, files in list order.  Files that
+ * out_off = offset - chunk_lo and out_len = length (digest_emit_file); a file's algorithms next to each other, files in list order.  Files that
  * cross a chunk boundary, reach past padded_len, have length 0 or are above the ratio get none.  Returns the number of units
  * (heads and tails); writes them to units[0 .. cap) as far as they fit (units == NULL: counts only). */
 struct chm_digest_file { uint64_t offset, length; };
@@ -92,7 +209,7 @@ static inline size_t chm_digest_plan(const struct chm_digest_file *files, size_t
   const uint64_t hi = chunk_hi < padded_len ? chunk_hi : padded_len;
   size_t lo_i = 0, hi_i = n_files, i, n = 0;
   double sum = 0.0;
-  int pass, alg;
+  int pass;
   if (!algs || hi <= chunk_lo) return 0;
   while (lo_i < hi_i) {                                   /* the first file at or behind chunk_lo */
     const size_t mid = lo_i + (hi_i - lo_i) / 2;
@@ -102,18 +219,8 @@ static inline size_t chm_digest_plan(const struct chm_digest_file *files, size_t
     for (i = lo_i; i < n_files && files[i].offset < hi; i++) {
       const uint64_t len = files[i].length;
       if (!len || len > hi - files[i].offset || len > 0xFFFFFFFFu) continue;
-      if (!pass) { sum += (double) len; continue; }
-      for (alg = MSPACK_DIGEST_MD5; alg <= MSPACK_DIGEST_SHA256; alg <<= 1) {
-        const size_t need = alg == MSPACK_DIGEST_MD5 ? 1 : 2;
-        if (!(algs & alg) || (double) len > ratio[digest_index(alg)] * sum) continue;
-        if (units && n + need <= cap) {
-          memset(&units[n], 0, need * sizeof(*units));
-          units[n].kind = digest_kind(alg);
-          units[n].out_off = files[i].offset - chunk_lo; units[n].out_len = (uint32_t) len;
-          if (need == 2) units[n + 1].kind = MSPACK_HIP_KIND_DIGEST_MORE;
-        }
-        n += need;
-      }
+      if (!pass) sum += (double) len;
+      else n += digest_emit_file(files[i].offset - chunk_lo, (uint32_t) len, sum, algs, ratio, units, n, cap);
     }
   return n;
 }

@@ -1,8 +1,11 @@
 """mspack_cabd_digest() (include/mspack.h): extract() with the writes replaced by a hash, by algorithm.  The driver on the CPU stand-in
 for the batch ABI, which has no feature word -- so every digest is the host fallback's (the plain-C SHA-1 / SHA-256 of
 csrc/host/sha.c, the MD5 of csrc/host/md5.c) whatever MSCABD_PARAM_HIP_DIGESTS says.  The reference for a digest is hashlib over what
-extract() of a second, fresh decompressor wrote; for codes it is that extract().  The device side is tests/test_gpu_sha.py's."""
+extract() of a second, fresh decompressor wrote; for codes it is that extract().  The device side is tests/test_gpu_sha.py's; here
+only the cabinet whose file list runs in descending offset order, on both: the folder's table of kept digests
+(csrc/host/host_digest.h) must answer every call from the device although its units arrive descending."""
 import hashlib
+import os
 
 import pytest
 
@@ -123,3 +126,51 @@ def test_host_fallback_is_counted_per_algorithm_cpu(built, hostlogic):
     assert api.cabd_digest_counts(api.MSPACK_DIGEST_SHA1, L=hostlogic) == (0, 1)
     assert api.cabd_digest_counts(api.MSPACK_DIGEST_MD5, L=hostlogic) == api.cabd_md5_counts(L=hostlogic) == (0, 0)
     assert api.cabd_digest_counts(3, L=hostlogic) == (0, 0)
+
+
+# ---- a file list in descending offset order: the folder's table of kept digests is made from units that arrive descending -----------------
+N_DESC, LEN_DESC = 32, 256
+
+_desc = []
+
+
+def descending_cabinet():
+    """one MSZIP folder of 32 files of 256 bytes, the file list in descending offset order -> (cabinet, [the files' bytes in list
+    order]).  Equal sizes: every file is 1/32 of the batch's digest bytes, below all three compiled ratios (0.10, 0.05, 0.04)"""
+    if not _desc:
+        import zlib
+        import libmspack_amd as M
+        data = M.gen_plaintext(11, 0, N_DESC * LEN_DESC).tobytes()
+        co = zlib.compressobj(6, zlib.DEFLATED, -15)
+        block = b"CK" + co.compress(data) + co.flush()
+        offs = [LEN_DESC * i for i in reversed(range(N_DESC))]
+        cab = M.cab_write([(1, [block], [len(data)])], [(b"f%02d.bin" % (o // LEN_DESC), LEN_DESC, o, 0) for o in offs])
+        _desc.append((cab, [data[o:o + LEN_DESC] for o in offs]))
+    return _desc[0]
+
+
+def digest_descending(L):
+    """digest() of every file and every algorithm in list order, against hashlib -> the counts per algorithm"""
+    assert 1.0 / N_DESC < 0.04
+    cab, want = descending_cabinet()
+    for alg in ALGS:
+        api.cabd_digest_counts(alg, reset=True, L=L)
+    with api.Cab(cab, mem=True, L=L) as c:
+        assert [(ln, off) for _n, ln, off, _ct in c.files] == [(LEN_DESC, LEN_DESC * i) for i in reversed(range(N_DESC))]
+        assert c.set_param(api.MSCABD_PARAM_HIP_DIGESTS, 7) == 0
+        for i in range(N_DESC):
+            for alg, h in ALGS.items():
+                assert c.digest(i, alg) == (0, h(want[i]).digest()), (i, alg)
+        assert not c.mem.outputs
+    return [api.cabd_digest_counts(alg, L=L) for alg in ALGS]
+
+
+def test_descending_file_list_host_fallback_cpu(built, hostlogic):
+    assert digest_descending(hostlogic) == [(0, N_DESC)] * 3
+
+
+@pytest.mark.gpu
+def test_descending_file_list_is_answered_from_the_device_gpu(built):
+    """all 96 calls are answered from the digests the batch took: the table sorts what the descending list made, and loses none"""
+    assert not any(os.environ.get(k) for k in ("MSPACK_HIP_MD5_RATIO", "MSPACK_HIP_SHA1_RATIO", "MSPACK_HIP_SHA256_RATIO"))
+    assert digest_descending(None) == [(N_DESC, 0)] * 3
