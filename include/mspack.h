@@ -354,6 +354,40 @@ extern int mspack_chmd_digest(struct mschm_decompressor *self, struct mschmd_fil
  * reading; an unknown alg: zeros */
 extern void mspack_chmd_digest_counts(int alg, unsigned long long counts[2], int reset);
 
+/* Gather the not-yet-decoded reset intervals of the given CHMs into ONE GPU batch, so that the extract() / mspack_chmd_digest()
+ * calls that follow are slices of it.  Advice: what every later extract(), fast_find() + extract() and mspack_chmd_digest() returns,
+ * writes, hashes and says through sys->message is the same with and without it -- the LZX decoder the reference keeps between
+ * calls, intervals decoded again for a shifted E8 origin, damaged or table-less streams (decoded serially) and files of section 0
+ * included.  The call itself says nothing through sys->message and opens no output file.
+ *
+ * Without it a CHM's compressed section is decoded by the first call that touches it, in batches of that CHM's intervals alone: a
+ * collection of thousands of small CHMs is then thousands of batches of two to ten units each.
+ *   chms[i]   CHMs this decompressor opened with open() or fast_open(); an entry given twice is harmless.
+ *   chunks    The CHMs are taken in argument order, within a CHM its chunks (up to 64 MiB of reset intervals) in stream order:
+ *             every chunk whose intervals have reset-table entries, except those that are decoded already or part of a batch that
+ *             is still running -- while the decoded bytes gathered by this call plus those the listed CHMs hold already fit
+ *             mspack_hip_cache_mb(), and while the batch's input (the CHMs' compressed sections behind one another) stays below
+ *             2^34 bytes.  Everything left out is decoded on demand as ever.
+ *   setup     A CHM whose compressed section has not been looked at gets that done here (ControlData, ResetTable, SpanInfo and
+ *             Content are read).  A CHM for which that fails is left exactly as it was -- no failure is remembered, nothing is said;
+ *             its next extract() does it again and reports as ever -- and does not make the call fail.
+ *   digests   MSCHMD_PARAM_HIP_DIGESTS is read here: when it is non-zero the batch carries the digest units of every gathered
+ *             chunk, kept with that chunk as after a chunk's own batch.
+ *   returns   MSPACK_ERR_OK (also for n_chms == 0, when nothing is left to decode and when every CHM was skipped: no batch is
+ *             started then); MSPACK_ERR_ARGS for self == NULL, n_chms < 0, chms == NULL with n_chms > 0 or a NULL entry (nothing
+ *             is gathered); MSPACK_ERR_NOMEMORY; MSPACK_ERR_DECRUNCH when the batch call itself failed ("GPU batch decode failed:
+ *             ..." is said then, and nothing of the batch is kept).  last_error() answers the same.
+ * With at least two intervals, one device (mspack_hip_default_devices() <= 1) and no digest units the batch runs as a job: the call
+ * returns at once and each later call waits only for the intervals it needs.  Otherwise -- also with MSPACK_HIP_JOBS=0 -- it returns
+ * when the batch is through.  A chunk's decoded bytes stay valid until that chunk leaves the cache or its CHM is closed, whatever
+ * happens to the other CHMs of the batch.  Closing a CHM while the batch runs takes its intervals out of it; the other CHMs' stay.
+ * mspack_destroy_chm_decompressor() settles a batch that is still running. */
+extern int mspack_chmd_prefetch(struct mschm_decompressor *self, struct mschmd_header **chms, int n_chms);
+/* diagnostics: the batch calls the CHM driver has issued in this process (counts[0]) and the interval units in them (counts[1]) --
+ * a chunk's own batch, a serial span, intervals decoded again for another E8 origin and a prefetch batch count alike; counts may be
+ * NULL; reset != 0 clears them after reading */
+extern void mspack_chmd_batch_counts(unsigned long long counts[2], int reset);
+
 /* ---- SZDD (reference mspack.h:1750-1790, 1876-1975) ------------------------------------------------------ */
 #define MSSZDD_FMT_NORMAL (0)
 #define MSSZDD_FMT_QBASIC (1)

@@ -137,6 +137,10 @@ def _setup(L=None):
     L.mspack_chmd_digest.argtypes = [_P(MschmDecompressor), _P(MschmdFile), C.c_int, C.c_void_p, C.c_size_t]
     L.mspack_chmd_digest_counts.restype = None
     L.mspack_chmd_digest_counts.argtypes = [C.c_int, C.c_void_p, C.c_int]
+    L.mspack_chmd_prefetch.restype = C.c_int
+    L.mspack_chmd_prefetch.argtypes = [_P(MschmDecompressor), _P(_P(MschmdHeader)), C.c_int]
+    L.mspack_chmd_batch_counts.restype = None
+    L.mspack_chmd_batch_counts.argtypes = [C.c_void_p, C.c_int]
     L.mspack_chmd_set_param.restype = C.c_int
     L.mspack_chmd_set_param.argtypes = [_P(MschmDecompressor), C.c_int, C.c_int]
     L.mspack_chmd_get_param.restype = C.c_int
@@ -164,6 +168,13 @@ def chmd_digest_counts(alg, reset=False, L=None):
     """mspack_chmd_digest_counts (mspack.h): successful Chm.digest() calls of algorithm alg answered (from a device digest, by the host)"""
     c = (C.c_ulonglong * 2)()
     _setup(L).mspack_chmd_digest_counts(int(alg), c, int(reset))
+    return int(c[0]), int(c[1])
+
+
+def chmd_batch_counts(reset=False, L=None):
+    """mspack_chmd_batch_counts (mspack.h): (batch calls the CHM driver has issued in this process, interval units in them)"""
+    c = (C.c_ulonglong * 2)()
+    _setup(L).mspack_chmd_batch_counts(c, int(reset))
     return int(c[0]), int(c[1])
 
 
@@ -579,6 +590,90 @@ class Chm:
             self.L.mspack_destroy_chm_decompressor(self.d); self.d = None
         if self._tmp:
             os.unlink(self._tmp); self._tmp = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+class ChmSet:
+    """Many CHM images opened on ONE decompressor and one in-memory mspack_system:
+    with ChmSet([blob1, blob2, ...]) as s: s.prefetch(); s.files(k); s.extract(k, i); s.digest(k, i, alg)"""
+
+    def __init__(self, blobs, L=None, fast=False):
+        self.L = _setup(L)
+        self.mem = MemSystem(self.L)
+        self.paths = []
+        for k, blob in enumerate(blobs):
+            self.mem.files[b"mem:in%d" % k] = bytes(blob)
+            self.paths.append(b"mem:in%d" % k)                # must outlive the CHMs: the driver keeps the pointer
+        self.d = self.L.mspack_create_chm_decompressor(self.mem.ptr())
+        if not self.d:
+            raise RuntimeError("mspack_create_chm_decompressor failed")
+        m = self.d.contents
+        self.chms, self.open_errors, self._files = [], [], []
+        for p in self.paths:
+            c = (m.fast_open if fast else m.open)(self.d, p)
+            self.chms.append(c)
+            self.open_errors.append(0 if c else m.last_error(self.d))
+            self._files.append(list(_walk(c.contents.files)) if c else [])
+
+    @property
+    def messages(self):
+        return self.mem.messages
+
+    def last_error(self):
+        return self.d.contents.last_error(self.d)
+
+    def set_param(self, param, value):
+        return self.L.mspack_chmd_set_param(self.d, param, value)
+
+    def prefetch(self, indices=None):
+        """mspack_chmd_prefetch (mspack.h): the not-yet-decoded reset intervals of these CHMs (indices into the list given to the
+        constructor; None = all that are open) in ONE batch -> MSPACK_ERR_*"""
+        if indices is None:
+            indices = [k for k, c in enumerate(self.chms) if c]
+        arr = (_P(MschmdHeader) * max(len(indices), 1))(*[self.chms[k] for k in indices])
+        return self.L.mspack_chmd_prefetch(self.d, arr, len(indices))
+
+    def files(self, k):
+        """[(name, length, offset, section)] of CHM k's list"""
+        return [(f.contents.filename, f.contents.length, f.contents.offset, f.contents.section.contents.id) for f in self._files[k]]
+
+    def extract(self, k, i):
+        self.mem.outputs.clear()
+        err = self.d.contents.extract(self.d, self._files[k][i], b"mem:out")
+        return err, bytes(self.mem.outputs.get(b"mem:out", b""))
+
+    def find(self, k, name):
+        f = MschmdFile()
+        err = self.d.contents.fast_find(self.d, self.chms[k], name, C.byref(f), C.sizeof(MschmdFile))
+        return err, (f if f.section else None)
+
+    def extract_found(self, f):
+        self.mem.outputs.clear()
+        err = self.d.contents.extract(self.d, C.pointer(f), b"mem:out")
+        return err, bytes(self.mem.outputs.get(b"mem:out", b""))
+
+    def digest(self, k, i, alg, cap=None):
+        """mspack_chmd_digest (mspack.h) of file i of CHM k -> (err, the digest bytes)"""
+        return _digest(self.L, self.d, self._files[k][i], alg, cap, fn=self.L.mspack_chmd_digest)
+
+    def close(self, k=None):
+        """close(k): CHM k alone; close(): every CHM that is still open, then the decompressor"""
+        if k is not None:
+            if self.d and self.chms[k]:
+                self.d.contents.close(self.d, self.chms[k])
+                self.chms[k] = None; self._files[k] = []
+            return
+        if self.d:
+            for j, c in enumerate(self.chms):
+                if c:
+                    self.d.contents.close(self.d, c)
+                    self.chms[j] = None; self._files[j] = []
+            self.L.mspack_destroy_chm_decompressor(self.d); self.d = None
 
     def __enter__(self):
         return self

@@ -38,6 +38,9 @@ def lib():
         L.mspk_api_bench_cabs_digest.argtypes = [C.c_void_p, C.c_void_p, C.c_uint, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_uint, C.POINTER(Stats)]
         L.mspk_api_bench_chm_digest.restype = C.c_int
         L.mspk_api_bench_chm_digest.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_uint, C.POINTER(Stats)]
+        L.mspk_api_bench_chms.restype = C.c_int
+        L.mspk_api_bench_chms.argtypes = [C.c_void_p, C.c_void_p, C.c_uint, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p,
+                                          C.c_uint, C.POINTER(Stats)]
         L.mspk_api_cab_run.restype = C.c_int
         L.mspk_api_cab_run.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]
@@ -127,6 +130,45 @@ def run_chm_digest(image, hip_digests, alg, max_files=65536, L=None):
     rc = L.mspk_api_bench_chm_digest(image.ctypes.data, image.size, int(hip_digests), int(alg), dg.ctypes.data, max_files, C.byref(st))
     n = min(st.n_files, max_files)
     return rc, [dg[32 * i:32 * i + nd].tobytes() for i in range(n)], {k: getattr(st, k) for k, _t in Stats._fields_}
+
+
+def run_chms(images, out_cap, prefetch, hip_digests=0, alg=0, max_files=65536, L=None):
+    """MANY CHM images on one decompressor (mspk_api_bench_chms): open all, [mspack_chmd_prefetch of all], then every file, CHM by
+    CHM -- extract() (alg 0) or mspack_chmd_digest(alg) with MSCHMD_PARAM_HIP_DIGESTS = hip_digests.
+    -> (rc, out uint8[bytes_out] or [digest bytes per file], stats dict; first_extract_s is the prefetch's time when there was one)"""
+    L = L or lib()
+    offs = np.zeros(len(images) + 1, dtype=np.uint64)
+    offs[1:] = np.cumsum([len(i) for i in images])
+    blob = np.frombuffer(b"".join(bytes(i) for i in images), dtype=np.uint8)
+    out = np.zeros((0 if alg else int(out_cap)) + 64, dtype=np.uint8)
+    dg = np.zeros(32 * (max_files if alg else 1), dtype=np.uint8)
+    st = Stats()
+    rc = L.mspk_api_bench_chms(blob.ctypes.data, offs.ctypes.data, len(images), int(bool(prefetch)), int(hip_digests), int(alg),
+                               out.ctypes.data, 0 if alg else int(out_cap), dg.ctypes.data, max_files, C.byref(st))
+    d = {k: getattr(st, k) for k, _t in Stats._fields_}
+    if alg:
+        nd = {1: 16, 2: 20, 4: 32}[alg]
+        return rc, [dg[32 * i:32 * i + nd].tobytes() for i in range(min(st.n_files, max_files))], d
+    return rc, out[:st.bytes_out], d
+
+
+def build_small_chms(M, n=1024, intervals=2, ub=65536, window_bits=16, n_files=4, seed=0xC4A5):
+    """n CHMs of `intervals` LZX reset intervals of ub bytes each (window 2^window_bits), n_files files of unequal length tiling each
+    one, in the
+    order of the directory.  -> ([image], [plaintext bytes], [[(offset, length)] per image])"""
+    fpu = ub // 32768
+    total = intervals * ub
+    images, plains, tables = [], [], []
+    for i in range(n):
+        d = M.gen_plaintext(seed + i, i % 3, total)
+        lz, fo = M.lzx_encode(d, window_bits, fpu, M.lzx_opts(mode=0, block_size=0, intel_filesize=0, e8_base=0))
+        rng = np.random.default_rng(seed + i)
+        cuts = [0] + sorted(int(c) for c in rng.choice(np.arange(1, total), size=n_files - 1, replace=False)) + [total]
+        files = [(b"/doc%02d.html" % k, cuts[k], cuts[k + 1] - cuts[k]) for k in range(n_files)]
+        images.append(M.chm_write(lz, fo, total, window_bits, fpu, files))
+        plains.append(bytes(d))
+        tables.append([(f[1], f[2]) for f in files])
+    return images, plains, tables
 
 
 def build_small_cabs(M, n=4096, ub=32768, plain=None):

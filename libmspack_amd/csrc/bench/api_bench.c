@@ -378,6 +378,67 @@ int mspk_api_bench_chm_digest(const unsigned char *chm, size_t chm_len, int hip_
   return 0;
 }
 
+/* MANY CHM images on ONE decompressor -- the help collection of small CHMs (tools/chm_prefetch_bench.py): open them all, then every
+ * file, CHM by CHM.  prefetch == 0: every CHM's first call decodes its own chunk; != 0: mspack_chmd_prefetch() of all of them first
+ * (its time is reported as first_extract_s).  alg == 0: extract() into `out`; else mspack_chmd_digest(alg) with
+ * MSCHMD_PARAM_HIP_DIGESTS = hip_digests, digests receiving 32 bytes per file in call order (at most max_files of them).
+ * images: the CHMs back to back, image k = [offs[k], offs[k + 1]). */
+int mspk_api_bench_chms(const unsigned char *images, const unsigned long long *offs, unsigned int n_chms, int prefetch, int hip_digests,
+                        int alg, unsigned char *out, size_t out_cap, unsigned char *digests, unsigned int max_files, mspk_api_stats *st)
+{
+  struct mem_sys ms;
+  struct mschm_decompressor *d;
+  struct mschmd_header **chms;
+  char (*names)[12];
+  unsigned int k;
+  double t0, t1;
+  int rc = 0;
+  memset(st, 0, sizeof(*st));
+  mem_sys_init(&ms, images, (size_t) offs[n_chms], alg ? NULL : out, alg ? 0 : out_cap);
+  ms.many_offs = offs; ms.n_many = n_chms;
+  chms = (struct mschmd_header **) calloc(n_chms ? n_chms : 1, sizeof(*chms));
+  names = (char (*)[12]) calloc(n_chms ? n_chms : 1, sizeof(*names));         /* (they must outlive the CHMs) */
+  if (!chms || !names) { free(chms); free(names); return -1; }
+  mspack_hip_host_path_stats(NULL, 1);
+  t0 = now_s();
+  if (!(d = mspack_create_chm_decompressor(&ms.sys))) { free(chms); free(names); return -1; }
+  if (mspack_chmd_set_param(d, MSCHMD_PARAM_HIP_DIGESTS, hip_digests)) rc = -4;
+  t1 = now_s();
+  for (k = 0; k < n_chms && !rc; k++) {
+    snprintf(names[k], sizeof(names[k]), "c%u", k);
+    if (!(chms[k] = d->open(d, names[k]))) { st->first_error = d->last_error(d); rc = -2; }
+  }
+  st->open_s = now_s() - t1;
+  if (!rc && prefetch) {
+    const double e0 = now_s();
+    const int err = mspack_chmd_prefetch(d, chms, (int) n_chms);
+    st->first_extract_s = now_s() - e0;
+    if (err) { st->first_error = err; rc = -3; }
+  }
+  for (k = 0; k < n_chms && !rc; k++) {
+    struct mschmd_file *f;
+    for (f = chms[k]->files; f; f = f->next) {
+      unsigned char dg[32];
+      const double e0 = now_s();
+      const int err = alg ? (memset(dg, 0, sizeof(dg)), mspack_chmd_digest(d, f, alg, dg, sizeof(dg))) : d->extract(d, f, "out");
+      if (st->n_files == 0 && !prefetch) st->first_extract_s = now_s() - e0;
+      if (err) { if (!st->n_errors) st->first_error = err; st->n_errors++; }
+      if (alg && digests && st->n_files < max_files) memcpy(digests + 32 * (size_t) st->n_files, dg, 32);
+      if (alg) st->bytes_out += (unsigned long long) f->length;
+      st->n_files++;
+    }
+  }
+  for (k = 0; k < n_chms; k++) if (chms[k]) d->close(d, chms[k]);
+  mspack_destroy_chm_decompressor(d);
+  {
+    const unsigned long long hashed = st->bytes_out;
+    finish(&ms, st, t0);
+    if (alg) st->bytes_out = hashed;        /* (nothing was written: the bytes the digests cover) */
+  }
+  free(chms); free(names);
+  return rc;
+}
+
 /* the files order[0..n) of one cabinet image extracted one after another with ONE decompressor (MSCABD_PARAM_FIXMSZIP /
  * _SALVAGE as given) -- the call sequence of oracle/ref_harness.c:refh_cab_extract, for the driver tests that compare error
  * codes, bytes and the MESSAGE LOG with the real reference's.  Every extract's bytes land at out_offs[i]; msgs receives the

@@ -21,6 +21,9 @@
  * range.  A chunk batch that carries digest units is NOT run as a job -- digest units are through only when the whole
  * batch is (mspack_hip.h), the decision the cabinet driver takes in decode_cabinets -- so the first call into such a chunk
  * returns when every interval of it is decoded and its slowest digest lane has ended.
+ * mspack_chmd_prefetch (mspack.h) forms ONE batch over the not-yet-decoded chunks of MANY CHMs before the first extract(): the units
+ * and the harvest are the ones a chunk's own batch uses (interval_units, chunk_keep_digests), the input is a copy of every CHM's
+ * arena behind one another, the output one buffer the chunks share (struct chm_batch).
  */
 #include <stdlib.h>
 #include <stdio.h>
@@ -47,6 +50,10 @@ struct chm_chunk {                /* a run of reset intervals decoded in one GPU
   /* MSCHMD_PARAM_HIP_DIGESTS: the digests the chunk's batches took of its files, by offset in the stream (host_digest.h: struct
    * digest_table); dg_algs: the algorithms a batch of this chunk has carried units for.  Kept when buf is evicted; freed with section 1 */
   struct digest_table dg; int dg_algs;
+  /* mspack_chmd_prefetch: the batch of many CHMs' chunks this one was decoded by (struct chm_batch) -- buf then lies in that batch's
+   * output buffer and is given back to it, not freed; pf_k: which of its members; pf_run: the batch still runs as a job and this
+   * chunk has not taken all of its units (job_waited counts them, as for `job`).  pf != NULL exactly while buf is the batch's */
+  struct chm_batch *pf; size_t pf_k; int pf_run;
 };
 struct chm_p {
   struct mschmd_header base;
@@ -75,6 +82,7 @@ struct chm_p {
   unsigned int s_log_n, s_log_cap;     /* the serial span's reset log (MSPACK_HIP_UF_LZX_LOG): frames, counted from s_init, whose
                                           reset found a block open; it lies in s_buf behind the span (s_log) */
   const unsigned char *s_log;
+  unsigned int pf_stamp;          /* mspack_chmd_prefetch: chmd_p.pf_stamp of the call that last saw this CHM (an entry given twice) */
 };
 struct vdec {                     /* the reference's lzxd instance, replayed (chmd.c:989-1040)       */
   int alive, mode, serial, seek_pending;   /* mode 0: created at a reset-table entry, 1: at offset 0 with SpanInfo */
@@ -96,9 +104,18 @@ struct chmd_p {
   struct digest_sink *sink;           /* mspack_chmd_digest is running: what extract() would write goes here instead of a file */
   int sink_whole;                     /* ... and the emit step hands over exactly the file's plain range, of a call that is good so far */
   const unsigned char *sink_kept;     /* ... and that file's digest was taken by its chunk's batch: this one */
+  struct chm_batch *batches;          /* mspack_chmd_prefetch: the batches that still run or whose output buffer still has users */
+  unsigned int pf_stamp;              /* ... one number per call */
 };
 /* per algorithm, successful mspack_chmd_digest() calls answered from a device digest / hashed on the host (mspack.h) */
 static unsigned long long g_digest_counts[3][2];
+/* batch calls this driver has issued, and the interval units in them (mspack.h: mspack_chmd_batch_counts) */
+static unsigned long long g_batch_counts[2];
+static void count_batch(size_t n_intervals)
+{
+  __atomic_fetch_add(&g_batch_counts[0], 1ull, __ATOMIC_RELAXED);
+  __atomic_fetch_add(&g_batch_counts[1], (unsigned long long) n_intervals, __ATOMIC_RELAXED);
+}
 
 static off_t read_encint(const unsigned char **p, const unsigned char *end, int *err) {
   off_t v = 0; unsigned char c = 0x80; int i = 0;
@@ -544,53 +561,54 @@ static int hip_batch(mspack_hip_unit *units, size_t n, const void *in, size_t in
                 : mspack_hip_decode_batch(units, n, in, in_bytes, out, out_bytes, res);
 }
 
-/* the digests a chunk's batch took (units[0 .. n): heads and tails, out_off counted from the chunk's first byte at stream offset
- * `lo`; res: their results) join the chunk's table.  Without memory for it they are dropped: those files are hashed on the host */
+/* the digests a chunk's batch took (units[0 .. n): heads and tails, out_off counted from out_base, where the batch's output holds
+ * the chunk's first byte -- stream offset `lo`; res: their results) join the chunk's table.  Without memory for it they are
+ * dropped: those files are hashed on the host */
 static void chunk_keep_digests(struct mspack_system *sys, struct chm_chunk *ch, off_t lo, const mspack_hip_unit *units,
-                               const mspack_hip_result *res, size_t n, int algs)
+                               const mspack_hip_result *res, size_t n, int algs, uint64_t out_base)
 {
   struct digest_kept *t = (struct digest_kept *) sys->alloc(sys, (ch->dg.n + n) * sizeof(*t));
   if (!t) return;
   if (ch->dg.n) memcpy(t, ch->dg.e, ch->dg.n * sizeof(*t));
   sys->free(ch->dg.e); ch->dg.e = t;
-  digest_table_harvest(&ch->dg, units, res, n, 0, (uint64_t) lo);
+  digest_table_harvest(&ch->dg, units, res, n, out_base, (uint64_t) lo);
   ch->dg_algs |= algs;
 }
 
-/* decode intervals [first, first+count) stand-alone; interval i's E8 origin is i*interval - e8_origin.  dg_ch: the chunk these
- * intervals are, when its files' digest units may ride in the batch (chm_digest_plan, behind the interval units) */
-static int decode_intervals(struct chmd_p *self, struct chm_p *c, unsigned int first, unsigned int count,
-                            off_t e8_origin, unsigned char *out, mspack_hip_result *res, struct chm_chunk *as_job, struct chm_chunk *dg_ch)
+/* the algorithms a batch that decodes chunk dg_ch (from stream offset lo on) carries digest units for: asked for, not taken yet */
+static int chunk_digest_algs(const struct chmd_p *self, const struct chm_p *c, off_t lo, const struct chm_chunk *dg_ch)
 {
-  struct mspack_system *sys = self->system;
+  return dg_ch && c->n_dfiles && c->padded_len > lo ? digest_device_algs(self->hip_digests & ~dg_ch->dg_algs) : 0;
+}
+/* ... and those units (chm_digest_plan) for intervals [first, first+count), their ranges counted from out_base of the batch's output;
+ * units == NULL: counts only */
+static size_t chunk_digest_units(const struct chm_p *c, unsigned int first, unsigned int count, int algs, const double ratio[3],
+                                 uint64_t out_base, mspack_hip_unit *units, size_t cap)
+{
   const off_t lo = (off_t) first * c->interval_bytes;
-  const int dg_algs = dg_ch && c->n_dfiles && c->padded_len > lo ? digest_device_algs(self->hip_digests & ~dg_ch->dg_algs) : 0;
-  double ratio[3] = { 0.0, 0.0, 0.0 };
-  size_t n_dg = 0;
-  mspack_hip_unit *units;
-  mspack_hip_result *res_all = NULL;      /* with digest units: the batch's results, the intervals' copied to res afterwards */
+  const size_t n = chm_digest_plan(c->dfiles, c->n_dfiles, (uint64_t) lo, (uint64_t)(lo + (off_t) count * c->interval_bytes),
+                                   (uint64_t) c->padded_len, algs, ratio, units, cap);
+  size_t j;
+  if (units && out_base) for (j = 0; j < n && j < cap; j++) if (units[j].kind != MSPACK_HIP_KIND_DIGEST_MORE) units[j].out_off += out_base;
+  return n;
+}
+
+/* the units of intervals [first, first+count) of c, stand-alone; interval i's E8 origin is i*interval - e8_origin.  The CHM's arena
+ * (the stream, its slack, its frame tables) lies at in_base of the batch's input arena -- a multiple of 16; 0: it IS the arena --,
+ * the intervals' output one behind the other from out_base of the batch's output on */
+static void interval_units(const struct chm_p *c, unsigned int first, unsigned int count, off_t e8_origin,
+                           uint64_t in_base, uint64_t out_base, mspack_hip_unit *units)
+{
   unsigned int k;
-  int rc;
-  if (dg_algs) {
-    digest_ratios(ratio);
-    n_dg = chm_digest_plan(c->dfiles, c->n_dfiles, (uint64_t) lo, (uint64_t)(lo + (off_t) count * c->interval_bytes),
-                           (uint64_t) c->padded_len, dg_algs, ratio, NULL, 0);
-  }
-  units = (mspack_hip_unit *) sys->alloc(sys, ((size_t) count + n_dg) * sizeof(*units));
-  if (!units) return MSPACK_ERR_NOMEMORY;
-  if (n_dg && !(res_all = (mspack_hip_result *) sys->alloc(sys, ((size_t) count + n_dg) * sizeof(*res_all)))) n_dg = 0;   /* (no memory: no units) */
   memset(units, 0, (size_t) count * sizeof(*units));
-  if (n_dg) {
-    (void) chm_digest_plan(c->dfiles, c->n_dfiles, (uint64_t) lo, (uint64_t)(lo + (off_t) count * c->interval_bytes),
-                           (uint64_t) c->padded_len, dg_algs, ratio, units + count, n_dg);
-    memset(res_all, 0, ((size_t) count + n_dg) * sizeof(*res_all));
-  }
   for (k = 0; k < count; k++) {
     uint64_t off = c->ioff[first + k];
     if (off > (uint64_t) c->arena_len) off = c->arena_len;        /* an entry beyond the file: nothing to read */
-    units[k].in_off = off;
+    units[k].in_off = in_base + off;
+    /* (what is left of THIS CHM's bytes, wherever its arena lies: a stream cut short ends in the reference's two zero bytes and
+     *  MSPACK_ERR_READ, readbits.h:192-214, not in what the batch holds behind it) */
     units[k].in_len = (uint32_t)((uint64_t) c->arena_len - off > 0xFFFFFFF0u ? 0xFFFFFFF0u : (uint64_t) c->arena_len - off);
-    units[k].out_off = (uint64_t) k * (uint64_t) c->interval_bytes;
+    units[k].out_off = out_base + (uint64_t) k * (uint64_t) c->interval_bytes;
     units[k].out_len = (uint32_t) c->interval_bytes;
     {
       /* the stream ends where the (padded) UncompLen says: an interval that holds the end is as long as what is left of it --
@@ -605,9 +623,37 @@ static int decode_intervals(struct chmd_p *self, struct chm_p *c, unsigned int f
     units[k].e8_base = (int32_t)((off_t)(first + k) * c->interval_bytes - e8_origin);
     if (c->ftab_off) {
       units[k].flags |= MSPACK_HIP_UF_FRAME_TABLE;
-      units[k].in_chunk = (uint32_t)((c->ftab_off + (size_t)(first + k) * c->fper * 4) / 4);
+      units[k].in_chunk = (uint32_t)((in_base + c->ftab_off + (uint64_t)(first + k) * c->fper * 4) / 4);
     }
   }
+}
+
+/* decode intervals [first, first+count) stand-alone (interval_units).  dg_ch: the chunk these
+ * intervals are, when its files' digest units may ride in the batch (chm_digest_plan, behind the interval units) */
+static int decode_intervals(struct chmd_p *self, struct chm_p *c, unsigned int first, unsigned int count,
+                            off_t e8_origin, unsigned char *out, mspack_hip_result *res, struct chm_chunk *as_job, struct chm_chunk *dg_ch)
+{
+  struct mspack_system *sys = self->system;
+  const off_t lo = (off_t) first * c->interval_bytes;
+  const int dg_algs = chunk_digest_algs(self, c, lo, dg_ch);
+  double ratio[3] = { 0.0, 0.0, 0.0 };
+  size_t n_dg = 0;
+  mspack_hip_unit *units;
+  mspack_hip_result *res_all = NULL;      /* with digest units: the batch's results, the intervals' copied to res afterwards */
+  int rc;
+  if (dg_algs) {
+    digest_ratios(ratio);
+    n_dg = chunk_digest_units(c, first, count, dg_algs, ratio, 0, NULL, 0);
+  }
+  units = (mspack_hip_unit *) sys->alloc(sys, ((size_t) count + n_dg) * sizeof(*units));
+  if (!units) return MSPACK_ERR_NOMEMORY;
+  if (n_dg && !(res_all = (mspack_hip_result *) sys->alloc(sys, ((size_t) count + n_dg) * sizeof(*res_all)))) n_dg = 0;   /* (no memory: no units) */
+  interval_units(c, first, count, e8_origin, 0, 0, units);
+  if (n_dg) {
+    (void) chunk_digest_units(c, first, count, dg_algs, ratio, 0, units + count, n_dg);
+    memset(res_all, 0, ((size_t) count + n_dg) * sizeof(*res_all));
+  }
+  count_batch(count);
   /* a chunk's batch runs as a job when it can: extract() of the first file returns when the file's intervals are through,
    * and the caller writes it while the rest is decoded and copied back (one device: a sharded batch is synchronous) */
   /* (digest units are through when the whole batch is: a batch that carries some is waited for here) */
@@ -619,11 +665,87 @@ static int decode_intervals(struct chmd_p *self, struct chm_p *c, unsigned int f
   rc = hip_batch(units, (size_t) count + n_dg, c->arena, c->arena_room, out, (size_t) count * (size_t) c->interval_bytes + 64, n_dg ? res_all : res);
   if (n_dg && !rc) {
     memcpy(res, res_all, (size_t) count * sizeof(*res));
-    chunk_keep_digests(sys, dg_ch, lo, units + count, res_all + count, n_dg, dg_algs);
+    chunk_keep_digests(sys, dg_ch, lo, units + count, res_all + count, n_dg, dg_algs, 0);
   }
   sys->free(units); sys->free(res_all);
   if (rc) { sys->message(NULL, "GPU batch decode failed: %s", mspack_hip_last_error()); return MSPACK_ERR_DECRUNCH; }
   return MSPACK_ERR_OK;
+}
+
+/* ---- one batch over the chunks of many CHMs (mspack_chmd_prefetch) ----
+ * The batch owns what it reads -- the units, and an input arena that holds a copy of every CHM's arena, so that none of it points
+ * into a CHM -- and what it writes: the results, and ONE output buffer that the chunks share.  A member chunk's buf points into
+ * that buffer (no copy per chunk); the buffer goes when its last user has gone (users), whatever happens to the other CHMs.  While
+ * the batch runs as a job, `left` members have not taken all of their units yet; the last one out ends the job, and units, results
+ * and the input arena go then.  The decompressor keeps the list (chmd_p.batches) so that destroying it can settle them. */
+struct chm_member {
+  struct chm_chunk *ch;               /* NULL: the chunk has left (evicted, its CHM closed) */
+  mspack_hip_result *ires;            /* where the results of its intervals go: its CHM's ires[] from the chunk's first interval on */
+  size_t u0; unsigned int count;      /* its intervals are units [u0, u0 + count) */
+};
+struct chm_batch {
+  struct chm_batch *next; struct chmd_p *owner;
+  struct chm_member *m; size_t n, users, left;
+  mspack_hip_unit *units; mspack_hip_result *res; unsigned char *in, *out; int in_pinned;
+  mspack_hip_job *job;
+};
+
+/* the job, if there is one, to its end, and everything only the running batch needs given back (0, or the batch's failure) */
+static int batch_end_job(struct mspack_system *sys, struct chm_batch *B)
+{
+  int rc = 0;
+  if (B->job) { rc = mspack_hip_job_end(B->job); B->job = NULL; }
+  if (B->in_pinned) { mspack_hip_unpin(B->in); B->in_pinned = 0; }
+  sys->free(B->units); sys->free(B->res); mspack_arena_free(sys, B->in);
+  B->units = NULL; B->res = NULL; B->in = NULL;
+  return rc;
+}
+static void batch_free(struct mspack_system *sys, struct chm_batch *B)
+{
+  struct chm_batch **at;
+  (void) batch_end_job(sys, B);
+  for (at = &B->owner->batches; *at; at = &(*at)->next) if (*at == B) { *at = B->next; break; }
+  mspack_arena_free(sys, B->out); sys->free(B->m); sys->free(B);
+}
+/* a chunk that no longer runs in the batch and no longer uses its buffer: the last one out frees it */
+static void chunk_leave_batch(struct mspack_system *sys, struct chm_chunk *ch)
+{
+  struct chm_batch *B = ch->pf;
+  B->m[ch->pf_k].ch = NULL; ch->pf = NULL;
+  if (--B->users == 0) batch_free(sys, B);
+}
+/* a chunk stops waiting for the running batch (its units are through, or nobody will ask: eviction, close); the batch goes on for
+ * the others.  Returns the job's answer when this was the last one it ran for, else 0 */
+static int chunk_detach(struct mspack_system *sys, struct chm_chunk *ch)
+{
+  struct chm_batch *B = ch->pf;
+  int rc = 0;
+  ch->pf_run = 0;
+  if (--B->left == 0) rc = batch_end_job(sys, B);
+  return rc;
+}
+/* the chunk's decoded bytes go: its own buffer is freed, a share of a batch's buffer is given back */
+static void chunk_drop_buf(struct mspack_system *sys, struct chm_chunk *ch)
+{
+  if (ch->pf) {
+    if (ch->pf_run) (void) chunk_detach(sys, ch);
+    ch->buf = NULL;
+    chunk_leave_batch(sys, ch);
+  }
+  else { mspack_arena_free(sys, ch->buf); ch->buf = NULL; }
+}
+
+/* unit i of the chunk's running batch (its own job, or the batch of many CHMs: the result goes to ires[] then) */
+static int chunk_wait_unit(struct chm_chunk *ch, unsigned int i)
+{
+  if (ch->job) return mspack_hip_job_wait_unit(ch->job, i);
+  {
+    struct chm_batch *B = ch->pf;
+    const struct chm_member *m = &B->m[ch->pf_k];
+    const int rc = mspack_hip_job_wait_unit(B->job, m->u0 + i);
+    if (!rc) m->ires[i] = B->res[m->u0 + i];
+    return rc;
+  }
 }
 
 /* the chunk's batch, if it is still running, to its end: buf and ires[] are the driver's again (0, or the batch's failure) */
@@ -635,12 +757,21 @@ static int chunk_settle(struct mspack_system *sys, struct chm_chunk *ch)
     ch->job = NULL;
     sys->free(ch->job_units); ch->job_units = NULL;
   }
+  else if (ch->pf_run) {
+    /* (a batch of many CHMs: to the end of THIS chunk's units) */
+    const unsigned int count = ch->pf->m[ch->pf_k].count;
+    int rc2;
+    while (!rc && ch->job_waited < count) if (!(rc = chunk_wait_unit(ch, ch->job_waited))) ch->job_waited++;
+    rc2 = chunk_detach(sys, ch);
+    if (!rc) rc = rc2;
+  }
   return rc;
 }
 
 static void free_sec1(struct mspack_system *sys, struct chm_p *c) {
   unsigned int i;
-  if (c->chunks) for (i = 0; i < c->n_chunks; i++) { (void) chunk_settle(sys, &c->chunks[i]); mspack_arena_free(sys, c->chunks[i].buf); sys->free(c->chunks[i].dg.e); }
+  /* (a chunk of a running batch of many CHMs is taken out of it unwaited, chunk_drop_buf: the batch goes on for the others) */
+  if (c->chunks) for (i = 0; i < c->n_chunks; i++) { if (c->chunks[i].job) (void) chunk_settle(sys, &c->chunks[i]); chunk_drop_buf(sys, &c->chunks[i]); sys->free(c->chunks[i].dg.e); }
   if (c->arena_pinned) { mspack_hip_unpin(c->arena); c->arena_pinned = 0; }
   sys->free(c->chunks); mspack_arena_free(sys, c->arena); sys->free(c->ioff); sys->free(c->ires); mspack_arena_free(sys, c->s_buf);
   sys->free(c->dfiles); c->dfiles = NULL; c->n_dfiles = 0;
@@ -818,6 +949,7 @@ static int setup_sec1(struct chmd_p *self, struct chm_p *c, struct mspack_file *
       c->chunks[i].buf = NULL; c->chunks[i].stamp = 0; c->chunks[i].res_valid = 0;
       c->chunks[i].job = NULL; c->chunks[i].job_units = NULL; c->chunks[i].job_waited = 0;
       memset(&c->chunks[i].dg, 0, sizeof(c->chunks[i].dg)); c->chunks[i].dg_algs = 0;
+      c->chunks[i].pf = NULL; c->chunks[i].pf_k = 0; c->chunks[i].pf_run = 0;
     }
     if (!(c->ires = (mspack_hip_result *) sys->alloc(sys, (size_t) c->n_fast * sizeof(mspack_hip_result)))) return MSPACK_ERR_NOMEMORY;
     collect_dfiles(sys, c);
@@ -830,21 +962,21 @@ static int chunk_wait(struct chmd_p *self, struct chm_chunk *ch, unsigned int fi
 {
   struct mspack_system *sys = self->system;
   unsigned int upto = k_to - first + 1;
-  if (!ch->job) return MSPACK_ERR_OK;
+  if (!ch->job && !ch->pf_run) return MSPACK_ERR_OK;
   if (upto > count) upto = count;
   while (ch->job_waited < upto) {
-    if (mspack_hip_job_wait_unit(ch->job, ch->job_waited)) {
+    if (chunk_wait_unit(ch, ch->job_waited)) {
       /* the batch failed: what decode_intervals says of a failed call -- nothing of the chunk is kept */
       (void) chunk_settle(sys, ch);
       sys->message(NULL, "GPU batch decode failed: %s", mspack_hip_last_error());
-      mspack_arena_free(sys, ch->buf); ch->buf = NULL; ch->res_valid = 0;
+      chunk_drop_buf(sys, ch); ch->res_valid = 0;
       return MSPACK_ERR_DECRUNCH;
     }
     ch->job_waited++;
   }
   if (ch->job_waited >= count && chunk_settle(sys, ch)) {
     sys->message(NULL, "GPU batch decode failed: %s", mspack_hip_last_error());
-    mspack_arena_free(sys, ch->buf); ch->buf = NULL; ch->res_valid = 0;
+    chunk_drop_buf(sys, ch); ch->res_valid = 0;
     return MSPACK_ERR_DECRUNCH;
   }
   return MSPACK_ERR_OK;
@@ -870,7 +1002,7 @@ static int ensure_chunk_to(struct chmd_p *self, struct chm_p *c, unsigned int k,
         if (c->chunks[i].buf) { used += each; if (&c->chunks[i] != ch && (!lru || c->chunks[i].stamp < lru->stamp)) lru = &c->chunks[i]; }
       if (used + each <= budget || !lru) break;
       if (chunk_settle(sys, lru)) lru->res_valid = 0;      /* (a batch that failed behind what was asked of it: decoded again when needed) */
-      mspack_arena_free(sys, lru->buf); lru->buf = NULL;
+      chunk_drop_buf(sys, lru);
     }
   }
   if (!(ch->buf = (unsigned char *) mspack_arena_alloc(sys, (size_t) count * (size_t) c->interval_bytes + 128))) return MSPACK_ERR_NOMEMORY;
@@ -922,6 +1054,7 @@ static int ensure_serial(struct chmd_p *self, struct chm_p *c, off_t need)
   u.kind = MSPACK_HIP_KIND_LZX; u.window_bits = (uint8_t) c->window_bits; u.reset_frames = (uint16_t) c->fper;
   u.e8_base = 0;
   u.flags = MSPACK_HIP_UF_LZX_LOG; u.ref_len = log_cap;
+  count_batch(1);
   if (mspack_hip_decode_batch(&u, 1, c->arena, c->arena_len + 64, c->s_buf, log_off + 4 + 4 * (size_t) log_cap + 64, &c->s_res)) {
     sys->message(NULL, "GPU batch decode failed: %s", mspack_hip_last_error());
     return MSPACK_ERR_DECRUNCH;
@@ -1196,6 +1329,164 @@ int mspack_chmd_digest(struct mschm_decompressor *base, struct mschmd_file *file
 
 void mspack_chmd_digest_counts(int alg, unsigned long long counts[2], int reset) { digest_counts_get(g_digest_counts, alg, counts, reset); }
 
+void mspack_chmd_batch_counts(unsigned long long counts[2], int reset)
+{
+  int i;
+  for (i = 0; i < 2; i++) {
+    if (counts) counts[i] = __atomic_load_n(&g_batch_counts[i], __ATOMIC_RELAXED);
+    if (reset) __atomic_store_n(&g_batch_counts[i], 0ull, __ATOMIC_RELAXED);
+  }
+}
+
+/* ---- mspack_chmd_prefetch (mspack.h) ---------------------------------------------------------------------------------------------- */
+/* section 1 of a CHM that has not had it, for the prefetch: what extract() does first, but a CHM whose setup fails is left as it
+ * was -- no failure is cached, its next extract() sets it up again and reports.  (setup_sec1 and what it calls say nothing through
+ * sys->message; the directory chunks and system-file entries it looked up stay cached, as after any fast_find().) */
+static void prefetch_setup(struct chmd_p *self, struct chm_p *c)
+{
+  struct mspack_system *sys = self->system;
+  struct mspack_file *fh = sys->open(sys, c->base.filename, MSPACK_SYS_OPEN_READ);
+  if (!fh) return;
+  if (setup_sec1(self, c, fh)) free_sec1(sys, c); else c->sec1_state = 1;
+  sys->close(fh);
+}
+
+struct pf_pick { struct chm_p *c; struct chm_chunk *ch; unsigned int first, count; uint64_t in_base, out_base; int dg_algs; size_t dg_n; };
+
+int mspack_chmd_prefetch(struct mschm_decompressor *base, struct mschmd_header **chms, int n_chms)
+{
+  struct chmd_p *self = (struct chmd_p *) base;
+  struct mspack_system *sys;
+  struct chm_p **list;
+  struct pf_pick *pk = NULL;
+  struct chm_batch *B = NULL;
+  const uint64_t in_limit = (uint64_t) 1 << 34;             /* what in_chunk * 4 can address */
+  uint64_t in_total = 0, out_total = 0;
+  size_t budget, used = 0, n_list = 0, cap = 0, n = 0, n_units = 0, n_dg = 0, k, l;
+  double ratio[3] = { 0.0, 0.0, 0.0 };
+  int i, err = MSPACK_ERR_OK, stop = 0, as_job, rc;
+  if (!self) return MSPACK_ERR_ARGS;
+  if (n_chms < 0 || (n_chms > 0 && !chms)) return self->error = MSPACK_ERR_ARGS;
+  for (i = 0; i < n_chms; i++) if (!chms[i]) return self->error = MSPACK_ERR_ARGS;
+  if (n_chms == 0) return self->error = MSPACK_ERR_OK;
+  sys = self->system;
+  budget = (size_t) mspack_hip_cache_mb() << 20;
+  if (!(list = (struct chm_p **) sys->alloc(sys, (size_t) n_chms * sizeof(*list)))) return self->error = MSPACK_ERR_NOMEMORY;
+  /* every CHM once, section 1 set up; the decoded bytes they hold already count against the budget */
+  if (!++self->pf_stamp) ++self->pf_stamp;
+  for (i = 0; i < n_chms; i++) {
+    struct chm_p *c = (struct chm_p *) chms[i];
+    unsigned int ci;
+    if (c->pf_stamp == self->pf_stamp) continue;
+    c->pf_stamp = self->pf_stamp;
+    if (c->sec1_state == 0) prefetch_setup(self, c);
+    if (c->sec1_state != 1) continue;                       /* (a failure extract() has cached already, or found just now: skipped) */
+    for (ci = 0; ci < c->n_chunks; ci++) {
+      const unsigned int first = ci * c->chunk_int, count = (first + c->chunk_int <= c->n_fast) ? c->chunk_int : c->n_fast - first;
+      if (c->chunks[ci].buf) used += (size_t) count * (size_t) c->interval_bytes;
+    }
+    cap += c->n_chunks;
+    list[n_list++] = c;
+  }
+  if (cap && !(pk = (struct pf_pick *) sys->alloc(sys, cap * sizeof(*pk)))) { sys->free(list); return self->error = MSPACK_ERR_NOMEMORY; }
+  /* the chunks: argument order, chunk order, while they fit the budget and the input arena stays addressable */
+  if (self->hip_digests) digest_ratios(ratio);
+  for (l = 0; l < n_list && !stop; l++) {
+    struct chm_p *c = list[l];
+    const uint64_t piece = ((uint64_t) c->arena_room + 15) & ~(uint64_t) 15;
+    uint64_t in_base = 0;
+    unsigned int ci;
+    int placed = 0;
+    for (ci = 0; ci < c->n_chunks; ci++) {
+      struct chm_chunk *ch = &c->chunks[ci];
+      const unsigned int first = ci * c->chunk_int, count = (first + c->chunk_int <= c->n_fast) ? c->chunk_int : c->n_fast - first;
+      const size_t bytes = (size_t) count * (size_t) c->interval_bytes;
+      if (ch->buf || ch->res_valid || ch->job || ch->pf) continue;      /* decoded already, or part of a batch that still runs */
+      if (used + bytes > budget) { stop = 1; break; }
+      if (!placed) {
+        if (in_total + piece + 64 > in_limit) { stop = 1; break; }
+        in_base = in_total; in_total += piece; placed = 1;
+      }
+      pk[n].c = c; pk[n].ch = ch; pk[n].first = first; pk[n].count = count; pk[n].in_base = in_base; pk[n].out_base = out_total;
+      pk[n].dg_algs = chunk_digest_algs(self, c, (off_t) first * c->interval_bytes, ch);
+      pk[n].dg_n = pk[n].dg_algs ? chunk_digest_units(c, first, count, pk[n].dg_algs, ratio, 0, NULL, 0) : 0;
+      out_total += ((uint64_t) bytes + 63) & ~(uint64_t) 63;
+      n_units += count; n_dg += pk[n].dg_n; used += bytes;
+      n++;
+    }
+  }
+  if (!n) { sys->free(pk); sys->free(list); return self->error = MSPACK_ERR_OK; }      /* nothing left to decode: no batch */
+
+  if ((B = (struct chm_batch *) sys->alloc(sys, sizeof(*B)))) {
+    memset(B, 0, sizeof(*B));
+    B->owner = self; B->n = n;
+    B->m = (struct chm_member *) sys->alloc(sys, n * sizeof(*B->m));
+    B->units = (mspack_hip_unit *) sys->alloc(sys, (n_units + n_dg) * sizeof(*B->units));
+    B->res = (mspack_hip_result *) sys->alloc(sys, (n_units + n_dg) * sizeof(*B->res));
+    B->in = (unsigned char *) mspack_arena_alloc(sys, (size_t) in_total + 64);
+    B->out = (unsigned char *) mspack_arena_alloc(sys, (size_t) out_total + 128);
+  }
+  if (!B || !B->m || !B->units || !B->res || !B->in || !B->out) err = MSPACK_ERR_NOMEMORY;
+  else {
+    /* every CHM's piece of the input arena: its stream, the zero bytes behind it, its frame tables -- on a 16-byte boundary, so
+     * that the tables stay uint32-aligned and in_chunk names them (interval_units); 64 zero bytes of slack behind the last one */
+    size_t u = 0, d = n_units;
+    const struct chm_p *done = NULL;
+    for (k = 0; k < n; k++) {
+      const struct chm_p *c = pk[k].c;
+      if (c != done) {
+        const size_t piece = (c->arena_room + 15) & ~(size_t) 15;
+        memcpy(B->in + pk[k].in_base, c->arena, c->arena_room);
+        memset(B->in + pk[k].in_base + c->arena_room, 0, piece - c->arena_room);
+        done = c;
+      }
+      B->m[k].ch = NULL; B->m[k].ires = &pk[k].c->ires[pk[k].first]; B->m[k].u0 = u; B->m[k].count = pk[k].count;
+      interval_units(c, pk[k].first, pk[k].count, 0, pk[k].in_base, pk[k].out_base, B->units + u);
+      u += pk[k].count;
+      if (pk[k].dg_n) { (void) chunk_digest_units(c, pk[k].first, pk[k].count, pk[k].dg_algs, ratio, pk[k].out_base, B->units + d, pk[k].dg_n); d += pk[k].dg_n; }
+    }
+    memset(B->in + in_total, 0, 64);
+    memset(B->res, 0, (n_units + n_dg) * sizeof(*B->res));
+    /* the arena was written a moment ago: page-locked, its copy to the device is plain DMA (advice only) */
+    B->in_pinned = in_total >= ((uint64_t) 4 << 20) && !mspack_arena_is_locked(B->in) && mspack_hip_pin(B->in, mspack_arena_room((size_t) in_total + 64)) == 0;
+    count_batch(n_units);
+    /* as a chunk's own batch: a job when it can be one (several units, one device, no digest units -- those are through only when
+     * the whole batch is); the call returns at once then and every extract() waits for the units of its chunk only */
+    as_job = n_units >= 2 && !n_dg && mspack_hip_default_devices() <= 1 &&
+             (B->job = mspack_hip_decode_batch_begin(B->units, n_units, B->in, (size_t) in_total, B->out, (size_t) out_total + 64, B->res)) != NULL;
+    rc = as_job ? 0 : hip_batch(B->units, n_units + n_dg, B->in, (size_t) in_total, B->out, (size_t) out_total + 64, B->res);
+    if (rc) {
+      sys->message(NULL, "GPU batch decode failed: %s", mspack_hip_last_error());
+      err = MSPACK_ERR_DECRUNCH;                           /* nothing of the batch is kept */
+    }
+    else {
+      size_t dd = n_units;
+      for (k = 0; k < n; k++) {
+        struct chm_chunk *ch = pk[k].ch;
+        B->m[k].ch = ch;
+        ch->pf = B; ch->pf_k = k; ch->buf = B->out + pk[k].out_base; ch->res_valid = 1; ch->job_waited = 0;
+        ch->pf_run = as_job;
+        if (!as_job) {
+          memcpy(B->m[k].ires, B->res + B->m[k].u0, (size_t) pk[k].count * sizeof(*B->res));
+          if (pk[k].dg_n) {
+            chunk_keep_digests(sys, ch, (off_t) pk[k].first * pk[k].c->interval_bytes, B->units + dd, B->res + dd, pk[k].dg_n, pk[k].dg_algs, pk[k].out_base);
+            dd += pk[k].dg_n;
+          }
+        }
+      }
+      B->users = n; B->left = as_job ? n : 0;
+      B->next = self->batches; self->batches = B;
+      if (!as_job) (void) batch_end_job(sys, B);           /* (units, results and the input arena have served) */
+    }
+  }
+  if (err && B) {
+    if (B->in_pinned) mspack_hip_unpin(B->in);
+    sys->free(B->m); sys->free(B->units); sys->free(B->res); mspack_arena_free(sys, B->in); mspack_arena_free(sys, B->out); sys->free(B);
+  }
+  sys->free(pk); sys->free(list);
+  return self->error = err;
+}
+
 int mspack_chmd_set_param(struct mschm_decompressor *base, int param, int value)
 {
   struct chmd_p *self = (struct chmd_p *) base;
@@ -1239,5 +1530,17 @@ struct mschm_decompressor *mspack_create_chm_decompressor(struct mspack_system *
 void mspack_destroy_chm_decompressor(struct mschm_decompressor *base)
 {
   struct chmd_p *self = (struct chmd_p *) base;
-  if (self) self->system->free(self);
+  if (!self) return;
+  /* mspack_chmd_prefetch: batches that still run are settled, and the output buffers that CHMs which were never closed still
+   * use are freed -- those chunks count as not decoded from here on */
+  while (self->batches) {
+    struct chm_batch *B = self->batches;
+    size_t k;
+    for (k = 0; k < B->n; k++) {
+      struct chm_chunk *ch = B->m[k].ch;
+      if (ch) { ch->pf = NULL; ch->pf_run = 0; ch->buf = NULL; ch->res_valid = 0; }
+    }
+    batch_free(self->system, B);
+  }
+  self->system->free(self);
 }
