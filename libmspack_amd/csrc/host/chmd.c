@@ -21,9 +21,10 @@
  * range.  A chunk batch that carries digest units is NOT run as a job -- digest units are through only when the whole
  * batch is (mspack_hip.h), the decision the cabinet driver takes in decode_cabinets -- so the first call into such a chunk
  * returns when every interval of it is decoded and its slowest digest lane has ended.
- * mspack_chmd_prefetch (mspack.h) forms ONE batch over the not-yet-decoded chunks of MANY CHMs before the first extract(): the units
- * and the harvest are the ones a chunk's own batch uses (interval_units, chunk_keep_digests), the input is a copy of every CHM's
- * arena behind one another, the output one buffer the chunks share (struct chm_batch).
+ * Chunks are decoded by ONE mechanism: a struct chm_batch, issued by issue_batch() from a list of chunks.  extract() issues a batch
+ * of the one chunk it needs (ensure_chunk_to), reading the CHM's own arena; mspack_chmd_prefetch (mspack.h) issues ONE batch over
+ * the not-yet-decoded chunks of MANY CHMs before the first extract(), reading a copy of every CHM's arena behind one another.
+ * Either way the output is one buffer the batch's chunks point into, and waiting, eviction, close() and destroy go the same way.
  */
 #include <stdlib.h>
 #include <stdio.h>
@@ -38,22 +39,18 @@ static const char spaninfo_name[] = "::DataSpace/Storage/MSCompressed/SpanInfo";
 static const char rtable_name[]   = "::DataSpace/Storage/MSCompressed/Transform/"
                                     "{7FC28940-9D31-11D0-9B27-00A0C91E9C7C}/InstanceData/ResetTable";
 
-struct chm_chunk {                /* a run of reset intervals decoded in one GPU batch */
-  unsigned char *buf;             /* decoded bytes (E8 origin 0), or NULL when evicted               */
+struct chm_chunk {                /* a run of reset intervals, decoded together as one member of a batch (struct chm_batch) */
+  unsigned char *buf;             /* decoded bytes (E8 origin 0): a place in its batch's output buffer; NULL when evicted */
   unsigned long stamp;            /* LRU clock                                                      */
   int res_valid;                  /* ires[] of these intervals is filled in                         */
-  /* the chunk's batch while it is still running (mspack_hip.h: jobs): interval first + i is unit i; of buf and ires[] only what
-   * chunk_wait() has covered may be read, and neither may be freed before chunk_settle() */
-  mspack_hip_job *job;
-  mspack_hip_unit *job_units;
-  unsigned int job_waited;        /* units [0, job_waited) have come through                        */
+  /* the batch that decoded the chunk, for as long as buf points into its output (bat != NULL exactly while buf != NULL: the bytes
+   * are given back to the batch, never freed); bat_k: which of its members; bat_run: the batch still runs as a job (mspack_hip.h)
+   * and this chunk has not taken all of its units -- of buf and ires[] only what chunk_wait() has covered may be read then */
+  struct chm_batch *bat; size_t bat_k; int bat_run;
+  unsigned int job_waited;        /* units [0, job_waited) of the chunk have come through            */
   /* MSCHMD_PARAM_HIP_DIGESTS: the digests the chunk's batches took of its files, by offset in the stream (host_digest.h: struct
    * digest_table); dg_algs: the algorithms a batch of this chunk has carried units for.  Kept when buf is evicted; freed with section 1 */
   struct digest_table dg; int dg_algs;
-  /* mspack_chmd_prefetch: the batch of many CHMs' chunks this one was decoded by (struct chm_batch) -- buf then lies in that batch's
-   * output buffer and is given back to it, not freed; pf_k: which of its members; pf_run: the batch still runs as a job and this
-   * chunk has not taken all of its units (job_waited counts them, as for `job`).  pf != NULL exactly while buf is the batch's */
-  struct chm_batch *pf; size_t pf_k; int pf_run;
 };
 struct chm_p {
   struct mschmd_header base;
@@ -104,8 +101,8 @@ struct chmd_p {
   struct digest_sink *sink;           /* mspack_chmd_digest is running: what extract() would write goes here instead of a file */
   int sink_whole;                     /* ... and the emit step hands over exactly the file's plain range, of a call that is good so far */
   const unsigned char *sink_kept;     /* ... and that file's digest was taken by its chunk's batch: this one */
-  struct chm_batch *batches;          /* mspack_chmd_prefetch: the batches that still run or whose output buffer still has users */
-  unsigned int pf_stamp;              /* ... one number per call */
+  struct chm_batch *batches;          /* the batches that still run or whose output buffer still has users */
+  unsigned int pf_stamp;              /* mspack_chmd_prefetch: one number per call */
 };
 /* per algorithm, successful mspack_chmd_digest() calls answered from a device digest / hashed on the host (mspack.h) */
 static unsigned long long g_digest_counts[3][2];
@@ -628,56 +625,39 @@ static void interval_units(const struct chm_p *c, unsigned int first, unsigned i
   }
 }
 
-/* decode intervals [first, first+count) stand-alone (interval_units).  dg_ch: the chunk these
- * intervals are, when its files' digest units may ride in the batch (chm_digest_plan, behind the interval units) */
-static int decode_intervals(struct chmd_p *self, struct chm_p *c, unsigned int first, unsigned int count,
-                            off_t e8_origin, unsigned char *out, mspack_hip_result *res, struct chm_chunk *as_job, struct chm_chunk *dg_ch)
+/* what every failed batch call says and answers */
+static int batch_failed(struct mspack_system *sys)
 {
-  struct mspack_system *sys = self->system;
-  const off_t lo = (off_t) first * c->interval_bytes;
-  const int dg_algs = chunk_digest_algs(self, c, lo, dg_ch);
-  double ratio[3] = { 0.0, 0.0, 0.0 };
-  size_t n_dg = 0;
-  mspack_hip_unit *units;
-  mspack_hip_result *res_all = NULL;      /* with digest units: the batch's results, the intervals' copied to res afterwards */
-  int rc;
-  if (dg_algs) {
-    digest_ratios(ratio);
-    n_dg = chunk_digest_units(c, first, count, dg_algs, ratio, 0, NULL, 0);
-  }
-  units = (mspack_hip_unit *) sys->alloc(sys, ((size_t) count + n_dg) * sizeof(*units));
-  if (!units) return MSPACK_ERR_NOMEMORY;
-  if (n_dg && !(res_all = (mspack_hip_result *) sys->alloc(sys, ((size_t) count + n_dg) * sizeof(*res_all)))) n_dg = 0;   /* (no memory: no units) */
-  interval_units(c, first, count, e8_origin, 0, 0, units);
-  if (n_dg) {
-    (void) chunk_digest_units(c, first, count, dg_algs, ratio, 0, units + count, n_dg);
-    memset(res_all, 0, ((size_t) count + n_dg) * sizeof(*res_all));
-  }
-  count_batch(count);
-  /* a chunk's batch runs as a job when it can: extract() of the first file returns when the file's intervals are through,
-   * and the caller writes it while the rest is decoded and copied back (one device: a sharded batch is synchronous) */
-  /* (digest units are through when the whole batch is: a batch that carries some is waited for here) */
-  if (as_job && !n_dg && count > 1 && mspack_hip_default_devices() <= 1 &&
-      (as_job->job = mspack_hip_decode_batch_begin(units, count, c->arena, c->arena_room, out, (size_t) count * (size_t) c->interval_bytes + 64, res))) {
-    as_job->job_units = units; as_job->job_waited = 0;
-    return MSPACK_ERR_OK;
-  }
-  rc = hip_batch(units, (size_t) count + n_dg, c->arena, c->arena_room, out, (size_t) count * (size_t) c->interval_bytes + 64, n_dg ? res_all : res);
-  if (n_dg && !rc) {
-    memcpy(res, res_all, (size_t) count * sizeof(*res));
-    chunk_keep_digests(sys, dg_ch, lo, units + count, res_all + count, n_dg, dg_algs, 0);
-  }
-  sys->free(units); sys->free(res_all);
-  if (rc) { sys->message(NULL, "GPU batch decode failed: %s", mspack_hip_last_error()); return MSPACK_ERR_DECRUNCH; }
-  return MSPACK_ERR_OK;
+  sys->message(NULL, "GPU batch decode failed: %s", mspack_hip_last_error());
+  return MSPACK_ERR_DECRUNCH;
 }
 
-/* ---- one batch over the chunks of many CHMs (mspack_chmd_prefetch) ----
- * The batch owns what it reads -- the units, and an input arena that holds a copy of every CHM's arena, so that none of it points
- * into a CHM -- and what it writes: the results, and ONE output buffer that the chunks share.  A member chunk's buf points into
- * that buffer (no copy per chunk); the buffer goes when its last user has gone (users), whatever happens to the other CHMs.  While
- * the batch runs as a job, `left` members have not taken all of their units yet; the last one out ends the job, and units, results
- * and the input arena go then.  The decompressor keeps the list (chmd_p.batches) so that destroying it can settle them. */
+/* intervals [first, first+count) decoded again, stand-alone (interval_units) and synchronously, with another E8 origin: no chunk,
+ * no digest units, the caller's buffers (vdec_emit) */
+static int decode_intervals(struct chmd_p *self, struct chm_p *c, unsigned int first, unsigned int count,
+                            off_t e8_origin, unsigned char *out, mspack_hip_result *res)
+{
+  struct mspack_system *sys = self->system;
+  mspack_hip_unit *units = (mspack_hip_unit *) sys->alloc(sys, (size_t) count * sizeof(*units));
+  int rc;
+  if (!units) return MSPACK_ERR_NOMEMORY;
+  interval_units(c, first, count, e8_origin, 0, 0, units);
+  count_batch(count);
+  rc = hip_batch(units, count, c->arena, c->arena_room, out, (size_t) count * (size_t) c->interval_bytes + 64, res);
+  sys->free(units);
+  return rc ? batch_failed(sys) : MSPACK_ERR_OK;
+}
+
+/* ---- the batch: what decodes chunks, one (extract()) or those of many CHMs (mspack_chmd_prefetch) ----
+ * The batch owns the units and what it writes: the results, and ONE output buffer that its chunks share.  A member chunk's buf
+ * points into that buffer (no copy per chunk); the buffer goes when its last user has gone (users), whatever happens to the other
+ * CHMs.  While the batch runs as a job, `left` members have not taken all of their units yet; the last one out ends the job, and
+ * units, results and the input arena go then.  The decompressor keeps the list (chmd_p.batches) so that destroying it can settle them.
+ * The input is either the batch's own (in: a copy of every CHM's arena, so that nothing points into a CHM and close() of one never
+ * waits) or BORROWED (in == NULL: the units address the arena of the one CHM at in_base 0 -- no copy of an arena that can be large).
+ * The invariant of a borrowed input: every member is a chunk of that one CHM, and the job has ended before that CHM's arena is freed.
+ * free_sec1 keeps it by dropping the CHM's chunks (chunk_drop_buf -> chunk_detach: the last one out ends the job) BEFORE it frees the
+ * arena; destroying the decompressor ends every job while the CHMs, which only close() frees, still stand. */
 struct chm_member {
   struct chm_chunk *ch;               /* NULL: the chunk has left (evicted, its CHM closed) */
   mspack_hip_result *ires;            /* where the results of its intervals go: its CHM's ires[] from the chunk's first interval on */
@@ -707,71 +687,131 @@ static void batch_free(struct mspack_system *sys, struct chm_batch *B)
   for (at = &B->owner->batches; *at; at = &(*at)->next) if (*at == B) { *at = B->next; break; }
   mspack_arena_free(sys, B->out); sys->free(B->m); sys->free(B);
 }
-/* a chunk that no longer runs in the batch and no longer uses its buffer: the last one out frees it */
-static void chunk_leave_batch(struct mspack_system *sys, struct chm_chunk *ch)
-{
-  struct chm_batch *B = ch->pf;
-  B->m[ch->pf_k].ch = NULL; ch->pf = NULL;
-  if (--B->users == 0) batch_free(sys, B);
-}
 /* a chunk stops waiting for the running batch (its units are through, or nobody will ask: eviction, close); the batch goes on for
  * the others.  Returns the job's answer when this was the last one it ran for, else 0 */
 static int chunk_detach(struct mspack_system *sys, struct chm_chunk *ch)
 {
-  struct chm_batch *B = ch->pf;
-  int rc = 0;
-  ch->pf_run = 0;
-  if (--B->left == 0) rc = batch_end_job(sys, B);
-  return rc;
+  struct chm_batch *B = ch->bat;
+  ch->bat_run = 0;
+  return --B->left == 0 ? batch_end_job(sys, B) : 0;
 }
-/* the chunk's decoded bytes go: its own buffer is freed, a share of a batch's buffer is given back */
+/* the chunk's decoded bytes go: it stops waiting for its batch and gives its share of the output buffer back -- the last one out
+ * frees the batch */
 static void chunk_drop_buf(struct mspack_system *sys, struct chm_chunk *ch)
 {
-  if (ch->pf) {
-    if (ch->pf_run) (void) chunk_detach(sys, ch);
-    ch->buf = NULL;
-    chunk_leave_batch(sys, ch);
-  }
-  else { mspack_arena_free(sys, ch->buf); ch->buf = NULL; }
+  struct chm_batch *B = ch->bat;
+  if (!B) return;
+  if (ch->bat_run) (void) chunk_detach(sys, ch);
+  B->m[ch->bat_k].ch = NULL; ch->bat = NULL; ch->buf = NULL;
+  if (--B->users == 0) batch_free(sys, B);
 }
 
-/* unit i of the chunk's running batch (its own job, or the batch of many CHMs: the result goes to ires[] then) */
+/* unit i of the chunk in its running batch: its result goes to the CHM's ires[] */
 static int chunk_wait_unit(struct chm_chunk *ch, unsigned int i)
 {
-  if (ch->job) return mspack_hip_job_wait_unit(ch->job, i);
-  {
-    struct chm_batch *B = ch->pf;
-    const struct chm_member *m = &B->m[ch->pf_k];
-    const int rc = mspack_hip_job_wait_unit(B->job, m->u0 + i);
-    if (!rc) m->ires[i] = B->res[m->u0 + i];
-    return rc;
-  }
+  struct chm_batch *B = ch->bat;
+  const struct chm_member *m = &B->m[ch->bat_k];
+  const int rc = mspack_hip_job_wait_unit(B->job, m->u0 + i);
+  if (!rc) m->ires[i] = B->res[m->u0 + i];
+  return rc;
 }
 
-/* the chunk's batch, if it is still running, to its end: buf and ires[] are the driver's again (0, or the batch's failure) */
+/* the chunk's units, if its batch is still running, to their end: buf and ires[] are the driver's again (0, or the batch's failure) */
 static int chunk_settle(struct mspack_system *sys, struct chm_chunk *ch)
 {
-  int rc = 0;
-  if (ch->job) {
-    rc = mspack_hip_job_end(ch->job);
-    ch->job = NULL;
-    sys->free(ch->job_units); ch->job_units = NULL;
+  int rc = 0, rc2;
+  if (!ch->bat_run) return 0;
+  while (!rc && ch->job_waited < ch->bat->m[ch->bat_k].count) if (!(rc = chunk_wait_unit(ch, ch->job_waited))) ch->job_waited++;
+  rc2 = chunk_detach(sys, ch);
+  return rc ? rc : rc2;
+}
+
+/* ONE batch that decodes the chunks pk[0 .. n) -- the caller fills c, ch, first, count (chunk_span) and in_base -- and makes them
+ * its members.  in_total > 0: the batch reads a copy of its own of the CHMs' arenas, in_total bytes, every CHM's piece at in_base (a
+ * multiple of 16; the picks of one CHM lie together); in_total == 0: it borrows the arena of the one CHM all picks are of (in_base
+ * 0; struct chm_batch).  It runs as a job when it may and can -- several units, one device, no digest units: those are through only
+ * when the whole batch is -- and the call returns at once then, every later call waiting for the units of its chunk only
+ * (chunk_wait); otherwise it has run to its end here, the results are in ires[] and the digests it took are kept.  A batch that
+ * fails says so once and leaves nothing behind: no chunk is touched */
+struct chm_pick { struct chm_p *c; struct chm_chunk *ch; unsigned int first, count; uint64_t in_base, out_base; int dg_algs; size_t dg_n; };
+
+static int issue_batch(struct chmd_p *self, struct chm_pick *pk, size_t n, uint64_t in_total, int may_job)
+{
+  struct mspack_system *sys = self->system;
+  struct chm_batch *B = (struct chm_batch *) sys->alloc(sys, sizeof(*B));
+  const void *in = pk[0].c->arena;
+  size_t in_bytes = pk[0].c->arena_room, n_units = 0, n_dg = 0, out_total = 0, k, u = 0, d;
+  double ratio[3] = { 0.0, 0.0, 0.0 };
+  int as_job;
+  if (!B) return MSPACK_ERR_NOMEMORY;
+  memset(B, 0, sizeof(*B));
+  B->owner = self; B->n = n;
+  if (self->hip_digests) digest_ratios(ratio);
+  for (k = 0; k < n; k++) {
+    pk[k].out_base = out_total;
+    pk[k].dg_algs = chunk_digest_algs(self, pk[k].c, (off_t) pk[k].first * pk[k].c->interval_bytes, pk[k].ch);
+    pk[k].dg_n = pk[k].dg_algs ? chunk_digest_units(pk[k].c, pk[k].first, pk[k].count, pk[k].dg_algs, ratio, 0, NULL, 0) : 0;
+    out_total += ((size_t) pk[k].count * (size_t) pk[k].c->interval_bytes + 63) & ~(size_t) 63;
+    n_units += pk[k].count; n_dg += pk[k].dg_n;
   }
-  else if (ch->pf_run) {
-    /* (a batch of many CHMs: to the end of THIS chunk's units) */
-    const unsigned int count = ch->pf->m[ch->pf_k].count;
-    int rc2;
-    while (!rc && ch->job_waited < count) if (!(rc = chunk_wait_unit(ch, ch->job_waited))) ch->job_waited++;
-    rc2 = chunk_detach(sys, ch);
-    if (!rc) rc = rc2;
+  B->m = (struct chm_member *) sys->alloc(sys, n * sizeof(*B->m));
+  B->units = (mspack_hip_unit *) sys->alloc(sys, (n_units + n_dg) * sizeof(*B->units));
+  B->res = (mspack_hip_result *) sys->alloc(sys, (n_units + n_dg) * sizeof(*B->res));
+  if (in_total) B->in = (unsigned char *) mspack_arena_alloc(sys, (size_t) in_total + 64);
+  B->out = (unsigned char *) mspack_arena_alloc(sys, out_total + 128);
+  if (!B->m || !B->units || !B->res || (in_total && !B->in) || !B->out) { batch_free(sys, B); return MSPACK_ERR_NOMEMORY; }
+  for (k = 0, d = n_units; k < n; k++) {
+    const struct chm_p *c = pk[k].c;
+    if (in_total && (!k || c != pk[k - 1].c)) {
+      /* every CHM's piece of the input arena: its stream, the zero bytes behind it, its frame tables -- on a 16-byte boundary, so
+       * that the tables stay uint32-aligned and in_chunk names them (interval_units); 64 zero bytes of slack behind the last one */
+      const size_t piece = (c->arena_room + 15) & ~(size_t) 15;
+      memcpy(B->in + pk[k].in_base, c->arena, c->arena_room);
+      memset(B->in + pk[k].in_base + c->arena_room, 0, piece - c->arena_room);
+    }
+    B->m[k].ch = NULL; B->m[k].ires = &pk[k].c->ires[pk[k].first]; B->m[k].u0 = u; B->m[k].count = pk[k].count;
+    interval_units(c, pk[k].first, pk[k].count, 0, pk[k].in_base, pk[k].out_base, B->units + u);
+    u += pk[k].count;
+    if (pk[k].dg_n) { (void) chunk_digest_units(c, pk[k].first, pk[k].count, pk[k].dg_algs, ratio, pk[k].out_base, B->units + d, pk[k].dg_n); d += pk[k].dg_n; }
   }
-  return rc;
+  memset(B->res, 0, (n_units + n_dg) * sizeof(*B->res));
+  if (in_total) {
+    memset(B->in + in_total, 0, 64);
+    /* the arena was written a moment ago: page-locked, its copy to the device is plain DMA (advice only) */
+    B->in_pinned = in_total >= ((uint64_t) 4 << 20) && !mspack_arena_is_locked(B->in) && mspack_hip_pin(B->in, mspack_arena_room((size_t) in_total + 64)) == 0;
+    in = B->in; in_bytes = (size_t) in_total;
+  }
+  count_batch(n_units);
+  as_job = may_job && n_units >= 2 && !n_dg && mspack_hip_default_devices() <= 1 &&
+           (B->job = mspack_hip_decode_batch_begin(B->units, n_units, in, in_bytes, B->out, out_total + 64, B->res)) != NULL;
+  if (!as_job && hip_batch(B->units, n_units + n_dg, in, in_bytes, B->out, out_total + 64, B->res)) {
+    const int err = batch_failed(sys);
+    batch_free(sys, B);
+    return err;
+  }
+  for (k = 0, d = n_units; k < n; k++) {
+    struct chm_chunk *ch = pk[k].ch;
+    B->m[k].ch = ch;
+    ch->bat = B; ch->bat_k = k; ch->bat_run = as_job; ch->buf = B->out + pk[k].out_base; ch->res_valid = 1; ch->job_waited = 0;
+    if (!as_job) {
+      memcpy(B->m[k].ires, B->res + B->m[k].u0, (size_t) pk[k].count * sizeof(*B->res));
+      if (pk[k].dg_n) {
+        chunk_keep_digests(sys, ch, (off_t) pk[k].first * pk[k].c->interval_bytes, B->units + d, B->res + d, pk[k].dg_n, pk[k].dg_algs, pk[k].out_base);
+        d += pk[k].dg_n;
+      }
+    }
+  }
+  B->users = n; B->left = as_job ? n : 0;
+  B->next = self->batches; self->batches = B;
+  if (!as_job) (void) batch_end_job(sys, B);               /* (units, results and the input arena have served) */
+  return MSPACK_ERR_OK;
 }
 
 static void free_sec1(struct mspack_system *sys, struct chm_p *c) {
   unsigned int i;
-  /* (a chunk of a running batch of many CHMs is taken out of it unwaited, chunk_drop_buf: the batch goes on for the others) */
-  if (c->chunks) for (i = 0; i < c->n_chunks; i++) { if (c->chunks[i].job) (void) chunk_settle(sys, &c->chunks[i]); chunk_drop_buf(sys, &c->chunks[i]); sys->free(c->chunks[i].dg.e); }
+  /* the chunks first, the arena behind them: a chunk is taken out of a running batch unwaited (chunk_drop_buf: the batch goes on
+   * for the others), and a batch that borrows this CHM's arena has ended its job when its last chunk has left (struct chm_batch) */
+  if (c->chunks) for (i = 0; i < c->n_chunks; i++) { chunk_drop_buf(sys, &c->chunks[i]); sys->free(c->chunks[i].dg.e); }
   if (c->arena_pinned) { mspack_hip_unpin(c->arena); c->arena_pinned = 0; }
   sys->free(c->chunks); mspack_arena_free(sys, c->arena); sys->free(c->ioff); sys->free(c->ires); mspack_arena_free(sys, c->s_buf);
   sys->free(c->dfiles); c->dfiles = NULL; c->n_dfiles = 0;
@@ -941,16 +981,10 @@ static int setup_sec1(struct chmd_p *self, struct chm_p *c, struct mspack_file *
 
   /* fast-result bookkeeping */
   if (c->n_fast) {
-    unsigned int i;
     c->chunk_int = (unsigned int)(CHM_CHUNK_BYTES / c->interval_bytes); if (!c->chunk_int) c->chunk_int = 1;
     c->n_chunks = (c->n_fast + c->chunk_int - 1) / c->chunk_int;
     if (!(c->chunks = (struct chm_chunk *) sys->alloc(sys, (size_t) c->n_chunks * sizeof(*c->chunks)))) return MSPACK_ERR_NOMEMORY;
-    for (i = 0; i < c->n_chunks; i++) {
-      c->chunks[i].buf = NULL; c->chunks[i].stamp = 0; c->chunks[i].res_valid = 0;
-      c->chunks[i].job = NULL; c->chunks[i].job_units = NULL; c->chunks[i].job_waited = 0;
-      memset(&c->chunks[i].dg, 0, sizeof(c->chunks[i].dg)); c->chunks[i].dg_algs = 0;
-      c->chunks[i].pf = NULL; c->chunks[i].pf_k = 0; c->chunks[i].pf_run = 0;
-    }
+    memset(c->chunks, 0, (size_t) c->n_chunks * sizeof(*c->chunks));      /* (nothing decoded, no batch, no digests) */
     if (!(c->ires = (mspack_hip_result *) sys->alloc(sys, (size_t) c->n_fast * sizeof(mspack_hip_result)))) return MSPACK_ERR_NOMEMORY;
     collect_dfiles(sys, c);
   }
@@ -958,41 +992,42 @@ static int setup_sec1(struct chmd_p *self, struct chm_p *c, struct mspack_file *
 }
 
 /* a chunk whose batch is still running: wait until intervals up to k_to (of this chunk) have come through */
-static int chunk_wait(struct chmd_p *self, struct chm_chunk *ch, unsigned int first, unsigned int count, unsigned int k_to)
+static int chunk_wait(struct chmd_p *self, struct chm_chunk *ch, unsigned int first, unsigned int k_to)
 {
   struct mspack_system *sys = self->system;
-  unsigned int upto = k_to - first + 1;
-  if (!ch->job && !ch->pf_run) return MSPACK_ERR_OK;
+  unsigned int count, upto = k_to - first + 1;
+  int rc = 0;
+  if (!ch->bat_run) return MSPACK_ERR_OK;
+  count = ch->bat->m[ch->bat_k].count;
   if (upto > count) upto = count;
-  while (ch->job_waited < upto) {
-    if (chunk_wait_unit(ch, ch->job_waited)) {
-      /* the batch failed: what decode_intervals says of a failed call -- nothing of the chunk is kept */
-      (void) chunk_settle(sys, ch);
-      sys->message(NULL, "GPU batch decode failed: %s", mspack_hip_last_error());
-      chunk_drop_buf(sys, ch); ch->res_valid = 0;
-      return MSPACK_ERR_DECRUNCH;
-    }
-    ch->job_waited++;
-  }
-  if (ch->job_waited >= count && chunk_settle(sys, ch)) {
-    sys->message(NULL, "GPU batch decode failed: %s", mspack_hip_last_error());
-    chunk_drop_buf(sys, ch); ch->res_valid = 0;
-    return MSPACK_ERR_DECRUNCH;
-  }
-  return MSPACK_ERR_OK;
+  while (!rc && ch->job_waited < upto) if (!(rc = chunk_wait_unit(ch, ch->job_waited))) ch->job_waited++;
+  /* a unit failed, or all of the chunk's are through: it leaves the running batch (the last one out hears the job's answer) */
+  if ((rc || ch->job_waited >= count) && chunk_detach(sys, ch)) rc = 1;
+  if (!rc) return MSPACK_ERR_OK;
+  /* the batch failed: what issue_batch says of a failed call, and nothing of the chunk is kept */
+  rc = batch_failed(sys);
+  chunk_drop_buf(sys, ch); ch->res_valid = 0;
+  return rc;
+}
+
+/* chunk ci of c: its intervals [first, first + count) */
+static void chunk_span(const struct chm_p *c, unsigned int ci, unsigned int *first, unsigned int *count)
+{
+  *first = ci * c->chunk_int;
+  *count = (*first + c->chunk_int <= c->n_fast) ? c->chunk_int : c->n_fast - *first;
 }
 
 /* fast results (and, if `need_buf`, the decoded bytes) of the chunk that holds interval k -- of its intervals up to k_to */
 static int ensure_chunk_to(struct chmd_p *self, struct chm_p *c, unsigned int k, unsigned int k_to, int need_buf, struct chm_chunk **out)
 {
   struct mspack_system *sys = self->system;
-  unsigned int ci = k / c->chunk_int, first = ci * c->chunk_int, i;
-  unsigned int count = (first + c->chunk_int <= c->n_fast) ? c->chunk_int : c->n_fast - first;
+  unsigned int ci = k / c->chunk_int, first, count, i;
   struct chm_chunk *ch = &c->chunks[ci];
   int err;
+  chunk_span(c, ci, &first, &count);
   if (out) *out = ch;
   ch->stamp = ++c->stamp;
-  if (ch->buf || (ch->res_valid && !need_buf)) return chunk_wait(self, ch, first, count, k_to);
+  if (ch->buf || (ch->res_valid && !need_buf)) return chunk_wait(self, ch, first, k_to);
   /* stay inside the cache budget: drop the least recently used buffers */
   {
     size_t budget = (size_t) mspack_hip_cache_mb() << 20, each = (size_t) c->chunk_int * (size_t) c->interval_bytes;
@@ -1005,16 +1040,18 @@ static int ensure_chunk_to(struct chmd_p *self, struct chm_p *c, unsigned int k,
       chunk_drop_buf(sys, lru);
     }
   }
-  if (!(ch->buf = (unsigned char *) mspack_arena_alloc(sys, (size_t) count * (size_t) c->interval_bytes + 128))) return MSPACK_ERR_NOMEMORY;
-  /* (a chunk whose bytes will not be kept -- beyond the cache budget -- is decoded synchronously: its buffer goes at once) */
+  /* the chunk's own batch: one member, the CHM's arena borrowed; it runs as a job when it can -- extract() of the first file
+   * returns when the file's intervals are through, and the caller writes it while the rest is decoded and copied back.
+   * (a chunk whose bytes will not be kept -- beyond the cache budget -- is decoded synchronously: it leaves the batch at once) */
   {
     const int keep = need_buf || count * (size_t) c->interval_bytes <= ((size_t) mspack_hip_cache_mb() << 20);
-    err = decode_intervals(self, c, first, count, 0, ch->buf, &c->ires[first], keep ? ch : NULL, ch);
-    if (err) { mspack_arena_free(sys, ch->buf); ch->buf = NULL; return err; }
-    ch->res_valid = 1;
-    if (!keep) { mspack_arena_free(sys, ch->buf); ch->buf = NULL; }
+    struct chm_pick pk;
+    memset(&pk, 0, sizeof(pk));
+    pk.c = c; pk.ch = ch; pk.first = first; pk.count = count;
+    if ((err = issue_batch(self, &pk, 1, 0, keep))) return err;
+    if (!keep) chunk_drop_buf(sys, ch);
   }
-  return chunk_wait(self, ch, first, count, k_to);
+  return chunk_wait(self, ch, first, k_to);
 }
 static int ensure_chunk(struct chmd_p *self, struct chm_p *c, unsigned int k, int need_buf, struct chm_chunk **out)
 {
@@ -1055,10 +1092,7 @@ static int ensure_serial(struct chmd_p *self, struct chm_p *c, off_t need)
   u.e8_base = 0;
   u.flags = MSPACK_HIP_UF_LZX_LOG; u.ref_len = log_cap;
   count_batch(1);
-  if (mspack_hip_decode_batch(&u, 1, c->arena, c->arena_len + 64, c->s_buf, log_off + 4 + 4 * (size_t) log_cap + 64, &c->s_res)) {
-    sys->message(NULL, "GPU batch decode failed: %s", mspack_hip_last_error());
-    return MSPACK_ERR_DECRUNCH;
-  }
+  if (mspack_hip_decode_batch(&u, 1, c->arena, c->arena_len + 64, c->s_buf, log_off + 4 + 4 * (size_t) log_cap + 64, &c->s_res)) return batch_failed(sys);
   c->s_log = c->s_buf + log_off + 4; c->s_log_cap = log_cap;
   c->s_log_n = rd_le32(c->s_buf + log_off); if (c->s_log_n > log_cap) c->s_log_n = log_cap;
   c->s_valid = 1; c->s_init = v->init; c->s_mode = v->mode; c->s_cover = cover;
@@ -1209,7 +1243,7 @@ static int vdec_emit(struct chmd_p *self, struct chm_p *c, struct mspack_file *f
       unsigned int cnt = k1 - k + 1;
       mspack_hip_result *r2 = (mspack_hip_result *) sys->alloc(sys, cnt * sizeof(*r2));
       unsigned char *tmp = (unsigned char *) mspack_arena_alloc(sys, (size_t) cnt * (size_t) c->interval_bytes + 128);
-      err = (!r2 || !tmp) ? MSPACK_ERR_NOMEMORY : decode_intervals(self, c, k, cnt, v->init, tmp, r2, NULL, NULL);
+      err = (!r2 || !tmp) ? MSPACK_ERR_NOMEMORY : decode_intervals(self, c, k, cnt, v->init, tmp, r2);
       if (!err) err = emit_slice(self, fh, tmp + (from - (off_t) k * c->interval_bytes), (size_t)(stop - from));
       sys->free(r2); mspack_arena_free(sys, tmp);
       if (err) return err;
@@ -1351,20 +1385,17 @@ static void prefetch_setup(struct chmd_p *self, struct chm_p *c)
   sys->close(fh);
 }
 
-struct pf_pick { struct chm_p *c; struct chm_chunk *ch; unsigned int first, count; uint64_t in_base, out_base; int dg_algs; size_t dg_n; };
-
 int mspack_chmd_prefetch(struct mschm_decompressor *base, struct mschmd_header **chms, int n_chms)
 {
   struct chmd_p *self = (struct chmd_p *) base;
   struct mspack_system *sys;
   struct chm_p **list;
-  struct pf_pick *pk = NULL;
-  struct chm_batch *B = NULL;
+  struct chm_pick *pk = NULL;
   const uint64_t in_limit = (uint64_t) 1 << 34;             /* what in_chunk * 4 can address */
-  uint64_t in_total = 0, out_total = 0;
-  size_t budget, used = 0, n_list = 0, cap = 0, n = 0, n_units = 0, n_dg = 0, k, l;
-  double ratio[3] = { 0.0, 0.0, 0.0 };
-  int i, err = MSPACK_ERR_OK, stop = 0, as_job, rc;
+  uint64_t in_total = 0;
+  size_t budget, used = 0, n_list = 0, cap = 0, n = 0, l;
+  unsigned int first, count;
+  int i, err = MSPACK_ERR_OK, stop = 0;
   if (!self) return MSPACK_ERR_ARGS;
   if (n_chms < 0 || (n_chms > 0 && !chms)) return self->error = MSPACK_ERR_ARGS;
   for (i = 0; i < n_chms; i++) if (!chms[i]) return self->error = MSPACK_ERR_ARGS;
@@ -1382,15 +1413,14 @@ int mspack_chmd_prefetch(struct mschm_decompressor *base, struct mschmd_header *
     if (c->sec1_state == 0) prefetch_setup(self, c);
     if (c->sec1_state != 1) continue;                       /* (a failure extract() has cached already, or found just now: skipped) */
     for (ci = 0; ci < c->n_chunks; ci++) {
-      const unsigned int first = ci * c->chunk_int, count = (first + c->chunk_int <= c->n_fast) ? c->chunk_int : c->n_fast - first;
+      chunk_span(c, ci, &first, &count);
       if (c->chunks[ci].buf) used += (size_t) count * (size_t) c->interval_bytes;
     }
     cap += c->n_chunks;
     list[n_list++] = c;
   }
-  if (cap && !(pk = (struct pf_pick *) sys->alloc(sys, cap * sizeof(*pk)))) { sys->free(list); return self->error = MSPACK_ERR_NOMEMORY; }
+  if (cap && !(pk = (struct chm_pick *) sys->alloc(sys, cap * sizeof(*pk)))) { sys->free(list); return self->error = MSPACK_ERR_NOMEMORY; }
   /* the chunks: argument order, chunk order, while they fit the budget and the input arena stays addressable */
-  if (self->hip_digests) digest_ratios(ratio);
   for (l = 0; l < n_list && !stop; l++) {
     struct chm_p *c = list[l];
     const uint64_t piece = ((uint64_t) c->arena_room + 15) & ~(uint64_t) 15;
@@ -1399,90 +1429,22 @@ int mspack_chmd_prefetch(struct mschm_decompressor *base, struct mschmd_header *
     int placed = 0;
     for (ci = 0; ci < c->n_chunks; ci++) {
       struct chm_chunk *ch = &c->chunks[ci];
-      const unsigned int first = ci * c->chunk_int, count = (first + c->chunk_int <= c->n_fast) ? c->chunk_int : c->n_fast - first;
-      const size_t bytes = (size_t) count * (size_t) c->interval_bytes;
-      if (ch->buf || ch->res_valid || ch->job || ch->pf) continue;      /* decoded already, or part of a batch that still runs */
+      size_t bytes;
+      chunk_span(c, ci, &first, &count);
+      bytes = (size_t) count * (size_t) c->interval_bytes;
+      if (ch->buf || ch->res_valid) continue;                 /* decoded already (a chunk of a batch that still runs has its buf) */
       if (used + bytes > budget) { stop = 1; break; }
       if (!placed) {
         if (in_total + piece + 64 > in_limit) { stop = 1; break; }
         in_base = in_total; in_total += piece; placed = 1;
       }
-      pk[n].c = c; pk[n].ch = ch; pk[n].first = first; pk[n].count = count; pk[n].in_base = in_base; pk[n].out_base = out_total;
-      pk[n].dg_algs = chunk_digest_algs(self, c, (off_t) first * c->interval_bytes, ch);
-      pk[n].dg_n = pk[n].dg_algs ? chunk_digest_units(c, first, count, pk[n].dg_algs, ratio, 0, NULL, 0) : 0;
-      out_total += ((uint64_t) bytes + 63) & ~(uint64_t) 63;
-      n_units += count; n_dg += pk[n].dg_n; used += bytes;
+      pk[n].c = c; pk[n].ch = ch; pk[n].first = first; pk[n].count = count; pk[n].in_base = in_base;
+      used += bytes;
       n++;
     }
   }
-  if (!n) { sys->free(pk); sys->free(list); return self->error = MSPACK_ERR_OK; }      /* nothing left to decode: no batch */
-
-  if ((B = (struct chm_batch *) sys->alloc(sys, sizeof(*B)))) {
-    memset(B, 0, sizeof(*B));
-    B->owner = self; B->n = n;
-    B->m = (struct chm_member *) sys->alloc(sys, n * sizeof(*B->m));
-    B->units = (mspack_hip_unit *) sys->alloc(sys, (n_units + n_dg) * sizeof(*B->units));
-    B->res = (mspack_hip_result *) sys->alloc(sys, (n_units + n_dg) * sizeof(*B->res));
-    B->in = (unsigned char *) mspack_arena_alloc(sys, (size_t) in_total + 64);
-    B->out = (unsigned char *) mspack_arena_alloc(sys, (size_t) out_total + 128);
-  }
-  if (!B || !B->m || !B->units || !B->res || !B->in || !B->out) err = MSPACK_ERR_NOMEMORY;
-  else {
-    /* every CHM's piece of the input arena: its stream, the zero bytes behind it, its frame tables -- on a 16-byte boundary, so
-     * that the tables stay uint32-aligned and in_chunk names them (interval_units); 64 zero bytes of slack behind the last one */
-    size_t u = 0, d = n_units;
-    const struct chm_p *done = NULL;
-    for (k = 0; k < n; k++) {
-      const struct chm_p *c = pk[k].c;
-      if (c != done) {
-        const size_t piece = (c->arena_room + 15) & ~(size_t) 15;
-        memcpy(B->in + pk[k].in_base, c->arena, c->arena_room);
-        memset(B->in + pk[k].in_base + c->arena_room, 0, piece - c->arena_room);
-        done = c;
-      }
-      B->m[k].ch = NULL; B->m[k].ires = &pk[k].c->ires[pk[k].first]; B->m[k].u0 = u; B->m[k].count = pk[k].count;
-      interval_units(c, pk[k].first, pk[k].count, 0, pk[k].in_base, pk[k].out_base, B->units + u);
-      u += pk[k].count;
-      if (pk[k].dg_n) { (void) chunk_digest_units(c, pk[k].first, pk[k].count, pk[k].dg_algs, ratio, pk[k].out_base, B->units + d, pk[k].dg_n); d += pk[k].dg_n; }
-    }
-    memset(B->in + in_total, 0, 64);
-    memset(B->res, 0, (n_units + n_dg) * sizeof(*B->res));
-    /* the arena was written a moment ago: page-locked, its copy to the device is plain DMA (advice only) */
-    B->in_pinned = in_total >= ((uint64_t) 4 << 20) && !mspack_arena_is_locked(B->in) && mspack_hip_pin(B->in, mspack_arena_room((size_t) in_total + 64)) == 0;
-    count_batch(n_units);
-    /* as a chunk's own batch: a job when it can be one (several units, one device, no digest units -- those are through only when
-     * the whole batch is); the call returns at once then and every extract() waits for the units of its chunk only */
-    as_job = n_units >= 2 && !n_dg && mspack_hip_default_devices() <= 1 &&
-             (B->job = mspack_hip_decode_batch_begin(B->units, n_units, B->in, (size_t) in_total, B->out, (size_t) out_total + 64, B->res)) != NULL;
-    rc = as_job ? 0 : hip_batch(B->units, n_units + n_dg, B->in, (size_t) in_total, B->out, (size_t) out_total + 64, B->res);
-    if (rc) {
-      sys->message(NULL, "GPU batch decode failed: %s", mspack_hip_last_error());
-      err = MSPACK_ERR_DECRUNCH;                           /* nothing of the batch is kept */
-    }
-    else {
-      size_t dd = n_units;
-      for (k = 0; k < n; k++) {
-        struct chm_chunk *ch = pk[k].ch;
-        B->m[k].ch = ch;
-        ch->pf = B; ch->pf_k = k; ch->buf = B->out + pk[k].out_base; ch->res_valid = 1; ch->job_waited = 0;
-        ch->pf_run = as_job;
-        if (!as_job) {
-          memcpy(B->m[k].ires, B->res + B->m[k].u0, (size_t) pk[k].count * sizeof(*B->res));
-          if (pk[k].dg_n) {
-            chunk_keep_digests(sys, ch, (off_t) pk[k].first * pk[k].c->interval_bytes, B->units + dd, B->res + dd, pk[k].dg_n, pk[k].dg_algs, pk[k].out_base);
-            dd += pk[k].dg_n;
-          }
-        }
-      }
-      B->users = n; B->left = as_job ? n : 0;
-      B->next = self->batches; self->batches = B;
-      if (!as_job) (void) batch_end_job(sys, B);           /* (units, results and the input arena have served) */
-    }
-  }
-  if (err && B) {
-    if (B->in_pinned) mspack_hip_unpin(B->in);
-    sys->free(B->m); sys->free(B->units); sys->free(B->res); mspack_arena_free(sys, B->in); mspack_arena_free(sys, B->out); sys->free(B);
-  }
+  /* (nothing left to decode: no batch.)  The batch has a copy of the arenas: close() of one of these CHMs does not wait for it */
+  if (n) err = issue_batch(self, pk, n, in_total, 1);
   sys->free(pk); sys->free(list);
   return self->error = err;
 }
@@ -1531,14 +1493,14 @@ void mspack_destroy_chm_decompressor(struct mschm_decompressor *base)
 {
   struct chmd_p *self = (struct chmd_p *) base;
   if (!self) return;
-  /* mspack_chmd_prefetch: batches that still run are settled, and the output buffers that CHMs which were never closed still
-   * use are freed -- those chunks count as not decoded from here on */
+  /* batches that still run are settled, and the output buffers that CHMs which were never closed still use are freed -- those
+   * chunks count as not decoded from here on */
   while (self->batches) {
     struct chm_batch *B = self->batches;
     size_t k;
     for (k = 0; k < B->n; k++) {
       struct chm_chunk *ch = B->m[k].ch;
-      if (ch) { ch->pf = NULL; ch->pf_run = 0; ch->buf = NULL; ch->res_valid = 0; }
+      if (ch) { ch->bat = NULL; ch->bat_run = 0; ch->buf = NULL; ch->res_valid = 0; }
     }
     batch_free(self->system, B);
   }

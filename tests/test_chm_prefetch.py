@@ -357,6 +357,146 @@ def test_digests_of_a_prefetched_set_cpu(built, hostlogic):
     check_digests(hostlogic, "cpu", on_device=False)
 
 
+ONE_BATCH = ["lzx16-r2", "w15-r1", "w16-r2-small", "one-interval"]     # 12, 3, 2 reset intervals, and 1: never a job
+
+
+def one_interval():
+    return custom("one-interval", seed=47, text=2, n_bytes=R.FRAME, window_bits=15, reset_frames=1, n_files=4)
+
+
+MIB = 1 << 20
+
+
+def three_chunks():
+    """3 MiB in 48 intervals of 64 KiB -- three chunks of 16 units where chmd.c is built with chunks of 1 MiB (the sanitizer program's
+    sequence 6).  Files, in directory order: in chunk 0's first interval, in chunk 1, in chunk 2, further into chunk 0, across
+    the border of chunks 0 and 1"""
+    return custom("three-chunks", seed=53, text=0, n_bytes=3 * MIB, window_bits=16, reset_frames=2,
+                  files=[["/a.bin", 1000, 5000], ["/b.bin", MIB + 70000, 5000], ["/c.bin", 2 * MIB + 200000, 70000],
+                         ["/d.bin", 500000, 300000], ["/e.bin", MIB - 3000, 10000]])
+
+
+def destroy_with_chms_open(s):
+    """the decompressor goes while its CHMs are open; what the CHMs themselves hold is given back afterwards through a second
+    decompressor on the same mspack_system (close() needs the system alone), so that a leak checker has nothing to report"""
+    s.L.mspack_destroy_chm_decompressor(s.d)
+    d2 = s.L.mspack_create_chm_decompressor(s.mem.ptr())
+    for j, c in enumerate(s.chms):
+        if c:
+            d2.contents.close(d2, c)
+            s.chms[j] = None; s._files[j] = []
+    s.L.mspack_destroy_chm_decompressor(d2)
+    s.d = None
+
+
+def one_batch_sequences(L, where, set_mb, get_mb, jobs_begun=None):
+    """Where a chunk's own batch (the first extract() that needs the chunk) and the batch of many CHMs meet: both are a struct
+    chm_batch (csrc/host/chmd.c), the first with one member.  Every call against the same call on a fresh decompressor that was
+    never told anything: code, last_error(), bytes, lines said.  None of these CHMs is damaged, so a call's answer does not depend
+    on the calls before it."""
+    blobs = [blob_of(n) for n in ONE_BATCH[:3]] + [one_interval()]
+
+    def counts():
+        return api.chmd_batch_counts(L=L)
+
+    def calls(s, ops):
+        return [r[2:6] for r in run_ops(s, ops, L)]
+
+    with api.ChmSet(blobs, L=L) as ref:
+        every = orders(ref, 4)["forward"]
+        want = dict(zip(every, calls(ref, every)))
+        assert all(w[0] == 0 and not w[3] for w in want.values())
+
+    def same(s, ops, seq):
+        got = calls(s, ops)
+        assert got == [want[o] for o in ops], (where, seq, [(o, x, want[o]) for o, x in zip(ops, got) if x != want[o]][:3])
+
+    # 1. the first file of lzx16-r2: the chunk's own job runs with most of its units unwaited -- close() at once; and on a
+    #    second decompressor: destroy without closing
+    s = api.ChmSet(blobs[:1], L=L)
+    same(s, [(0, 0)], 1)
+    s.close()
+    s = api.ChmSet(blobs[:1], L=L)
+    same(s, [(0, 0)], 1)
+    destroy_with_chms_open(s)
+
+    # 2. two CHMs on demand, then prefetch() of all four: the batch holds the others' units only; everything backward; close in an
+    #    order that frees a one-member batch (CHM 0's) between the members of the shared one (CHMs 1 and 3)
+    with api.ChmSet(blobs, L=L) as s:
+        api.chmd_batch_counts(reset=True, L=L)
+        same(s, [(0, 0), (2, 1)], 2)
+        assert counts() == (2, 12 + 2)
+        assert s.prefetch() == 0 and counts() == (3, 12 + 2 + 3 + 1), counts()
+        same(s, every[::-1], 2)
+        assert counts() == (3, 12 + 2 + 3 + 1), counts()
+        for k in (1, 0, 3, 2):
+            s.close(k)
+
+    # 3. prefetch([a, b]), close a, one file of c on demand, prefetch() again: nothing of b or c is issued twice
+    with api.ChmSet(blobs, L=L) as s:
+        api.chmd_batch_counts(reset=True, L=L)
+        assert s.prefetch([0, 1]) == 0 and counts() == (1, 12 + 3), counts()
+        s.close(0)
+        same(s, [(2, 1)], 3)                                              # (file 0 is the empty one)
+        assert counts() == (2, 12 + 3 + 2), counts()
+        assert s.prefetch() == 0 and counts() == (3, 12 + 3 + 2 + 1), counts()      # the one interval of the last CHM is what is left
+        same(s, [o for o in every[::-1] if o[0] != 0], 3)
+        assert s.prefetch() == 0 and counts() == (3, 12 + 3 + 2 + 1), counts()
+
+    # 4. a budget of 1 MiB, lzx16-r2 and lzx21-r2 (768 KiB each) on demand, their files in turn: the answers of the default budget.
+    #    (The driver's LRU counts per CHM, so each of the two keeps its one chunk while the other's job may still run: nothing is
+    #    evicted here.  A chunk whose own job still runs is evicted in tests/csrc/chm_prefetch_check.c, sequence 6: that needs a
+    #    CHM of several chunks, which the library's 64 MiB chunks put out of a quick test's reach.)
+    two = [blobs[0], blob_of("lzx21-r2")]
+    with api.ChmSet(two, L=L) as ref:
+        turns = orders(ref, 2)["interleaved"]
+        want4 = calls(ref, turns)
+    old = get_mb()
+    try:
+        assert set_mb(1) == 0
+        with api.ChmSet(two, L=L) as s:
+            got = calls(s, turns)
+            assert got == want4, (where, 4, [(o, x, y) for o, x, y in zip(turns, got, want4) if x != y][:3])
+    finally:
+        assert set_mb(old) == 0
+
+    # 5. (the stand-in only) the CHM of one interval on demand, and prefetched alone: a batch of one unit each, never a job
+    if jobs_begun:
+        b0 = jobs_begun()
+        last = [i for k, i in every if k == 3][::-1]
+        for tell in (False, True):
+            with api.ChmSet(blobs[3:], L=L) as s:
+                api.chmd_batch_counts(reset=True, L=L)
+                assert not tell or (s.prefetch() == 0 and counts() == (1, 1))
+                assert calls(s, [(0, i) for i in last]) == [want[(3, i)] for i in last], (where, 5, tell)
+                assert counts() == (1, 1), counts()
+        assert jobs_begun() == b0
+
+
+def test_own_batch_and_shared_batch_meet_cpu(built, hostlogic):
+    """one_batch_sequences on the stand-in's lazy jobs, without jobs (MSPACK_HIP_JOBS=0) and on two devices (the sharded,
+    synchronous call); the batch of one unit (sequence 5) begins no job in any of them"""
+    L = api._setup(hostlogic)
+    L.mspack_standin_jobs_begun.restype = api.C.c_ulong
+    args = (hostlogic.mspack_hip_set_cache_mb, hostlogic.mspack_hip_cache_mb, L.mspack_standin_jobs_begun)
+    b0 = L.mspack_standin_jobs_begun()
+    one_batch_sequences(hostlogic, "cpu, jobs", *args)
+    assert L.mspack_standin_jobs_begun() >= b0 + 6                            # the own batches and the shared ones ran as (lazy) jobs
+    b0 = L.mspack_standin_jobs_begun()
+    os.environ["MSPACK_HIP_JOBS"] = "0"
+    try:
+        one_batch_sequences(hostlogic, "cpu, no jobs", *args)
+    finally:
+        del os.environ["MSPACK_HIP_JOBS"]
+    old = hostlogic.mspack_hip_default_devices()
+    try:
+        assert hostlogic.mspack_hip_set_default_devices(2) == 0
+        one_batch_sequences(hostlogic, "cpu, two devices", *args)
+    finally:
+        assert hostlogic.mspack_hip_set_default_devices(old) == 0
+    assert L.mspack_standin_jobs_begun() == b0
+
+
 SAN = ["-O1", "-g", "-fsanitize=address,undefined", "-static-libasan", "-static-libubsan", "-fno-omit-frame-pointer",
        "-fno-sanitize-recover=undefined", "-Wall", "-Wno-unused-function", "-I", os.path.join(ROOT, "include")]
 SAN_ENV = dict(ASAN_OPTIONS="detect_leaks=1:abort_on_error=0:exitcode=97", UBSAN_OPTIONS="print_stacktrace=1")
@@ -365,17 +505,24 @@ SAN_ENV = dict(ASAN_OPTIONS="detect_leaks=1:abort_on_error=0:exitcode=97", UBSAN
 def test_chm_prefetch_check_under_asan_ubsan(built, tmp_path):
     """tests/csrc/chm_prefetch_check.c: a program of its own (no python in the process, nothing preloaded) on the drivers + the stand-in
     + the oracle, all compiled with -fsanitize=address,undefined: the lifetime sequences above on lazy jobs, without jobs and on
-    two devices, the argument cases, a budget of 1 MiB.  Any report -- leaks included -- fails."""
+    two devices, the argument cases, a budget of 1 MiB; and one_batch_sequences above, over the CHMs behind "--", with one more:
+    the eviction of a chunk whose own job still runs.  For that chmd.c is built with chunks of 1 MiB (as tests/test_chm_digest.py
+    does) and the last CHM has three of them; every other CHM decodes to 768 KiB at most and is one chunk as in the library.  Any
+    report -- leaks included -- fails."""
     names = ["lzx16-r2", "w15-r1", "lzx21-r2-cut", "w16-r2-small", "lzx21-r2-e8", "lzx21-r2-badwindow"]
+    blobs = [blob_of(n) for n in names] + [None] + [blob_of(n) for n in ONE_BATCH[:3]] + [one_interval(), blob_of("lzx21-r2"), three_chunks()]
     paths = []
-    for k, n in enumerate(names):
-        (tmp_path / ("c%d.chm" % k)).write_bytes(blob_of(n))
+    for k, blob in enumerate(blobs):
+        if blob is None:
+            paths.append("--")
+            continue
+        (tmp_path / ("c%d.chm" % k)).write_bytes(blob)
         paths.append(str(tmp_path / ("c%d.chm" % k)))
     exe = str(tmp_path / "chm_prefetch_check")
     srcs = [os.path.join(HERE, "csrc", "chm_prefetch_check.c")] + \
         sorted(glob.glob(os.path.join(ROOT, "libmspack_amd", "csrc", "host", "*.c"))) + \
         [os.path.join(HERE, "csrc", "batch_standin.c")] + sorted(glob.glob(os.path.join(ROOT, "oracle", "*_oracle.c")))
-    subprocess.check_call(["gcc"] + SAN + ["-o", exe] + srcs + ["-lpthread"])
+    subprocess.check_call(["gcc"] + SAN + ["-DCHM_CHUNK_BYTES=((off_t)1<<20)", "-o", exe] + srcs + ["-lpthread"])
     env = dict(os.environ, **SAN_ENV)
     env.pop("MSPACK_HIP_JOBS", None)
     p = subprocess.run([exe, str(tmp_path)] + paths, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
@@ -430,6 +577,15 @@ def test_budget_leaves_the_rest_to_extract_gpu(built):
 @pytest.mark.gpu
 def test_digests_of_a_prefetched_set_gpu(built):
     check_digests(None, "gpu", on_device=True)
+
+
+@pytest.mark.gpu
+def test_own_batch_and_shared_batch_meet_gpu(built):
+    """one_batch_sequences 1 to 4 on the library's real jobs: close and destroy while a chunk's own batch may still run, on demand
+    beside a batch of many CHMs and at a budget of 1 MiB (every CHM decodes to 768 KiB at most: one chunk each, so no chunk is
+    evicted here)"""
+    L = api.lib()
+    one_batch_sequences(None, "gpu", L.mspack_hip_set_cache_mb, L.mspack_hip_cache_mb)
 
 
 @pytest.mark.gpu

@@ -203,7 +203,7 @@ def test_lzx_e8_at_the_edge(built, fill):
 # ---- lzx_intervals_the_chm_way -------------------------------------------------------------------------------------------------------
 def chm_items():
     """ONE copy of each stream in the arena; every reset interval is a unit whose in_off is the reset-table entry (any even residue)
-    and whose in_len reaches to the end of the WHOLE stream, as chmd.c decode_intervals builds them: the look-ahead frame of
+    and whose in_len reaches to the end of the WHOLE stream, as chmd.c interval_units builds them: the look-ahead frame of
     lzxd.c:419 is decodable and its bytes are the next unit's.  And a copy with one flipped bit in interval 3."""
     items = []
     for s, (wb, reset, n) in enumerate([(16, 1, 6 * FRAME + 5000), (21, 2, 5 * 2 * FRAME + 40000), (17, 2, 4 * 2 * FRAME + 9), (21, 1, 4 * FRAME)]):

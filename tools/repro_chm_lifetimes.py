@@ -2,7 +2,7 @@
 
   python tools/repro_chm_lifetimes.py driver [N]   N x (create -> open -> extract(last file) -> extract(first) -> close -> destroy)
   python tools/repro_chm_lifetimes.py units  [N]   the same 1024-interval batch, N times, through mspack_hip_decode_batch the way
-                                                   chmd.c:decode_intervals builds it (every unit's input runs to the end of the arena)
+                                                   chmd.c:interval_units builds it (every unit's input runs to the end of the arena)
 Prints one line per lifetime / call: error code, sys->message lines, mspack_hip_last_error(), dirty units."""
 import hashlib
 import json

@@ -2,7 +2,7 @@
 
   python tools/stress_chm_batch.py SECONDS [mix]
 
-Decodes the 1024-interval batch the way chmd.c:decode_intervals builds it (every unit's input runs to the end of the arena)
+Decodes the 1024-interval batch the way chmd.c:interval_units builds it (every unit's input runs to the end of the arena)
 over and over for SECONDS; with `mix`, batches of other shapes (a few intervals of another CHM, MSZIP units) are decoded in
 between so that the persistent context's buffers are reused at other sizes.  Every anomaly is printed with the unit's result,
 the result of decoding that unit ALONE right afterwards, and the first differing byte."""
