@@ -208,6 +208,7 @@ const char *mspack_hip_last_error(void);
 #define MSPACK_HIP_FEAT_MD5   2u        /* MSPACK_HIP_KIND_MD5 */
 #define MSPACK_HIP_FEAT_SHA1   4u       /* MSPACK_HIP_KIND_SHA1 (and MSPACK_HIP_KIND_DIGEST_MORE) */
 #define MSPACK_HIP_FEAT_SHA256 8u       /* MSPACK_HIP_KIND_SHA256 (and MSPACK_HIP_KIND_DIGEST_MORE) */
+#define MSPACK_HIP_FEAT_SLOTS 16u       /* mspack_hip_set_slots / _slots / _slot_stats: context slots of the host-buffer entry points */
 unsigned mspack_hip_features(void);
 
 /* ---- device-resident batch decode (the hot path proper) ---------------------------------------
@@ -271,7 +272,9 @@ size_t mspack_hip_frame_scratch_bytes(size_t n_frames_total);
  * units stored (bytes of a range that no unit of the call wrote are unspecified).  mspack_hip_job_wait_unit() on a digest unit
  * or a tail returns when the batch is through.  mspack_hip_decode_batch_multi never cuts its shards inside a digest range (at worst it
  * makes fewer shards); a digest unit goes to the shard that holds its range, a tail to its head's shard.
- * Thread-safe; calls that target the same device are serialised. */
+ * Thread-safe.  A batch runs in one context SLOT of its device from its first step to its last; a device has mspack_hip_slots()
+ * of them (1 unless told otherwise: see "context slots" below), so with one slot calls that target the same device are serialised,
+ * and with k slots up to k of them run side by side and the next one waits for a slot. */
 int mspack_hip_decode_batch(mspack_hip_unit *units, size_t n_units, const void *in, size_t in_bytes,
                             void *out, size_t out_bytes, mspack_hip_result *results);
 
@@ -287,7 +290,9 @@ int mspack_hip_decode_batch(mspack_hip_unit *units, size_t n_units, const void *
  * unit's chunk came through (mspack_hip_last_error() says what).  A batch that is not cut into chunks (interleaved outputs, a
  * small batch) is handed over whole: _wait_unit then returns with _end's answer.  _begin returns NULL when no job could be
  * started (no thread, MSPACK_HIP_JOBS=0): the caller then makes the synchronous call.  One device (the calling thread's current
- * one); calls for the same device -- jobs or not -- are serialised: a second batch waits until the job's batch has returned. */
+ * one); the job's batch holds a context slot of that device like any other batch (its thread does, not the caller): with one slot
+ * (the default) calls for the same device -- jobs or not -- are serialised, a second batch waits until the job's batch has returned;
+ * with more slots the second batch runs beside it. */
 typedef struct mspack_hip_job mspack_hip_job;
 mspack_hip_job *mspack_hip_decode_batch_begin(mspack_hip_unit *units, size_t n_units, const void *in, size_t in_bytes,
                                               void *out, size_t out_bytes, mspack_hip_result *results);
@@ -307,8 +312,38 @@ int mspack_hip_decode_batch_multi(mspack_hip_unit *units, size_t n_units, const 
                                   size_t in_bytes, void *out, size_t out_bytes,
                                   mspack_hip_result *results, int n_devices);
 
-/* Free every persistent per-device context of this process (arenas, pinned staging, streams). */
+/* Free every persistent per-device context of this process (arenas, pinned staging, streams): every slot of every device, once the
+ * batch that runs in it has returned. */
 void mspack_hip_release(void);
+
+/* ---- context slots: batches of several threads side by side on one device -------------------------------------
+ * libmspack's threading contract is "any number of threads, each with a decompressor of its own".  With ONE persistent context per
+ * device the host-buffer entry points keep it by queueing: a thread's batch waits until the batch before it has copied its last
+ * byte home, however small both are beside the chip.  A device therefore has up to four context SLOTS, each with device arenas,
+ * pinned staging, streams and events of its own, none of it shared.  A batch (mspack_hip_decode_batch, _to_device, the thread of a
+ * job, each shard thread of _multi on its own device) takes the free slot with the lowest index below the configured count, keeps
+ * it from plan to drain and hands it back, also when it fails; with no slot free it waits (a condition variable: nothing spins,
+ * nothing waits on the device).  Batches in different slots are on different streams, and the runtime overlaps their copies and
+ * launches: that is the whole mechanism; no kernel knows of it.
+ *   mspack_hip_set_slots(n) : n = 1..4; anything else returns -1 and changes nothing.  Applies to batches that BEGIN afterwards;
+ *                             lowering it frees nothing (a slot's memory stays until mspack_hip_release()) and waits for nobody
+ *   mspack_hip_slots()      : the current value; initially the environment variable MSPACK_HIP_SLOTS (read once), else 1
+ *   mspack_hip_slot_stats() : since the last reset, over all devices: s[0] batches run, s[1] the largest number of batches that
+ *                             held a slot of ONE device at the same time, s[2] batches that had to wait for a slot.  s may be
+ *                             NULL; reset != 0 clears the three after reading
+ * The default is 1: every batch then behaves as it did before slots existed -- same order, same memory, same streams.
+ * What more slots COST: a slot's streams, events and buffers are created by the first batch that runs in it (a process whose
+ * batches never meet allocates nothing beyond slot 0), and kept: up to `slots` times the arenas and the pinned staging per device
+ * (each slot's arenas grow to the largest batch it has seen), and up to slots x (2 + MSPACK_HIP_NCOMPUTE) streams -- beyond the
+ * hardware queues a process has, streams share queues.  A slot that replaces a buffer with a larger one waits for its OWN streams
+ * first, but freeing device memory can stall the whole device for a moment: the neighbours are delayed, never disturbed.
+ * What does NOT change, with any number of slots: every result, every output byte and every error code of a batch are those it has
+ * alone; mspack_hip_last_error() stays per calling thread; the job contract (_begin / _wait_unit / _end) is as stated above.
+ * Batches that run side by side must not write the same memory (their `out` and `results` are their own; `in` may be shared).
+ * MSPACK_HIP_PIN_IN=1 (an experiment's knob) is honoured with one slot only. */
+int  mspack_hip_set_slots(int n);
+int  mspack_hip_slots(void);
+void mspack_hip_slot_stats(unsigned long long s[3], int reset);
 
 /* ---- process-wide defaults for the object API (mspack.h) ----------------------------------------------
  * mscab_decompressor has set_param (MSCABD_PARAM_HIP_DEVICES / _HIP_CACHE_MB); the CHM, OAB, SZDD and KWAJ

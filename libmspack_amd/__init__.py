@@ -28,6 +28,7 @@ FEAT_CRC32 = 1
 FEAT_MD5 = 2
 MASK_MD5 = 1 << KIND_MD5     # decode_batch_device(kind_mask): launch the MD5 pass
 FEAT_SHA1, FEAT_SHA256 = 4, 8
+FEAT_SLOTS = 16              # set_slots / slots / slot_stats: context slots of the host-buffer entry points
 MASK_SHA1, MASK_SHA256 = 1 << KIND_SHA1, 1 << KIND_SHA256     # ... the SHA-1 / the SHA-256 pass
 ERR_OK, ERR_ARGS, ERR_OPEN, ERR_READ, ERR_WRITE, ERR_SEEK, ERR_NOMEMORY, ERR_SIGNATURE, \
     ERR_DATAFORMAT, ERR_CHECKSUM, ERR_CRUNCH, ERR_DECRUNCH = range(12)
@@ -77,6 +78,10 @@ def lib():
         L.mspack_hip_release.restype = None
         L.mspack_hip_features.restype = C.c_uint
         L.mspack_hip_features.argtypes = []
+        L.mspack_hip_set_slots.argtypes = [C.c_int]
+        L.mspack_hip_slots.argtypes = []
+        L.mspack_hip_slot_stats.restype = None
+        L.mspack_hip_slot_stats.argtypes = [vp, C.c_int]
         _lib = L
     return _lib
 
@@ -89,6 +94,7 @@ EXPORTED_SYMBOLS = [
     "mspack_hip_set_default_devices", "mspack_hip_default_devices", "mspack_hip_set_cache_mb", "mspack_hip_cache_mb",
     "mspack_hip_host_path_stats", "mspack_hip_pin", "mspack_hip_unpin", "mspack_hip_stage_alloc", "mspack_hip_stage_free",
     "mspack_hip_decode_batch_begin", "mspack_hip_job_wait_unit", "mspack_hip_job_end", "mspack_hip_features",
+    "mspack_hip_set_slots", "mspack_hip_slots", "mspack_hip_slot_stats",
 ]
 
 
@@ -100,6 +106,26 @@ def _check(rc, what):
 def features():
     """capability word of the loaded library (FEAT_*): mspack_hip_features()"""
     return int(lib().mspack_hip_features())
+
+
+def set_slots(n):
+    """context slots per device (1..4): how many batches of different threads run side by side on one device; applies to batches
+    that begin afterwards.  mspack_hip_set_slots()"""
+    if lib().mspack_hip_set_slots(int(n)) != 0:
+        raise ValueError("slots must be 1..4, not %r" % (n,))
+
+
+def slots():
+    """the current number of context slots per device (initially MSPACK_HIP_SLOTS, else 1): mspack_hip_slots()"""
+    return int(lib().mspack_hip_slots())
+
+
+def slot_stats(reset=False):
+    """(batches run, the most batches that held a slot of one device at the same time, batches that waited for a slot) since the
+    last reset: mspack_hip_slot_stats()"""
+    s = (C.c_ulonglong * 3)()
+    lib().mspack_hip_slot_stats(s, 1 if reset else 0)
+    return int(s[0]), int(s[1]), int(s[2])
 
 
 def frames_of(units):

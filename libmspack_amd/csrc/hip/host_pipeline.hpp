@@ -24,11 +24,18 @@
 // (Four streams = four hardware queues: with more, two streams share a queue and a copy waits behind another
 // chunk's kernel -- what profiles/round2_hostpath_streams.txt shows for its third chunk.)
 // ---------------------------------------------------------------------------------------------------
+// Context SLOTS (mspack_hip_set_slots): a device has up to MSPK_MAX_SLOTS such contexts, each with arenas, staging, streams and events of
+// its own.  A batch takes the free slot with the lowest index below the configured count, keeps it from plan to drain and hands it
+// back; with none free it waits on the pool's condition variable.  Batches in different slots share nothing but the chip: their
+// copies and launches are on different streams and the runtime overlaps them.  One slot (the default) is the single context and the
+// queue of batches this file always had.  A slot's streams, events and buffers come with the first batch that runs in it.
 #define MSPK_MAX_DEV 16
 #define MSPK_MAX_STREAMS 8
+#define MSPK_MAX_SLOTS 4
 struct DevBuf { void *p = nullptr; size_t cap = 0; };
 struct DevCtx {
-  std::mutex mu;
+  std::mutex mu;                        // held by the batch that runs in the slot; by mspack_hip_release while it frees it
+  bool busy = false;                    // (DevPool::mu) a batch has taken the slot
   bool ready = false;
   int ns = 0;
   hipStream_t st[MSPK_MAX_STREAMS];      // [0] copy-in (and everything of a one-chunk call), [1] copy-out, [2] [3] compute
@@ -37,12 +44,67 @@ struct DevCtx {
   DevBuf d_in, d_out, d_units, d_order, d_res, d_fm;
   DevBuf h_stage;                       // pinned: results + (optionally) the output on its way to pageable memory
 };
-static DevCtx g_ctx[MSPK_MAX_DEV];
+struct DevPool {
+  std::mutex mu; std::condition_variable cv;
+  DevCtx slot[MSPK_MAX_SLOTS];
+  int held = 0;                         // slots taken
+};
+static DevPool g_pool[MSPK_MAX_DEV];
 
-static hipError_t grow(DevBuf &b, size_t need, bool pinned) {
+// the configured number of slots per device: MSPACK_HIP_SLOTS (read once), then whatever mspack_hip_set_slots said last
+static std::atomic<int> g_slots{0};
+static int slots_now()
+{
+  int n = g_slots.load(std::memory_order_acquire);
+  if (n) return n;
+  static const int from_env = env_int("MSPACK_HIP_SLOTS", 1, 1, MSPK_MAX_SLOTS);
+  g_slots.compare_exchange_strong(n, from_env);
+  return g_slots.load(std::memory_order_acquire);
+}
+static std::mutex g_slot_stats_mu;
+static unsigned long long g_slot_stats[3] = { 0, 0, 0 };      // batches, the most that held slots of one device at once, batches that waited
+
+// a batch's hold on a slot of its device's pool, from plan to drain (and on every way out)
+struct SlotLease {
+  DevPool &pool; DevCtx *cx = nullptr;
+  explicit SlotLease(DevPool &p) : pool(p) {
+    bool waited = false;
+    {
+      std::unique_lock<std::mutex> lk(pool.mu);
+      for (;;) {
+        const int n = slots_now();
+        for (int i = 0; i < n && !cx; i++) if (!pool.slot[i].busy) cx = &pool.slot[i];
+        if (cx) break;
+        waited = true;
+        pool.cv.wait(lk);
+      }
+      cx->busy = true;
+      pool.held++;
+      std::lock_guard<std::mutex> sl(g_slot_stats_mu);
+      g_slot_stats[0]++;
+      if ((unsigned long long) pool.held > g_slot_stats[1]) g_slot_stats[1] = (unsigned long long) pool.held;
+      if (waited) g_slot_stats[2]++;
+    }
+    cx->mu.lock();
+  }
+  ~SlotLease() {
+    cx->mu.unlock();
+    { std::lock_guard<std::mutex> lk(pool.mu); cx->busy = false; pool.held--; }
+    pool.cv.notify_all();
+  }
+  SlotLease(const SlotLease &) = delete;
+  SlotLease &operator=(const SlotLease &) = delete;
+};
+
+// a buffer of slot cx, at least `need` bytes.  What it replaces is freed behind the slot's OWN streams (hipFree itself may wait for the
+// whole device: a grow may stall the neighbours, it never touches what is theirs)
+static hipError_t grow(DevCtx &cx, DevBuf &b, size_t need, bool pinned) {
   if (need <= b.cap) return hipSuccess;
   hipError_t e;
-  if (b.p) { hipDeviceSynchronize(); e = pinned ? hipHostFree(b.p) : hipFree(b.p); b.p = nullptr; b.cap = 0; if (e != hipSuccess) return e; }
+  if (b.p) {
+    for (int i = 0; i < cx.ns; i++) if ((e = hipStreamSynchronize(cx.st[i])) != hipSuccess) return e;
+    e = pinned ? hipHostFree(b.p) : hipFree(b.p); b.p = nullptr; b.cap = 0; if (e != hipSuccess) return e;
+  }
   size_t cap = need + need / 4 + 4096;
   e = pinned ? hipHostMalloc(&b.p, cap, hipHostMallocDefault) : hipMalloc(&b.p, cap);
   if (e != hipSuccess) { b.p = nullptr; return e; }
@@ -134,15 +196,15 @@ static int grow_buffers(PipeCall &pc, void *dev_out)
 {
   DevCtx &cx = pc.cx;
   const size_t n_sel = pc.plan.local.size(), n_crc = pc.plan.n_crc, in_span = pc.in_span, out_span = pc.out_span;
-  TRY(grow(cx.d_in, in_span + 64, false));
-  if (!dev_out) TRY(grow(cx.d_out, out_span + 64, false));
-  TRY(grow(cx.d_units, n_sel * sizeof(mspack_hip_unit), false));
-  TRY(grow(cx.d_order, (n_sel + n_crc) * sizeof(uint32_t), false));
-  TRY(grow(cx.d_res, n_sel * sizeof(mspack_hip_result), false));
-  TRY(grow(cx.d_fm, lzx_scratch(nullptr, pc.plan.n_frames, pc.plan.n_rec_slots).bytes, false));
+  TRY(grow(cx, cx.d_in, in_span + 64, false));
+  if (!dev_out) TRY(grow(cx, cx.d_out, out_span + 64, false));
+  TRY(grow(cx, cx.d_units, n_sel * sizeof(mspack_hip_unit), false));
+  TRY(grow(cx, cx.d_order, (n_sel + n_crc) * sizeof(uint32_t), false));
+  TRY(grow(cx, cx.d_res, n_sel * sizeof(mspack_hip_result), false));
+  TRY(grow(cx, cx.d_fm, lzx_scratch(nullptr, pc.plan.n_frames, pc.plan.n_rec_slots).bytes, false));
   // (pinned staging: the results, and room for the few output bytes that lie outside every page-locked range -- CopyBack::copy_out)
   pc.stage_res = (n_sel * sizeof(mspack_hip_result) + 255u) & ~(size_t) 255u;
-  TRY(grow(cx.h_stage, pc.stage_res + STAGE_PIECE * STAGE_SLOTS, true));
+  TRY(grow(cx, cx.h_stage, pc.stage_res + STAGE_PIECE * STAGE_SLOTS, true));
   pc.d_in = (u8 *) cx.d_in.p;
   pc.d_out = dev_out ? (u8 *) dev_out : (u8 *) cx.d_out.p;
   pc.d_units = (mspack_hip_unit *) cx.d_units.p;
@@ -305,8 +367,9 @@ static int issue_chunks(PipeCall &pc, CopyBack &cb)
   // runtime's pageable path is as fast as the lock costs (to the host 7.4 -> 8.1 ms on the headline batch); for an arena that was
   // just written -- the C drivers' gather -- it runs at 5-6 GB/s, and those callers lock their arena themselves (mspack_hip_pin).
   static const bool pin_in = env_int("MSPACK_HIP_PIN_IN", 0, 0, 1) != 0;
-  if (pin_in && pc.in_span >= ((size_t) 4 << 20)) {
-    // (ONE range, the whole pages inside what the copies below read: the chunks' input ranges may overlap -- frame tables
+  if (pin_in && slots_now() == 1 && pc.in_span >= ((size_t) 4 << 20)) {
+    // (one slot only: beside another batch that reads the same input the copies of the two could not be cut at each other's locks)
+  // (ONE range, the whole pages inside what the copies below read: the chunks' input ranges may overlap -- frame tables
     // behind the streams)
     uintptr_t ra, rb;
     if (inner_pages((const char *) pc.in + plan.in_lo, pc.in_span, ra, rb)) cb.pins_in.lock(ra, rb);
@@ -447,7 +510,7 @@ static int run_plan(PipeCall &pc, void *dev_out)
 // `sel` lists the unit indices this device handles (NULL = all n_sel units).  host_out != NULL: outputs are
 // copied back into it; dev_out != NULL: the caller's DEVICE buffer receives them (out_off relative to it).
 // per_unit_back: copy the outputs back unit by unit (a sharded call whose shards' output spans interleave)
-// plan -> buffers -> issue -> drain, under the context's lock from the first step to the last.
+// plan -> buffers -> issue -> drain, in one slot of the device's pool from the first step to the last.
 static int pipeline_on_current_device(int dev, mspack_hip_unit *units, const uint32_t *sel, size_t n_sel,
                                       const void *in, size_t in_bytes, void *host_out, void *dev_out,
                                       size_t out_bytes, mspack_hip_result *results, char *errbuf, size_t errcap,
@@ -455,8 +518,8 @@ static int pipeline_on_current_device(int dev, mspack_hip_unit *units, const uin
 {
   if (n_sel == 0) return 0;
   if (dev < 0 || dev >= MSPK_MAX_DEV) { snprintf(errbuf, errcap, "device index %d out of range", dev); return -1; }
-  DevCtx &cx = g_ctx[dev];
-  std::lock_guard<std::mutex> lock(cx.mu);
+  SlotLease lease(g_pool[dev]);
+  DevCtx &cx = *lease.cx;
   BatchPlan plan;
   PipeCall pc{ dev, cx, plan, in, host_out, results, pg, errbuf, errcap, tnow() };
   // (a batch the planner rejects has touched nothing: no context, no stream to wait for)
@@ -600,24 +663,51 @@ void mspack_hip_host_path_stats(double *ms4, int reset)
   if (reset) for (int i = 0; i < 4; i++) g_stats_ms[i] = 0.0;
 }
 
-// free every persistent context (device arenas, pinned staging, streams) of this process
+int mspack_hip_set_slots(int n)
+{
+  if (n < 1 || n > MSPK_MAX_SLOTS) return -1;
+  g_slots.store(n, std::memory_order_release);
+  // (a batch that waits for a slot looks again)
+  for (int d = 0; d < MSPK_MAX_DEV; d++) { { std::lock_guard<std::mutex> lk(g_pool[d].mu); } g_pool[d].cv.notify_all(); }
+  return 0;
+}
+int mspack_hip_slots(void) { return slots_now(); }
+void mspack_hip_slot_stats(unsigned long long s[3], int reset)
+{
+  std::lock_guard<std::mutex> lock(g_slot_stats_mu);
+  if (s) for (int i = 0; i < 3; i++) s[i] = g_slot_stats[i];
+  if (reset) for (int i = 0; i < 3; i++) g_slot_stats[i] = 0;
+}
+
+// free every persistent context (device arenas, pinned staging, streams) of this process: device by device, the pool's lock (no
+// batch takes a slot meanwhile), then every slot's (the batches that hold one have handed it back), then the slots' resources
 void mspack_hip_release(void)
 {
   int keep = current_device();
   stage_release_idle();
   for (int d = 0; d < MSPK_MAX_DEV; d++) {
-    DevCtx &cx = g_ctx[d];
-    std::lock_guard<std::mutex> lock(cx.mu);
-    if (!cx.ready && !cx.d_in.p && !cx.h_stage.p) continue;
+    DevPool &pool = g_pool[d];
+    std::lock_guard<std::mutex> pl(pool.mu);
+    std::unique_lock<std::mutex> sl[MSPK_MAX_SLOTS];
+    bool any = false;
+    for (int k = 0; k < MSPK_MAX_SLOTS; k++) {
+      sl[k] = std::unique_lock<std::mutex>(pool.slot[k].mu);
+      any = any || pool.slot[k].ready || pool.slot[k].d_in.p || pool.slot[k].h_stage.p;
+    }
+    if (!any) continue;
     if (hipSetDevice(d) != hipSuccess) continue;
     hipDeviceSynchronize();
-    for (DevBuf *b : { &cx.d_in, &cx.d_out, &cx.d_units, &cx.d_order, &cx.d_res, &cx.d_fm }) { if (b->p) hipFree(b->p); b->p = nullptr; b->cap = 0; }
-    if (cx.h_stage.p) { hipHostFree(cx.h_stage.p); cx.h_stage.p = nullptr; cx.h_stage.cap = 0; }
-    if (cx.ready) {
-      for (int i = 0; i < cx.ns; i++) hipStreamDestroy(cx.st[i]);
-      for (int i = 0; i < MSPK_MAX_CHUNKS; i++) { hipEventDestroy(cx.ev_in[i]); hipEventDestroy(cx.ev_done[i]); hipEventDestroy(cx.ev_back[i]); }
+    for (int k = 0; k < MSPK_MAX_SLOTS; k++) {
+      DevCtx &cx = pool.slot[k];
+      if (!cx.ready && !cx.d_in.p && !cx.h_stage.p) continue;
+      for (DevBuf *b : { &cx.d_in, &cx.d_out, &cx.d_units, &cx.d_order, &cx.d_res, &cx.d_fm }) { if (b->p) hipFree(b->p); b->p = nullptr; b->cap = 0; }
+      if (cx.h_stage.p) { hipHostFree(cx.h_stage.p); cx.h_stage.p = nullptr; cx.h_stage.cap = 0; }
+      if (cx.ready) {
+        for (int i = 0; i < cx.ns; i++) hipStreamDestroy(cx.st[i]);
+        for (int i = 0; i < MSPK_MAX_CHUNKS; i++) { hipEventDestroy(cx.ev_in[i]); hipEventDestroy(cx.ev_done[i]); hipEventDestroy(cx.ev_back[i]); }
+      }
+      cx.ready = false; cx.ns = 0;
     }
-    cx.ready = false;
   }
   hipSetDevice(keep);
 }
