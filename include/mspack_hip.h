@@ -374,6 +374,18 @@ double mspack_hip_time_batch_device(const mspack_hip_unit *d_units, const uint32
  * of calls.  ms4 may be NULL; reset != 0 clears the sums after reading.  (bench infrastructure: csrc/bench/api_bench.c) */
 void mspack_hip_host_path_stats(double *ms4, int reset);
 
+/* ---- diagnostic: which path took a frame --------------------------------------------------------------------
+ * What the frame-parallel tasks left in the records of frame slots [first_slot, first_slot + n_slots) of the scratch a caller gave
+ * mspack_hip_decode_batch_device (n_frames_total as in that call; a unit's slots begin at its frame_base), 8 words per slot into out:
+ *   LZX   (mszip == 0): status, n_tokens, bytes_done, chain, rst, rs_valid, rs_frame, rs_partial
+ *   MSZIP (mszip != 0): status, n_tokens, total_out, fold, 0, 0, 0, 0
+ * rst is written by the fold tasks only: rst == 1 and chain == 1 say that a fold task finished the frame when the launch ran them
+ * (MSPACK_HIP_FOLD=2: the resolve tasks do not run then); MSZIP: fold == 1.  The copies are synchronous and the caller has
+ * synchronised the stream of its batch first.  0, or -1 (no scratch, slots beyond it) / a negative runtime code.  Tests and analysis
+ * only: the layout of the records is no part of the ABI and nothing on the decode path depends on this call. */
+int mspack_hip_debug_frame_words(const void *d_frame_scratch, size_t n_frames_total, size_t first_slot, size_t n_slots, int mszip,
+                                 uint32_t *out /* 8 words per slot */);
+
 /* ---- optional: page-lock a caller's input arena ---------------------------------------------------------
  * The host-buffer entry points copy their input with the runtime's pageable path unless the caller's buffer is
  * page-locked; for an arena that was just written (the C drivers' gather) that path runs at 5-6 GB/s.  mspack_hip_pin()

@@ -82,6 +82,7 @@ def lib():
         L.mspack_hip_slots.argtypes = []
         L.mspack_hip_slot_stats.restype = None
         L.mspack_hip_slot_stats.argtypes = [vp, C.c_int]
+        L.mspack_hip_debug_frame_words.argtypes = [vp, sz, sz, sz, C.c_int, vp]
         _lib = L
     return _lib
 
@@ -94,7 +95,7 @@ EXPORTED_SYMBOLS = [
     "mspack_hip_set_default_devices", "mspack_hip_default_devices", "mspack_hip_set_cache_mb", "mspack_hip_cache_mb",
     "mspack_hip_host_path_stats", "mspack_hip_pin", "mspack_hip_unpin", "mspack_hip_stage_alloc", "mspack_hip_stage_free",
     "mspack_hip_decode_batch_begin", "mspack_hip_job_wait_unit", "mspack_hip_job_end", "mspack_hip_features",
-    "mspack_hip_set_slots", "mspack_hip_slots", "mspack_hip_slot_stats",
+    "mspack_hip_set_slots", "mspack_hip_slots", "mspack_hip_slot_stats", "mspack_hip_debug_frame_words",
 ]
 
 
@@ -126,6 +127,16 @@ def slot_stats(reset=False):
     s = (C.c_ulonglong * 3)()
     lib().mspack_hip_slot_stats(s, 1 if reset else 0)
     return int(s[0]), int(s[1]), int(s[2])
+
+
+def debug_frame_words(d_frame_scratch, n_frames_total, first_slot, n_slots, mszip=False):
+    """diagnostic: the record words of n_slots frame slots of a caller's own scratch (a device pointer) behind a synchronised
+    mspack_hip_decode_batch_device call -> uint32 array (n_slots, 8); LZX: status, n_tokens, bytes_done, chain, rst, rs_valid,
+    rs_frame, rs_partial; MSZIP: status, n_tokens, total_out, fold, zeros.  mspack_hip_debug_frame_words()"""
+    w = np.zeros((int(n_slots), 8), dtype=np.uint32)
+    _check(lib().mspack_hip_debug_frame_words(d_frame_scratch, int(n_frames_total), int(first_slot), int(n_slots), 1 if mszip else 0,
+                                              w.ctypes.data), "mspack_hip_debug_frame_words")
+    return w
 
 
 def frames_of(units):

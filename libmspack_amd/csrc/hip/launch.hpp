@@ -269,6 +269,34 @@ int mspack_hip_debug_pipe_phases(unsigned long long *out32) {
   return hipMemcpyToSymbol(HIP_SYMBOL(lzxn::g_pipe_phase), z, sizeof(z)) == hipSuccess ? 0 : -1;
 }
 #endif
+/* diagnostic (always compiled): what the frame-parallel tasks left in the records of frame slots [first_slot, first_slot + n_slots) of a
+ * caller's own scratch -- which path took a frame.  8 words per slot; LZX: status, n_tokens, bytes_done, chain, rst, rs_valid, rs_frame,
+ * rs_partial; MSZIP (through ZipBlockRec): status, n_tokens, total_out, fold, then zeros.  Synchronous copies: the caller has
+ * synchronised the stream its batch ran on.  Nothing on the decode path reads or writes anything for it */
+int mspack_hip_debug_frame_words(const void *d_frame_scratch, size_t n_frames_total, size_t first_slot, size_t n_slots, int mszip,
+                                 uint32_t *out)
+{
+  if (!d_frame_scratch || !out || first_slot > n_frames_total + 1 || n_slots > n_frames_total + 1 - first_slot) {
+    snprintf(g_err, sizeof(g_err), "mspack_hip_debug_frame_words: no scratch, or slots beyond it");
+    return -1;
+  }
+  const LzxScratch L = lzx_scratch(const_cast<void *>(d_frame_scratch), n_frames_total, n_frames_total);
+  for (size_t i = 0; i < n_slots; i++) {
+    alignas(16) unsigned char raw[sizeof(lzxn::LzxFrameRec)];
+    CK(hipMemcpy(raw, &L.recs[first_slot + i], sizeof(raw), hipMemcpyDeviceToHost));
+    uint32_t *w = out + 8 * i;
+    if (mszip) {
+      const ZipBlockRec *z = (const ZipBlockRec *) raw;
+      w[0] = z->status; w[1] = z->n_tokens; w[2] = z->total_out; w[3] = z->fold; w[4] = w[5] = w[6] = w[7] = 0u;
+    }
+    else {
+      const lzxn::LzxFrameRec *r = (const lzxn::LzxFrameRec *) raw;
+      w[0] = r->status; w[1] = r->n_tokens; w[2] = r->bytes_done; w[3] = r->chain; w[4] = r->rst; w[5] = r->rs_valid; w[6] = r->rs_frame;
+      w[7] = r->rs_partial;
+    }
+  }
+  return 0;
+}
 const char *mspack_hip_version(void) { return "mspack-hip 0.4 (gfx950; LZX/LZX-DELTA/Quantum/MSZIP batch decode)"; }
 const char *mspack_hip_last_error(void) { return g_err; }
 unsigned mspack_hip_features(void) { return MSPACK_HIP_FEAT_CRC32 | MSPACK_HIP_FEAT_MD5 | MSPACK_HIP_FEAT_SHA1 | MSPACK_HIP_FEAT_SHA256 | MSPACK_HIP_FEAT_SLOTS; }

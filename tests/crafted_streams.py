@@ -103,12 +103,14 @@ class LzxBits:
         self.out, self.acc, self.n = bytearray(), 0, 0
 
     def put(self, v, n):
-        for k in range(n - 1, -1, -1):
-            self.acc = (self.acc << 1) | ((v >> k) & 1)
-            self.n += 1
-            if self.n == 16:
-                self.out += bytes((self.acc & 0xFF, self.acc >> 8))
-                self.acc, self.n = 0, 0
+        # (the low n bits of v, most significant first; whole words leave at once -- the fold cases write megabytes)
+        self.acc = (self.acc << n) | (v & ((1 << n) - 1))
+        self.n += n
+        while self.n >= 16:
+            self.n -= 16
+            w = (self.acc >> self.n) & 0xFFFF
+            self.out.append(w & 0xFF); self.out.append(w >> 8)
+            self.acc &= (1 << self.n) - 1
 
     def code(self, c):
         assert c is not None, "symbol without a code"
@@ -319,7 +321,7 @@ class Lzx:
         self.props.setdefault("offsets", []).append((off, self.pos))
         src = len(self.hist) - off
         for k in range(length):
-            self.hist.append(self.hist[src + k] if src + k >= 0 else 0)
+            self.hist.append(self.hist[src + k] if 0 <= src + k < len(self.hist) else 0)
             self._advance(1)
             if self.pos % FRAME == 0 and k + 1 < length:
                 self.fail = True           # (a match across a frame end: the cases that do this must fail)
@@ -376,16 +378,17 @@ class Deflate:
         self.props = {}
 
     def put(self, v, n):
-        for k in range(n):
-            self.acc |= ((v >> k) & 1) << self.n
-            self.n += 1
-            if self.n == 8:
-                self.out.append(self.acc); self.acc, self.n = 0, 0
+        # (the low n bits of v, least significant first; whole bytes leave at once)
+        self.acc |= (v & ((1 << n) - 1)) << self.n
+        self.n += n
+        while self.n >= 8:
+            self.out.append(self.acc & 0xFF)
+            self.acc >>= 8; self.n -= 8
 
     def code(self, c):
         assert c is not None, "symbol without a code"
-        for k in range(c[1] - 1, -1, -1):
-            self.put((c[0] >> k) & 1, 1)
+        # (a Huffman code goes most significant bit first: its bits reversed through the LSB-first writer)
+        self.put(int(format(c[0], "0%db" % c[1])[::-1], 2), c[1])
 
     def byte_align(self):
         if self.n:
@@ -865,11 +868,15 @@ def qtm_read_maxima(stream, out_len, wb):
 
 # ---- the cases --------------------------------------------------------------------------------------------------------
 class Case:
-    def __init__(self, name, codec, stream, out_len, wb=0, reset=0, ref=b"", tab=(), plain=None, err=ERR_OK, props=None, rooms=()):
+    def __init__(self, name, codec, stream, out_len, wb=0, reset=0, ref=b"", tab=(), plain=None, err=ERR_OK, props=None, rooms=(),
+                 folds=None):
         self.name, self.codec, self.stream, self.out_len = name, codec, stream, out_len
         self.wb, self.reset, self.ref, self.tab, self.plain, self.err = wb, reset, bytes(ref), list(tab), plain, err
         self.props = props or {}
         self.rooms = list(rooms)       # LZSS / LZH (wb: the LZSS mode): the rooms the unit is given, the first one ample
+        # fold_cases() only: the frames / blocks a fold task must finish under MSPACK_HIP_FOLD=2 (a frozenset), or None where
+        # that depends on timing (the cases that run the record pool dry)
+        self.folds = folds
 
     def __repr__(self):
         return "Case(%s)" % self.name
@@ -2373,7 +2380,445 @@ def kwaj_container(stream, method, length):
         length.to_bytes(4, "little") + stream
 
 
+# ---- hand-built folders at the fold tasks' and the record pool's limits ------------------------------------------------
+# (mspack_lzx_fold / mspack_mszip_fold: lzx_fold.hpp, fold_common.hpp, mszip_kernel.hpp zip_fold_block; RecWriter / RecPool in
+# wave_common.hpp.)  Units of up to 8 frames: not part of all_cases(), which tests/test_gpu_crafted.py repeats 600 times.
+# Every case carries `folds`: the frames (blocks) a fold task must finish when the launch runs them for every folder
+# (MSPACK_HIP_FOLD=2), read off the kernels:
+#   LZX   a frame is folded when its parse task emitted the whole frame (a verbatim or aligned block, tokens that end 56 bytes or
+#         more in front of in_len -- hence FOLD_PAD zero bytes behind every stream, so that a folder's LAST frame qualifies too),
+#         its records pass lzxd.c:613-634, the record pool had room for them, and every frame below it was folded;
+#   MSZIP a block is folded when it was parsed (no stored block in it), every block below it was folded and is a full one.
+FOLD_PAD = 128
+LEN_258 = [('d', (0 - l) % 17) for l in [2, 2] + [0] * 246] + [('r19', 4, 15)]      # footers 0, 1, 248, 249: matches of 9, 10, 257, 258
+REC_CHUNK, REC_CHUNKS, REC_POOL_PER_SLOT = 1024, 16, 6                              # wave_common.hpp
+
+
+def _fz(wb, total, reset=0, e8=0):
+    z = Lzx(wb, total, reset=reset, e8=e8)
+    z.props["matches"] = []            # (position, length, offset) of every match, as written
+    return z
+
+
+def _fblock(z, n=None):
+    """a verbatim block with every symbol in the main tree, over the next n bytes (default: the rest of the stream or of the
+    reset interval)"""
+    if n is None:
+        n = z.total - z.pos
+        if z.reset:
+            n = min(n, z.reset * FRAME - z.pos % (z.reset * FRAME))
+    z.block(1, n, main=flat_main(z.wb), len_ops=KEEP if any(z.lens[:250]) else LEN_258)
+
+
+def _fm(z, length, offset=None, rep=None):
+    p = z.pos
+    z.match(length, offset, rep=rep)
+    z.props["matches"].append((p, length, z.props["offsets"][-1][0]))
+
+
+def _flit(z, r, upto):
+    """seeded pseudo-random literals up to output position `upto`"""
+    assert upto >= z.pos, (upto, z.pos)
+    if upto > z.pos:
+        z.lit(bytes(r.getrandbits(8) for _ in range(upto - z.pos)))
+
+
+def _ftoks(z, r, base, toks, end):
+    """toks: {position in the frame: (length, first source position | ('rep', k))}; literals in between, up to base + end"""
+    for p in sorted(toks):
+        length, src = toks[p]
+        _flit(z, r, base + p)
+        if isinstance(src, tuple):
+            _fm(z, length, rep=src[1])
+        else:
+            _fm(z, length, base + p - src)
+    _flit(z, r, base + end)
+
+
+def _ordinary(z, r, base, fsz=FRAME, n=12):
+    """an ordinary frame: literals and a few short matches (under the shipped policy a folder whose first frame is long runs is
+    not folded: lzx_unit_runs, entry_kernels.hpp)"""
+    toks = {}
+    for k in range(n):
+        p = 500 + k * (fsz - 1000) // n
+        toks[p] = (3 + k % 7, base + p - (1 + (k * 37) % 400))
+    _ftoks(z, r, base, toks, fsz)
+
+
+def _fold_lzx_case(name, z, folds, err=ERR_OK, expect=None):
+    plain = z.plain() if err == ERR_OK else None
+    if err == ERR_OK:
+        assert not z.fail and z.pos == z.total, (name, z.pos, z.total)
+    nf = (z.total + FRAME - 1) // FRAME
+    assert len(z.tab) == nf, name
+    z.props["expect"] = expect or {}
+    if folds == "all":
+        folds = range(nf)
+    return Case(name, "lzx", z.stream(FOLD_PAD), z.total, z.wb, z.reset, b"", z.tab, plain, err, z.props,
+                folds=None if folds is None else frozenset(folds))
+
+
+def fold_lzx_cases():
+    C = []
+    R = random.Random
+
+    # ---- gather-step boundaries: fold_write_early / fold_write_late(0) / fold_write_late(1) are keyed on where a byte's source
+    # lies below the frame's base B: more than 64 KiB below (gathered early), bit 15 of source - (B - 64 KiB) clear (the frame two
+    # below) or set (the frame right below); B - 64 KiB wraps for frames 0 and 1.  Frames 0-1 literals; every later frame: matches
+    # of 2, 3 and 258 bytes whose first source byte is each of the boundaries, sources that straddle two frames (one match feeds two
+    # gather steps), offset 1 / 2 at the frame's first byte (root below the frame, the rest an in-frame chain), at the wave shares'
+    # edges (4095 / 4096 / 4097), at 8 * 4096 - 2 and at the frame's last bytes.  Every frame is a whole verbatim frame of valid
+    # matches: all eight fold.
+    total = 7 * FRAME + 1000
+    z = _fz(21, total); r = R(1001)
+    _fblock(z)
+    _ordinary(z, r, 0)
+    _flit(z, r, 2 * FRAME)
+    classes = {}
+    for f in range(2, 8):
+        B, fsz = f * FRAME, min(FRAME, total - f * FRAME)
+        srcs = [s for s in (B - 1, B - 2, B - 32767, B - 32768, B - 32769, B - 65535, B - 65536, B - 65537, B - 98304, 0,
+                            B - 65536 - 100, B - 32768 - 100) if s >= 0]
+        toks = {0: (258, B - 1 - (f & 1))}
+        p = 300
+        for L in ((2, 3, 258) if fsz == FRAME else (2, 3)):
+            for s in srcs:
+                toks[p] = (L, s); p += L + 1
+        assert p < min(4000, fsz - 258)
+        if fsz == FRAME:
+            toks[4095 + f % 3] = (258, srcs[f % len(srcs)])
+            toks[8 * 4096 - 2 - 258 * (f & 1) - 260] = (258, B - 32768 - 100)
+            if f & 1:
+                toks[FRAME - 258] = (258, B - 65536 - 100)
+            else:
+                toks[8 * 4096 - 2] = (2, B - 32768)
+        else:
+            toks[fsz - 258] = (258, B - 32768 - 100)
+        classes[f] = sorted(set(B - s for s in srcs))
+        _ftoks(z, r, B, toks, fsz)
+    C.append(_fold_lzx_case("fold_lzx_gather_step_boundaries", z, "all", expect=dict(below=classes)))
+
+    # ---- pointer chains: one frame per shape inside an 8-frame folder.  fold_jump_all ends when nothing moves (a pass resolves in
+    # address order, so a chain of n links needs about log2 n passes: 15 for the deepest here, under the cap of 64).  All fold.
+    z = _fz(21, 8 * FRAME); r = R(1002)
+    _fblock(z)
+    _ordinary(z, r, 0)
+    # frame 1: one literal, then offset-1 matches to the frame's end: byte b comes from b - 1, 32767 links
+    B = FRAME
+    _flit(z, r, B + 1)
+    for L in [258] * 126 + [257, 2]:
+        _fm(z, L, 1)
+    # frame 2: the same with the root in the frame below: the whole frame is the last byte of frame 1
+    for L in [258] * 127 + [2]:
+        _fm(z, L, 1)
+    # frame 3: offsets 2 and 3 in turn
+    B = 3 * FRAME
+    _flit(z, r, B + 3)
+    for k, L in enumerate([258] * 126 + [257]):
+        _fm(z, L, 2 + (k & 1))
+    # frame 4: a staircase: every match copies the match before it (offset = length = 257)
+    B = 4 * FRAME
+    _flit(z, r, B + 257)
+    for _ in range(126):
+        _fm(z, 257, 257)
+    _flit(z, r, B + FRAME)
+    # frame 5: links of 4097 bytes: every hop crosses a wave share (4096 bytes of a full frame)
+    B = 5 * FRAME
+    _flit(z, r, B + 4097)
+    for _ in range(111):
+        _fm(z, 258, 4097)
+    _flit(z, r, B + FRAME)
+    # frame 6: the last share copies the frame's first 128 bytes -- literals that lie in the record (edge_lit), not in the output, until
+    # the fold task stores them
+    B = 6 * FRAME
+    _flit(z, r, B + 7 * 4096)
+    for k in range(409):
+        _fm(z, 10, z.pos - (B + (k * 7) % 118))
+    _fm(z, 6, z.pos - B)
+    _ordinary(z, r, 7 * FRAME)
+    assert z.pos == 8 * FRAME
+    C.append(_fold_lzx_case("fold_lzx_pointer_chains", z, "all",
+                            expect=dict(depth_min={1: 32767, 2: 32767, 3: 10000, 4: 126, 5: 6, 6: 1})))
+
+    # ---- R0-R2 as placeholders: a frame's records are read before the three values in front of it are known; repeats only permute
+    # them, and the limit check (lzxd.c:613-634 for a value that is not there yet: the largest offset that passes) is made when they
+    # arrive.  Frame 0 sets (R0, R1, R2); frame 1 has no match; frames 2-7 begin with rep0 / rep1 / rep2 in the six orders and hold
+    # repeats only (every frame hands a permutation of three placeholders on), so what frame 7 copies with was set in frame 0; frame 7
+    # then replaces R0 by an explicit offset.  Valid offsets everywhere: all eight fold.
+    perms = [(0, 1, 2), (0, 2, 1), (1, 0, 2), (1, 2, 0), (2, 0, 1), (2, 1, 0)]
+    for reset in (0, 2):
+        z = _fz(21, 8 * FRAME, reset=reset); r = R(1003 + reset)
+        for f in range(8):
+            B = f * FRAME
+            starts = f == 0 or (reset and f % reset == 0)
+            if starts:
+                _fblock(z)
+            if f == 1 and not reset:
+                _flit(z, r, B + FRAME)
+                continue
+            if starts:
+                # (CHM style: behind a reset R0 = R1 = R2 = 1, the window is not cleared: a rep0 at the frame's first byte reaches below
+                # the reset, which lzxd.c allows)
+                if f:
+                    _fm(z, 5, rep=0)
+                _flit(z, r, B + 2000)
+                _fm(z, 4, 7); _fm(z, 3, 1234); _fm(z, 9, 1999 - f)          # R = (1999 - f, 1234, 7)
+                _flit(z, r, B + 20000); _fm(z, 258, rep=2); _fm(z, 2, rep=1)
+                _flit(z, r, B + FRAME)
+                continue
+            order = perms[(f - 2) % 6] if not reset else perms[(f // 2 + 2 * (f % 3)) % 6]
+            for k in order:
+                _fm(z, 3 + k, rep=k)
+            _flit(z, r, B + 300)
+            rr = R(f)
+            while z.pos < B + FRAME - 600:
+                _fm(z, rr.choice((2, 3, 9, 10, 257, 258)), rep=rr.randrange(3))
+                _flit(z, r, z.pos + rr.randrange(1, 200))
+            if f == 7:
+                _fm(z, 8, 4321)                                                # R0 replaced
+            _flit(z, r, B + FRAME)
+        firsts = [f for f in range(8) if f == 0 or (reset and f % reset == 0)]
+        C.append(_fold_lzx_case("fold_lzx_placeholders" + ("_reset_2" if reset else ""), z, "all",
+                                expect=dict(placeholder_frames=[f for f in range(2 if not reset else 1, 8) if f not in firsts])))
+    # odd values come out of a stored block's header (lzxd.c:551-557).  The frame in a stored block has no parse task's record and ends
+    # the chain of code lengths for the frames behind it: no frame from that one on is folded, and the serial path answers -- (0, 70000,
+    # 0x7FFFFFFF): rep0 with offset 0 copies the window onto itself, rep1 reaches 70000 back, rep2 is rejected (lzxd.c:618-625);
+    # (window size, 1, 1) in a 2^16 window behind 128 KiB of output: the byte one whole window back, which the reference takes
+    for name, wb, Rs, err in (("zero_70000_huge", 21, (0, 70000, 0x7FFFFFFF), ERR_DECRUNCH), ("window_size", 16, (1 << 16, 1, 1), ERR_OK)):
+        z = _fz(wb, 6 * FRAME); r = R(1010 + wb)
+        _fblock(z, 4 * FRAME)
+        _ordinary(z, r, 0)
+        for f in (1, 2, 3):
+            _ordinary(z, r, f * FRAME, n=40)
+        z.block(3, FRAME, R=Rs); z.raw(bytes(r.getrandbits(8) for _ in range(FRAME)))
+        _fblock(z, FRAME)
+        _fm(z, 5, rep=0); _fm(z, 6, rep=1)
+        _fm(z, 7, rep=2)
+        if err == ERR_OK:
+            _flit(z, r, 6 * FRAME)
+        C.append(_fold_lzx_case("fold_lzx_stored_block_sets_r0_r2_" + name, z, range(4), err=err))
+
+    # ---- record counts: the fold task reads a frame's records 256 at a time, 64 to a batch; the parse task takes a chunk of 1024
+    # records from the launch's pool as it needs one, 16 chunks to a frame at most.  Two-byte matches, the rest literals.  Pool:
+    # REC_POOL_PER_SLOT = 6 chunks per frame slot, a unit of n full frames has n + 1 slots.  Folder A (9 slots, 54 chunks) takes
+    # 1 + 0 + 1 + 1 + 1 + 1 + 1 + 1 = 7; folder B (7 full frames: 8 slots, 48 chunks) 1 + 1 + 1 + 1 + 2 + 4 + 16 = 26 -- its frame of
+    # 16384 matches (the whole frame: n_chunks == REC_CHUNKS exactly) is the last one and the only one of its size.  All fold.
+    for name, counts in (("a", [12, 0, 1, 63, 64, 65, 255, 256]), ("b", [12, 257, 1023, 1024, 1025, 4096, 16384])):
+        nf = len(counts)
+        z = _fz(21, nf * FRAME); r = R(1020 + nf)
+        _fblock(z)
+        _ordinary(z, r, 0)
+        for f in range(1, nf):
+            B, n = f * FRAME, counts[f]
+            if n == 16384:
+                for _ in range(n):
+                    _fm(z, 2, 40000)
+                continue
+            for k in range(n):
+                _flit(z, r, B + k * FRAME // n + 1)
+                _fm(z, 2, 3 + 32768 * (k & 1))
+            _flit(z, r, B + FRAME)
+        chunks = sum((n + REC_CHUNK - 1) // REC_CHUNK for n in counts)
+        assert chunks <= REC_POOL_PER_SLOT * (nf + 1) and max(counts) <= REC_CHUNK * REC_CHUNKS
+        C.append(_fold_lzx_case("fold_lzx_record_counts_" + name, z, "all", expect=dict(records=dict(enumerate(counts)))))
+
+    # ---- the pool runs dry: frames 1-7 hold 16384 two-byte matches each: 1 + 7 * 16 = 113 chunks, and the unit's 9 slots bring 54.
+    # RecWriter::ensure answers false, the parse task stops there with a partial record, the chain of folded frames ends at that frame
+    # and the serial path decodes the rest.  Which frame finds the pool empty depends on which parse task took its chunks first:
+    # folds is None (the folded frames are a prefix of the folder; parity must hold whatever happens).
+    for name in ("offset_32768", "rep0"):
+        z = _fz(21, 8 * FRAME); r = R(1030)
+        _fblock(z)
+        _ordinary(z, r, 0)
+        for f in range(1, 8):
+            for k in range(16384):
+                if name == "rep0" and (f, k) != (1, 0):
+                    _fm(z, 2, rep=0)
+                else:
+                    _fm(z, 2, 32768)
+        C.append(_fold_lzx_case("fold_lzx_pool_runs_dry_" + name, z, None, expect=dict(records={f: 16384 for f in range(1, 8)})))
+    # ... and the ordinary six-frame folder that shares a launch, and so a pool, with one of them
+    z = _fz(21, 6 * FRAME); r = R(1031)
+    _fblock(z)
+    for f in range(6):
+        _ordinary(z, r, f * FRAME, n=300)
+    C.append(_fold_lzx_case("fold_lzx_pool_neighbour", z, "all"))
+
+    # ---- short last frames: fold_share rounds a wave's share to 256 bytes, so a tail of 1 to 2049 bytes leaves waves without a share,
+    # and the tail has a list of its own.  Four full frames, then a tail of matches from the frame below and from three frames below
+    # (a tail of one byte can only be a literal).  All fold.
+    for tail in (1, 2, 255, 256, 257, 2049):
+        total = 4 * FRAME + tail
+        z = _fz(21, total); r = R(1040 + tail)
+        _fblock(z)
+        for f in range(4):
+            _ordinary(z, r, f * FRAME)
+        B = 4 * FRAME
+        k = 0
+        while total - z.pos >= 2:
+            left = total - z.pos
+            L = 258 if left >= 260 else min(left, 10)
+            _fm(z, L, (32768 - 5 * k) if k & 1 == 0 else (3 * 32768 - 11 * k))
+            k += 1
+        _flit(z, r, total)
+        C.append(_fold_lzx_case("fold_lzx_short_last_frame_%d" % tail, z, "all", expect=dict(records={4: k})))
+
+    # ---- the window's wrap: the fold task works in positions of the unit's output, the reference in a window of 2^15 or 2^16 bytes:
+    # offsets at the largest value the window allows (window size - 3) and one below; for 2^16 sources whose bytes lie on both sides of
+    # the window's end.  Six frames; all fold.
+    for wb in (15, 16):
+        ws = 1 << wb
+        z = _fz(wb, 6 * FRAME); r = R(1050 + wb)
+        _fblock(z)
+        _ordinary(z, r, 0)
+        if wb == 16:
+            _ordinary(z, r, FRAME)
+        for f in range(z.pos // FRAME, 6):
+            B = f * FRAME
+            toks = {}
+            for k, p in enumerate((0, 5, 700, 4095, 20000, 32000)):
+                toks[p] = ((2, 3, 258)[k % 3], B + p - (ws - 3 - (k & 1)))
+            if wb == 16 and f & 1:
+                toks[FRAME - 4] = (3, B + FRAME - 4 - (ws - 3))       # window positions 65535, 0, 1
+            _ftoks(z, r, B, toks, FRAME)
+        C.append(_fold_lzx_case("fold_lzx_window_wrap_w%d" % wb, z, "all", expect=dict(max_offset=ws - 3)))
+
+    # ---- E8 behind the fold: the translation (lzxd.c:699-736) is applied to a frame after its bytes left the window, so frame 2's
+    # matches copy frame 1's CALLs UNTRANSLATED, and both frames are translated afterwards, each at its own positions.  All fold.
+    z = _fz(21, 4 * FRAME, e8=3000000); r = R(1060)
+    _fblock(z)
+    _ordinary(z, r, 0)
+    B = FRAME
+    while z.pos < B + FRAME - 40:
+        z.lit(b"\xe8" + r.randrange(-z.pos, 3000000).to_bytes(4, "little", signed=True))
+        _flit(z, r, z.pos + r.randrange(0, 12))
+    _flit(z, r, B + FRAME)
+    B = 2 * FRAME
+    while z.pos < B + FRAME - 300:
+        _fm(z, r.choice((5, 10, 258)), FRAME + r.randrange(-3, 4))
+        _flit(z, r, z.pos + r.randrange(0, 4))
+    _flit(z, r, B + FRAME)
+    _ordinary(z, r, 3 * FRAME)
+    c = _fold_lzx_case("fold_lzx_e8_behind_the_fold", z, "all")
+    assert c.props["e8_translated"][1] > 1000 and c.props["e8_translated"][2] > 100
+    C.append(c)
+    return C
+
+
+def _fold_mszip_case(name, d, folds, expect=None):
+    d.props["expect"] = expect or {}
+    n = len(d.tab)
+    c = Case(name, "mszip", d.stream(FOLD_PAD), len(d.plain), tab=d.tab, plain=bytes(d.plain), props=d.props,
+             folds=frozenset(range(n) if folds == "all" else folds))
+    return c
+
+
+def _zblock(d, r, toks, size=FRAME):
+    """a CK block of `size` bytes: toks {position in the block: (length, distance)}, seeded literals in between"""
+    d.frame()
+    start = len(d.plain)
+    out, p = [], 0
+    for q in sorted(toks):
+        assert q >= p, (q, p)
+        if q > p:
+            out.append(('L', bytes(r.getrandbits(8) for _ in range(q - p))))
+        out.append(('M',) + tuple(toks[q]))
+        p = q + toks[q][0]
+    assert p <= size, (p, size)
+    if size > p:
+        out.append(('L', bytes(r.getrandbits(8) for _ in range(size - p))))
+    d.fixed(out, last=1)
+    assert len(d.plain) - start == size
+    d.props.setdefault("matches", []).append([(q,) + tuple(toks[q]) for q in sorted(toks)])
+
+
+def _zordinary(k=20, size=FRAME):
+    """an ordinary block's tokens: a few short matches (blocks of long runs divert a folder under the shipped policy)"""
+    return {p: (3 + i % 9, 1 + (i * 53) % 390) for i, p in ((i, 400 + i * 1500) for i in range(k)) if p + 12 <= size}
+
+
+def fold_mszip_cases():
+    C = []
+    R = random.Random
+    # ---- distances at the block's edges (zip_fold_block: a source below the block only within the 32 KiB right below it): dist = rpos + 1
+    # (the last byte of the block below), 32768 -- the largest a distance code states, so rpos + 32768 exists at rpos 0 only -- at rpos 0, 1
+    # and 4096 (the same position of the block below), 32768 at the block's last match, 258
+    # bytes at rpos 0 with distance 1 (begins below the block, runs into it).  Full blocks of valid matches: all fold.
+    d = Deflate(); r = R(2001)
+    _zblock(d, r, _zordinary())
+    _zblock(d, r, {0: (3, 32768), 3: (4, 4), 4096: (10, 32768), 9000: (258, 9001), FRAME - 3: (3, 32768)})
+    _zblock(d, r, {0: (258, 1), 258: (258, 32768), 1000: (3, 1001), 4096: (258, 4097), FRAME - 258: (258, 32768)})
+    _zblock(d, r, {1: (5, 32768), 4095: (258, 32768), 8 * 4096 - 3: (3, 8 * 4096 - 2)})
+    _zblock(d, r, _zordinary(size=1000), size=1000)
+    C.append(_fold_mszip_case("fold_mszip_distances_at_the_block_edges", d, "all", expect=dict(max_dist=32768)))
+
+    # ---- one literal, then distance-1 matches to the block's end: 32767 links.  (Its first block is ordinary, but blocks of runs divert
+    # a folder under the shipped policy: this one runs with policy 2 only.)
+    d = Deflate(); r = R(2002)
+    _zblock(d, r, _zordinary())
+    toks, p = {}, 1
+    while p < FRAME:
+        L = min(258, FRAME - p)
+        if 0 < FRAME - p - L < 3:
+            L -= 3
+        toks[p] = (L, 1); p += L
+    _zblock(d, r, toks)
+    _zblock(d, r, {0: (258, 1), 258: (258, 1)})
+    c = _fold_mszip_case("fold_mszip_chain_of_32767_links", d, "all", expect=dict(depth_min={1: 32767}))
+    c.props["policy_2_only"] = True
+    C.append(c)
+
+    # ---- blocks of exactly 0, 1, 64, 65, 256, 257, 1024, 1025 and 10922 matches of three bytes (the record groups, the pool's chunk,
+    # the most a block can hold): an 8-block folder has 8 slots = 48 chunks and needs 1 + 0 + 1 + 1 + 1 + 1 + 1 + 1 and 1 + 2 + 11.  All fold.
+    for name, counts in (("a", [20, 0, 1, 64, 65, 256, 257, 1024]), ("b", [20, 1025, 10922])):
+        d = Deflate(); r = R(2003)
+        _zblock(d, r, _zordinary())
+        for n in counts[1:]:
+            if n == 10922:
+                toks = {2 + 3 * k: (3, 2 + (k % 5) * 4000) for k in range(n)}
+            else:
+                toks = {1 + k * (FRAME // max(n, 1)): (3, 32768 if k & 1 else 1) for k in range(n)}
+            _zblock(d, r, toks)
+        C.append(_fold_mszip_case("fold_mszip_record_counts_" + name, d, "all", expect=dict(records=dict(enumerate(counts)))))
+
+    # ---- short blocks: a block is folded when the block below it is a FULL one that was folded: the block behind a short one has its
+    # history elsewhere than in the 32 KiB right below its position, so it and every block behind it are the folder's own wave's.
+    # A 20000-byte block in the middle (block 2 of six: 0, 1, 2 fold), a short first block (only block 0), a short last block (all).
+    for name, sizes, folds in (("short_block_in_the_middle", [FRAME, FRAME, 20000, FRAME, FRAME, FRAME], (0, 1, 2)),
+                               ("short_first_block", [20000, FRAME, FRAME, FRAME], (0,)),
+                               ("short_last_block", [FRAME, FRAME, FRAME, 20000], "all")):
+        d = Deflate(); r = R(2004)
+        for b, size in enumerate(sizes):
+            toks = _zordinary(12)
+            if b:
+                toks[0] = (10, min(32768, len(d.plain)))
+                # (below the block: behind a full block its last bytes; behind a short one bytes 18000.. of that block, which still
+                # lie in the window -- the reference's window is not cleared, so nothing may read what no block wrote)
+                toks[15000] = (258, 15000 + 5 if sizes[b - 1] == FRAME else 32768 - 3000)
+            _zblock(d, r, toks, size=size)
+        C.append(_fold_mszip_case("fold_mszip_" + name, d, folds, expect=dict(sizes=sizes)))
+
+    # ---- a stored block in the middle: the parse task gives a block with a stored deflate block up, and the chain of folded blocks ends
+    # there: blocks 0 and 1 fold, 2 (stored) and the ones behind it do not.
+    d = Deflate(); r = R(2005)
+    _zblock(d, r, _zordinary())
+    _zblock(d, r, {0: (258, 32768), 5000: (100, 5001)})
+    d.frame(); d.stored(bytes(r.getrandbits(8) for _ in range(FRAME)), last=1)
+    d.props["matches"].append([])
+    _zblock(d, r, {0: (258, 32768), 5000: (100, 5001)})
+    _zblock(d, r, _zordinary(size=3000), size=3000)
+    C.append(_fold_mszip_case("fold_mszip_stored_block_in_the_middle", d, (0, 1), expect=dict(stored=[2])))
+    return C
+
+
 _CACHE = {}
+
+
+def fold_cases():
+    """the hand-built folders at the fold tasks' limits, built once (nobody changes a case).  NOT part of all_cases()"""
+    if "fold" not in _CACHE:
+        _CACHE["fold"] = fold_lzx_cases() + fold_mszip_cases()
+    return list(_CACHE["fold"])
 
 
 def lz_cases():

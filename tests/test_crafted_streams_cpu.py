@@ -373,6 +373,109 @@ def test_lzss_lzh_cases_have_the_property_they_name():
     assert n_in >= 400
 
 
+# ---- the hand-built folders at the fold tasks' limits (CS.fold_cases(): not part of all_cases()) ----
+FOLD = CS.fold_cases()
+FRAME = CS.FRAME
+
+
+@pytest.mark.parametrize("c", FOLD, ids=[c.name for c in FOLD])
+def test_fold_cases_through_the_oracle_and_the_reference(built, c):
+    """err and out_len of oracle and reference are equal and the bytes are the case's own plaintext: a case is only worth anything
+    if the reference accepts it (or rejects it with the code the case states)"""
+    e, o, r = run_oracle(c)
+    assert e == c.err, (e, c.err)
+    if c.plain is not None:
+        assert e == 0 and r.out_len == c.out_len == len(c.plain)
+        assert o == c.plain, "differs at byte %d" % next(k for k in range(len(o)) if o[k] != c.plain[k])
+    if have_ref():
+        re, ro, rw = ref_lzx(c.stream, c.out_len, c.wb, c.reset) if c.codec == "lzx" else ref_mszip(c.stream, c.out_len)
+        assert re == e and rw == r.out_len and ro == o[:rw], (re, e, rw, r.out_len)
+
+
+def fold_frame_matches(c):
+    """per frame / block: [(position in it, length, offset)]"""
+    if c.codec == "mszip":
+        return dict(enumerate(c.props["matches"]))
+    per = {}
+    for p, n, off in c.props["matches"]:
+        per.setdefault(p // FRAME, []).append((p % FRAME, n, off))
+    return per
+
+
+def fold_chain_depth(ms, size=FRAME):
+    """the longest chain of copies inside one frame: links from a byte to the literal, or the byte below the frame, it comes from"""
+    depth = [0] * size
+    for p, n, off in ms:
+        for b in range(p, p + n):
+            depth[b] = depth[b - off] + 1 if b - off >= 0 else 0
+    return max(depth)
+
+
+def test_fold_cases_have_the_property_they_name():
+    """measured on what the builders wrote, not declared: record counts, the deepest chain, the classes of source distance"""
+    assert len({c.name for c in FOLD}) == len(FOLD) >= 28
+    assert not {c.name for c in FOLD} & {c.name for c in CASES}
+    assert all((c.folds is None) == c.name.startswith("fold_lzx_pool_runs_dry_") for c in FOLD)
+    assert all(c.out_len <= 8 * FRAME + 1000 for c in FOLD)
+    F = {c.name: c for c in FOLD}
+    for c in FOLD:
+        per, x = fold_frame_matches(c), c.props["expect"]
+        for f, n in x.get("records", {}).items():
+            assert len(per.get(f, [])) == n, (c.name, f, len(per.get(f, [])), n)
+        for f, n in x.get("depth_min", {}).items():
+            assert fold_chain_depth(per[f]) >= n, (c.name, f, fold_chain_depth(per[f]), n)
+        for f, classes in x.get("below", {}).items():
+            got = {off - p for p, n, off in per[f] if off > p}              # how far below the frame's base a match begins
+            assert set(classes) <= got, (c.name, f, sorted(set(classes) - got))
+            lens = {(off - p, n) for p, n, off in per[f]}
+            assert all((d, n) in lens for d in classes for n in ((2, 3, 258) if f < 7 else (2, 3))), (c.name, f)
+    g = F["fold_lzx_gather_step_boundaries"]
+    for f in range(3, 7):
+        assert {1, 2, 32767, 32768, 32769, 65535, 65536, 65537, 98304, f * FRAME} <= set(g.props["expect"]["below"][f])
+        ms = fold_frame_matches(g)[f]
+        assert ms[0][:2] == (0, 258) and ms[0][2] in (1, 2)                 # root below the frame, the rest an in-frame chain
+        assert {p for p, _n, _o in ms} & {4095, 4096, 4097} and max(p + n for p, n, _o in ms) == FRAME
+        # one match whose source bytes lie in two frames: f-3 / f-2 and f-2 / f-1
+        assert any(off - p > 65536 > off - p - n for p, n, off in ms) and any(off - p > 32768 > off - p - n for p, n, off in ms)
+    assert fold_chain_depth(fold_frame_matches(F["fold_lzx_pointer_chains"])[1]) == 32767
+    # every hop of frame 5's chain crosses a wave share; frame 6 copies the frame's first 128 bytes from its last share
+    pc = fold_frame_matches(F["fold_lzx_pointer_chains"])
+    assert all(off == 4097 for _p, _n, off in pc[5]) and all(p >= 7 * 4096 and p - off + n <= 128 for p, n, off in pc[6])
+    for name in ("fold_lzx_placeholders", "fold_lzx_placeholders_reset_2"):
+        c = F[name]
+        reps = {p for p, _k, _v in c.props["reps"]}
+        first_is_rep = [f for f, ms in sorted(fold_frame_matches(c).items()) if f * FRAME + ms[0][0] in reps]
+        firsts = [f for f in range(8) if f == 0 or (c.reset and f % c.reset == 0)]
+        assert [f for f in first_is_rep if f not in firsts] == c.props["expect"]["placeholder_frames"], (name, first_is_rep)
+        orders = {tuple(k for p, k, _v in c.props["reps"] if p // FRAME == f)[:3] for f in c.props["expect"]["placeholder_frames"]}
+        assert len(orders) == (6 if not c.reset else 4), (name, orders)
+        if c.reset:
+            assert all(f * FRAME in reps for f in firsts[1:])               # a repeat right behind every reset: it reaches below it
+        else:
+            assert 1 not in fold_frame_matches(c)                           # a frame without a match
+            assert all(f * FRAME + p in reps for f in range(2, 7) for p, _n, _o in fold_frame_matches(c)[f])   # repeats only
+    for name in ("fold_lzx_pool_runs_dry_offset_32768", "fold_lzx_pool_runs_dry_rep0"):
+        per = fold_frame_matches(F[name])
+        need = sum((len(ms) + CS.REC_CHUNK - 1) // CS.REC_CHUNK for ms in per.values())
+        assert need == 113 > CS.REC_POOL_PER_SLOT * 9 and all(n == 2 for ms in per.values() if len(ms) > 100 for _p, n, _o in ms)
+    for wb in (15, 16):
+        offs = {off for _p, _n, off in F["fold_lzx_window_wrap_w%d" % wb].props["matches"]}
+        assert {(1 << wb) - 3, (1 << wb) - 4} <= offs and max(offs) == (1 << wb) - 3
+    for t in (1, 2, 255, 256, 257, 2049):
+        c = F["fold_lzx_short_last_frame_%d" % t]
+        ms = fold_frame_matches(c).get(4, [])
+        assert c.out_len == 4 * FRAME + t and sum(n for _p, n, _o in ms) >= t - 1
+        assert t == 1 or ({(off - p + FRAME - 1) // FRAME for p, _n, off in ms} == ({1, 3} if t > 2 else {1}))
+    z = F["fold_mszip_distances_at_the_block_edges"]
+    assert z.props["max_dist"] == 32768
+    per = fold_frame_matches(z)
+    assert all(any(d == q + 1 for q, _n, d in per[b]) for b in (1, 2, 3)) and per[2][0] == (0, 258, 1)
+    assert {q for b in (1, 2, 3) for q, _n, d in per[b] if d == 32768} >= {0, 1, 4096, FRAME - 3, FRAME - 258}
+    sizes = F["fold_mszip_short_block_in_the_middle"].props["expect"]["sizes"]
+    assert sizes[2] == 20000 and len(F["fold_mszip_short_block_in_the_middle"].plain) == sum(sizes)
+    assert F["fold_mszip_stored_block_in_the_middle"].props["stored_lens"] == [FRAME]
+
+
 # the emulator run leaves out (at most two, by name): minutes each there, milliseconds on the GPU, which leaves out none
 EMU_LEAVES_OUT = ("qtm_literal_length_position_models_alternating_w10", "qtm_literal_length_position_models_alternating_w17")
 

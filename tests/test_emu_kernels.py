@@ -168,6 +168,53 @@ def test_fold_tasks_on_the_emulator(built, tmp_path):
     assert p.returncode == 0 and b"EMU_FOLD_OK" in p.stdout, p.stdout.decode()[-3000:]
 
 
+FOLD_CRAFTED_WORKER = r'''
+import sys
+sys.path.insert(0, %r); sys.path.insert(0, %r + "/tests")
+import libmspack_amd as M
+import test_gpu_fold_crafted as G
+assert "emu" in M.HIP_SO
+for c in G.CS.fold_cases():
+    print("CASE %%s" %% c.name, flush=True)
+    res, words = G.run_device([c], "emulator")                 # (parity against the oracle and the case's plaintext, guard bytes)
+    G.check_words(c, words[0], res[0], 2, "emulator")
+    print("WORDS %%s" %% " ".join(str(f) for f in sorted(G.folded(c, words[0])[0])), flush=True)
+print("EMU_FOLD_CRAFTED_OK")
+'''
+
+
+@pytest.mark.skipif(not os.path.exists(CLANG), reason="the emulator build needs ROCm's clang++")
+def test_hand_built_folders_through_the_fold_tasks_on_the_emulator(built, tmp_path):
+    """every folder of tests/crafted_streams.py fold_cases() through mspack_lzx_fold / mspack_mszip_fold on the wavefront emulator
+    (MSPACK_HIP_FOLD=2; 1 to 6 s each, 70 s in all): parity, and the fold task's own trace line says `ok 1` for every frame the case
+    expects folded -- `placeholders 1` where the case's frames begin with repeats of R0-R2 that the frame below has yet to hand over --
+    and the frame words (mspack_hip_debug_frame_words) name exactly those frames.  The emulator runs a task on ONE wave: the wave
+    shares are the GPU's business (tests/test_gpu_fold_crafted.py)."""
+    import re
+    import crafted_streams as CS
+    so = emu_so()
+    script = tmp_path / "w.py"
+    script.write_text(FOLD_CRAFTED_WORKER % (ROOT, ROOT))
+    env = dict(os.environ, MSPACK_HIP_SO=so, MSPACK_HIP_FOLD="2", MSPACK_EMU_FOLD_TRACE="1")
+    p = subprocess.run([sys.executable, str(script)], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=1500)
+    text = p.stdout.decode()
+    assert p.returncode == 0 and "EMU_FOLD_CRAFTED_OK" in text, text[-3000:]
+    parts = {s.split("\n", 1)[0].strip(): s for s in text.split("CASE ")[1:]}
+    for c in CS.fold_cases():
+        s = parts[c.name]
+        if c.codec == "lzx":
+            ok = {int(m.group(1)): (int(m.group(2)), int(m.group(3)))
+                  for m in re.finditer(r"lzx_fold_frame: frame (\d+): \d+ records, \d+ bytes, placeholders (\d), ok (\d)", s)}
+        else:
+            ok = {int(m.group(1)): (0, int(m.group(2))) for m in re.finditer(r"zip_fold_block: block (\d+): \d+ records, \d+ bytes, ok (\d)", s)}
+        if c.folds is None:
+            continue
+        assert all(ok.get(f, (0, 0))[1] == 1 for f in c.folds), (c.name, sorted(c.folds), ok)
+        for f in c.props["expect"].get("placeholder_frames", ()):
+            assert ok[f][0] == 1, (c.name, f, ok)
+        assert "WORDS %s\n" % " ".join(str(f) for f in sorted(c.folds)) in s, (c.name, s[-300:])
+
+
 STREAM_WORKER = r'''
 import sys
 sys.path.insert(0, %r); sys.path.insert(0, %r + "/tests")
