@@ -406,6 +406,37 @@ struct msszdd_decompressor {
 extern struct msszdd_decompressor *mspack_create_szdd_decompressor(struct mspack_system *sys);
 extern void mspack_destroy_szdd_decompressor(struct msszdd_decompressor *self);
 
+/* extension of this library (plain functions: the decompressor structs keep the reference's layout).
+ *
+ * Decode the coded streams of MANY open SZDD files in ONE GPU batch and keep each file's bytes with its header, so that the
+ * extract() calls that follow only write.  Advice: what extract() returns, writes, reports through last_error() and says through
+ * sys->message is the same with and without it.
+ *
+ * Without it every extract() is a batch of one unit -- its own launch, arenas and copy back; an installation medium of thousands of
+ * `*.ex_` / `*.dl_` files is then thousands of batches.
+ *   hdrs[i]   headers this decompressor opened; NULL entries, an entry given twice, a header of another decompressor and a header that
+ *             holds its bytes already are skipped.
+ *   reads     The call seeks to and reads every member's coded bytes through sys->seek / sys->tell / sys->read: the sys->read calls of
+ *             the later extract() have moved HERE.  extract() of a held member calls sys->seek, sys->open, sys->write and sys->close
+ *             as ever, and no sys->read.
+ *   room      A member's unit gets the length its header states as room when that lies in (0, largest possible expansion], else the
+ *             largest possible expansion (what a solitary extract() gives it).  A member whose stream produced more than its room is
+ *             decoded again, alone, by its extract() -- today's path; the answer is the same.
+ *   left out  A member whose bytes cannot be read, and a member that would push the decoded bytes this decompressor keeps past
+ *             mspack_hip_cache_mb(), stay out of the batch: their extract() runs as ever and reports what it reports today.
+ *   lifetime  A member's bytes are released by the extract() that writes them (a second extract() of the same header decodes it again,
+ *             as ever) or by close(); headers may be closed in any order, also before they are extracted.
+ *   returns   MSPACK_ERR_OK (also when nothing was left to decode: no batch is started then); MSPACK_ERR_ARGS for self == NULL,
+ *             hdrs == NULL or n <= 0; MSPACK_ERR_NOMEMORY; MSPACK_ERR_DECRUNCH when the batch call itself failed ("GPU batch decode
+ *             failed: ..." is said then, and nothing of the batch is kept).  last_error() answers the same.  Synchronous.
+ * LZSS members carry MSPACK_HIP_UF_LZSS_RING (no 4096 bytes below the unit) when the provider of the batch ABI reports
+ * MSPACK_HIP_FEAT_LZSS_RING.  decompress(input, output) is unchanged: one file, one batch. */
+extern int mspack_szddd_prefetch(struct msszdd_decompressor *self, struct msszddd_header **hdrs, int n);
+/* diagnostics: counts[0] the batch calls the SZDD driver has issued in this process (a solitary extract() is one, a prefetch is one),
+ * counts[1] the extract() calls answered from a prefetch batch, counts[2] the members decoded again alone because they did not fit
+ * their room; counts may be NULL; reset != 0 clears them after reading */
+extern void mspack_szddd_batch_counts(unsigned long long counts[3], int reset);
+
 /* ---- KWAJ (reference mspack.h:1978-2036, 2156-2250) ----------------------------------------------------- */
 #define MSKWAJ_COMP_NONE (0)
 #define MSKWAJ_COMP_XOR (1)
@@ -436,6 +467,15 @@ struct mskwaj_decompressor {
 };
 extern struct mskwaj_decompressor *mspack_create_kwaj_decompressor(struct mspack_system *sys);
 extern void mspack_destroy_kwaj_decompressor(struct mskwaj_decompressor *self);
+/* mspack_szddd_prefetch for KWAJ files, every word of it: methods 2 (LZSS), 3 (LZH) and 4 (MSZIP) go into the same batch -- LZH keeps
+ * its 4096 bytes below the unit, MSZIP its 32 KiB of slack and a room rounded up to whole 32 KiB blocks (the decoder starts a block only
+ * with a whole block of room left); a header's length counts when MSKWAJ_HDR_HASLENGTH is set; LZH and MSZIP
+ * members answer their unit's error code behind the bytes they produced, as their extract() does today.  Methods 0 and 1 (stored)
+ * and unknown methods are left to extract() as ever. */
+extern int mspack_kwajd_prefetch(struct mskwaj_decompressor *self, struct mskwajd_header **hdrs, int n);
+extern void mspack_kwajd_batch_counts(unsigned long long counts[3], int reset);
+/* diagnostic: the LZSS members of both drivers' prefetch batches that went out with MSPACK_HIP_UF_LZSS_RING; reset != 0 clears it */
+extern unsigned long long mspack_szdd_kwaj_ring_units(int reset);
 
 /* ---- OAB (Offline Address Book, LZX DELTA) -------------------------------------------------------------- */
 /* reference mspack.h:663-683, 2300-2380 */

@@ -36,7 +36,8 @@ extern "C" {
 #define MSPACK_HIP_KIND_LZSS     5   /* lzss_decompress (lzssd.c:36-91): SZDD, KWAJ method 2; window_bits = mode
                                        (0 EXPAND, 1 MSHELP, 2 QBASIC).  The stream carries no length: out_len is
                                        the room available, the result's out_len what the stream produced.  The
-                                       4096 bytes below out_off belong to the unit (its window pre-fill).        */
+                                       4096 bytes below out_off belong to the unit (its window pre-fill) -- unless
+                                       it carries MSPACK_HIP_UF_LZSS_RING.                                       */
 #define MSPACK_HIP_KIND_KWAJ_LZH 6   /* lzh_decompress (kwajd.c:432-563): KWAJ method 3; same conventions         */
 #define MSPACK_HIP_KIND_XORSUM   7   /* cabd_checksum(data, bytes, 0) (cabd.c:1462-1479): the checksum of ONE CFDATA block's
                                        payload -- the XOR of its little-endian dwords and the reference's odd big-endian tail of
@@ -85,6 +86,7 @@ extern "C" {
 
 #define MSPACK_HIP_MASK_FRAME_TABLES 0x80000000u   /* mspack_hip_decode_batch_device(kind_mask): see there */
 #define MSPACK_HIP_MASK_CRC32        0x40000000u   /* mspack_hip_decode_batch_device(kind_mask): units may carry MSPACK_HIP_UF_CRC32 */
+#define MSPACK_HIP_MASK_LZSS_RING    0x20000000u   /* mspack_hip_decode_batch_device(kind_mask): LZSS units may carry MSPACK_HIP_UF_LZSS_RING */
 
 /* result flags */
 #define MSPACK_HIP_F_E8_APPLIED     1u  /* >=1 frame went through the E8 translation (lzxd.c:706-736) */
@@ -152,6 +154,16 @@ extern "C" {
                                            ignored).  Rejected on MSPACK_HIP_KIND_XORSUM units (the host entry points return an error).
                                            Ask mspack_hip_features() & MSPACK_HIP_FEAT_CRC32 before setting it on a library of unknown age */
 
+#define MSPACK_HIP_UF_LZSS_RING   256u  /* MSPACK_HIP_KIND_LZSS only (ignored on every other kind): the unit keeps its 4096-byte window in LDS
+                                           and owns NOTHING below out_off -- out_off may be 0 and may have any alignment.  err, flags,
+                                           out_len, in_used, good_len and in_next are those of the same unit without the flag, and so are
+                                           the first min(unit.out_len, result.out_len) bytes of its region; result.out_len stays what
+                                           the stream produced, also beyond the room; bytes beyond the room are dropped and no byte
+                                           outside [out_off, out_off + unit.out_len) is written.  Modes 0, 1 and 2 as without the flag,
+                                           window_bits > 2 answers MSPACK_ERR_ARGS.  Flagged and unflagged units may share a batch, on
+                                           every entry point (the device-resident one: see MSPACK_HIP_MASK_LZSS_RING).
+                                           Ask mspack_hip_features() & MSPACK_HIP_FEAT_LZSS_RING before setting it */
+
 typedef struct mspack_hip_unit {
   uint64_t in_off;       /* byte offset of the unit's compressed bytes in the input arena          */
   uint64_t out_off;      /* byte offset of the unit's output in the output arena                   */
@@ -209,6 +221,7 @@ const char *mspack_hip_last_error(void);
 #define MSPACK_HIP_FEAT_SHA1   4u       /* MSPACK_HIP_KIND_SHA1 (and MSPACK_HIP_KIND_DIGEST_MORE) */
 #define MSPACK_HIP_FEAT_SHA256 8u       /* MSPACK_HIP_KIND_SHA256 (and MSPACK_HIP_KIND_DIGEST_MORE) */
 #define MSPACK_HIP_FEAT_SLOTS 16u       /* mspack_hip_set_slots / _slots / _slot_stats: context slots of the host-buffer entry points */
+#define MSPACK_HIP_FEAT_LZSS_RING 32u    /* MSPACK_HIP_UF_LZSS_RING / MSPACK_HIP_MASK_LZSS_RING */
 unsigned mspack_hip_features(void);
 
 /* ---- device-resident batch decode (the hot path proper) ---------------------------------------
@@ -240,6 +253,9 @@ unsigned mspack_hip_features(void);
  *                bit MSPACK_HIP_KIND_SHA1 (16) / MSPACK_HIP_KIND_SHA256 (17) set = heads of that algorithm (with their tails) may
  *                be present: only then is that algorithm's pass launched, one launch each, behind everything else on the stream
  *                like the MD5 pass; a mask of digest bits alone launches those passes only
+ *                MSPACK_HIP_MASK_LZSS_RING set = LZSS units may carry MSPACK_HIP_UF_LZSS_RING: only then is the kernel that takes
+ *                the flagged units launched, beside the one that takes the unflagged ones (with the LZSS bit, or a mask that names no
+ *                codec); without it a flagged unit is decoded by nobody and its result is not written
  * MSZIP units need 32768 bytes of slack after out_len in their output region.
  * Units with a frame / block table: the parse wavefronts store literals into the unit's output region (for MSZIP incl. its
  * slack) before the unit is known to decode; the first result.out_len bytes are the decoded data, the rest of the region

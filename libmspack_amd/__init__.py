@@ -29,6 +29,9 @@ FEAT_MD5 = 2
 MASK_MD5 = 1 << KIND_MD5     # decode_batch_device(kind_mask): launch the MD5 pass
 FEAT_SHA1, FEAT_SHA256 = 4, 8
 FEAT_SLOTS = 16              # set_slots / slots / slot_stats: context slots of the host-buffer entry points
+UF_LZSS_RING = 256           # KIND_LZSS: the window in LDS, nothing owned below out_off (include/mspack_hip.h)
+FEAT_LZSS_RING = 32
+MASK_LZSS_RING = 0x20000000  # decode_batch_device(kind_mask): launch the kernel of the units that carry UF_LZSS_RING
 MASK_SHA1, MASK_SHA256 = 1 << KIND_SHA1, 1 << KIND_SHA256     # ... the SHA-1 / the SHA-256 pass
 ERR_OK, ERR_ARGS, ERR_OPEN, ERR_READ, ERR_WRITE, ERR_SEEK, ERR_NOMEMORY, ERR_SIGNATURE, \
     ERR_DATAFORMAT, ERR_CHECKSUM, ERR_CRUNCH, ERR_DECRUNCH = range(12)
@@ -172,7 +175,7 @@ def make_units(kind, in_offs, in_lens, out_lens, window_bits=0, reset_frames=0, 
         u["flags"] |= UF_FRAME_TABLE
         u["in_chunk"] = np.asarray(frame_tabs, dtype=np.uint64) // 4
     rl = (u["ref_len"].astype(np.int64) + 15) & ~15
-    rl = np.where((u["kind"] == KIND_LZSS) | (u["kind"] == KIND_KWAJ_LZH), 4096, rl)   # window pre-fill room
+    rl = np.where(((u["kind"] == KIND_LZSS) & ((u["flags"] & UF_LZSS_RING) == 0)) | (u["kind"] == KIND_KWAJ_LZH), 4096, rl)   # window pre-fill room
     sizes = ((np.asarray(out_lens, dtype=np.int64) + out_slack + 15) & ~15) + rl
     offs = np.zeros(n, dtype=np.int64)
     if n:

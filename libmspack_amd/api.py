@@ -787,3 +787,128 @@ def szdd_kwaj_extract(kind, blob, L=None):
     finally:
         destroy(d)
         os.unlink(pin); os.unlink(pout)
+
+
+def _setup_sk(L=None):
+    """argument types of the SZDD / KWAJ extensions (mspack.h); L as in _setup"""
+    L = L or lib()
+    for T, name in ((MsszddDecompressor, "szdd"), (MskwajDecompressor, "kwaj")):
+        create, destroy = getattr(L, "mspack_create_%s_decompressor" % name), getattr(L, "mspack_destroy_%s_decompressor" % name)
+        create.restype = _P(T); create.argtypes = [C.c_void_p]; destroy.argtypes = [_P(T)]
+    L.mspack_szddd_prefetch.restype = C.c_int
+    L.mspack_szddd_prefetch.argtypes = [_P(MsszddDecompressor), _P(_P(MsszdddHeader)), C.c_int]
+    L.mspack_kwajd_prefetch.restype = C.c_int
+    L.mspack_kwajd_prefetch.argtypes = [_P(MskwajDecompressor), _P(_P(MskwajdHeader)), C.c_int]
+    for f in (L.mspack_szddd_batch_counts, L.mspack_kwajd_batch_counts):
+        f.restype = None
+        f.argtypes = [C.c_void_p, C.c_int]
+    L.mspack_szdd_kwaj_ring_units.restype = C.c_ulonglong
+    L.mspack_szdd_kwaj_ring_units.argtypes = [C.c_int]
+    return L
+
+
+def szdd_batch_counts(reset=False, L=None):
+    """mspack_szddd_batch_counts (mspack.h): (batches the SZDD driver issued, extract() calls answered from a prefetch batch, members
+    decoded again alone because they did not fit their room)"""
+    c = (C.c_ulonglong * 3)()
+    _setup_sk(L).mspack_szddd_batch_counts(c, int(reset))
+    return int(c[0]), int(c[1]), int(c[2])
+
+
+def kwaj_batch_counts(reset=False, L=None):
+    """mspack_kwajd_batch_counts (mspack.h): as szdd_batch_counts, of the KWAJ driver"""
+    c = (C.c_ulonglong * 3)()
+    _setup_sk(L).mspack_kwajd_batch_counts(c, int(reset))
+    return int(c[0]), int(c[1]), int(c[2])
+
+
+def lzss_ring_units(reset=False, L=None):
+    """mspack_szdd_kwaj_ring_units (mspack.h): LZSS members of the two drivers' prefetch batches that went out with UF_LZSS_RING"""
+    return int(_setup_sk(L).mspack_szdd_kwaj_ring_units(int(reset)))
+
+
+class _SkSet:
+    """Many SZDD (or KWAJ) images opened on ONE decompressor and one in-memory mspack_system:
+    with SzddSet([blob1, blob2, ...]) as s: s.prefetch(); s.extract(k)"""
+    KIND = 0
+
+    def __init__(self, blobs, L=None):
+        self.L = _setup_sk(L)
+        self.mem = MemSystem(self.L)
+        self.paths = []
+        for k, blob in enumerate(blobs):
+            self.mem.files[b"mem:in%d" % k] = bytes(blob)
+            self.paths.append(b"mem:in%d" % k)
+        create = self.L.mspack_create_szdd_decompressor if self.KIND == 0 else self.L.mspack_create_kwaj_decompressor
+        self.d = create(self.mem.ptr())
+        if not self.d:
+            raise RuntimeError("the decompressor could not be created")
+        m = self.d.contents
+        self.hdrs, self.open_errors = [], []
+        for p in self.paths:
+            h = m.open(self.d, p)
+            self.hdrs.append(h if h else None)
+            self.open_errors.append(0 if h else m.last_error(self.d))
+
+    @property
+    def messages(self):
+        return self.mem.messages
+
+    def last_error(self):
+        return self.d.contents.last_error(self.d)
+
+    def prefetch(self, indices=None):
+        """mspack_szddd_prefetch / mspack_kwajd_prefetch (mspack.h): the coded streams of these files (indices into the list given
+        to the constructor, None entries allowed; None = all that are open) in ONE batch -> MSPACK_ERR_*"""
+        if indices is None:
+            indices = [k for k, h in enumerate(self.hdrs) if h]
+        H = MsszdddHeader if self.KIND == 0 else MskwajdHeader
+        arr = (_P(H) * max(len(indices), 1))()
+        for j, k in enumerate(indices):
+            if k is not None and self.hdrs[k]:
+                arr[j] = self.hdrs[k]
+        fn = self.L.mspack_szddd_prefetch if self.KIND == 0 else self.L.mspack_kwajd_prefetch
+        return fn(self.d, arr, len(indices))
+
+    def extract(self, k):
+        """-> the dict of szdd_kwaj_extract for file k"""
+        h = self.hdrs[k]
+        if not h:
+            e = self.open_errors[k]
+            return dict(open_err=e, err=e, data=b"", comp_type=-1, length=-1, filename=b"")
+        hc = h.contents
+        info = dict(open_err=0, comp_type=hc.format if self.KIND == 0 else hc.comp_type, length=hc.length,
+                    filename=(hc.missing_char.rstrip(b"\0") if self.KIND == 0 else (hc.filename or b"")))
+        self.mem.outputs.clear()
+        info["err"] = self.d.contents.extract(self.d, h, b"mem:out")
+        info["data"] = bytes(self.mem.outputs.get(b"mem:out", b""))
+        return info
+
+    def close(self, k=None):
+        """close(k): file k alone; close(): every file that is still open, then the decompressor"""
+        if k is not None:
+            if self.d and self.hdrs[k]:
+                self.d.contents.close(self.d, self.hdrs[k])
+                self.hdrs[k] = None
+            return
+        if self.d:
+            for j, h in enumerate(self.hdrs):
+                if h:
+                    self.d.contents.close(self.d, h)
+                    self.hdrs[j] = None
+            (self.L.mspack_destroy_szdd_decompressor if self.KIND == 0 else self.L.mspack_destroy_kwaj_decompressor)(self.d)
+            self.d = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+class SzddSet(_SkSet):
+    KIND = 0
+
+
+class KwajSet(_SkSet):
+    KIND = 1

@@ -501,7 +501,21 @@ void mspack_decode_lzss(const mspack_hip_unit *units, const u32 *order, u32 n_un
   u32 ui;
   if (!pick_unit(units, order, n_units, MSPACK_HIP_KIND_LZSS, ui)) return;
   const mspack_hip_unit u = units[ui];
+  if (u.flags & MSPACK_HIP_UF_LZSS_RING) return;                         // (mspack_decode_lzss_ring's unit)
   lzss_decode_unit(u, in_arena, out_arena, &results[ui]);
+}
+// the same for the units that keep their window in LDS (MSPACK_HIP_UF_LZSS_RING, lzss_ring_kernel.hpp) -- launched beside
+// mspack_decode_lzss over the same list when the batch holds such a unit; each kernel leaves the other's units alone
+__global__ __launch_bounds__(64)
+void mspack_decode_lzss_ring(const mspack_hip_unit *units, const u32 *order, u32 n_units,
+                             const u8 *in_arena, u8 *out_arena, mspack_hip_result *results)
+{
+  __shared__ LzssRingShared sh;
+  u32 ui;
+  if (!pick_unit(units, order, n_units, MSPACK_HIP_KIND_LZSS, ui)) return;
+  const mspack_hip_unit u = units[ui];
+  if (!(u.flags & MSPACK_HIP_UF_LZSS_RING)) return;
+  lzss_ring_decode_unit(u, in_arena, out_arena, &results[ui], &sh);
 }
 
 __global__ __launch_bounds__(64)

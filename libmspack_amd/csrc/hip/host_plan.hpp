@@ -17,10 +17,13 @@ struct Chunk {
   size_t fm_lo, fm_n;
   size_t crc_off, crc_n; uint64_t crc_max;      // the chunk's units that carry MSPACK_HIP_UF_CRC32: slice of the order array, the longest
   bool has_ftab;                        // some LZX unit of the chunk carries a frame table
+  bool has_lzss_ring;                   // some LZSS unit of the chunk carries MSPACK_HIP_UF_LZSS_RING: its kernel is launched too
 };
 
 // bytes below out_off that belong to the unit, and the room it may write past out_len
+static inline bool unit_lzss_ring(const mspack_hip_unit &u) { return u.kind == MSPACK_HIP_KIND_LZSS && (u.flags & MSPACK_HIP_UF_LZSS_RING); }
 static inline uint64_t unit_below(const mspack_hip_unit &u) {
+  if (unit_lzss_ring(u)) return 0u;                    // (its window is in LDS)
   return (u.kind == MSPACK_HIP_KIND_LZSS || u.kind == MSPACK_HIP_KIND_KWAJ_LZH) ? 4096u
        : (u.kind == MSPACK_HIP_KIND_LZX_DELTA ? u.ref_len : 0u);
 }
@@ -260,7 +263,7 @@ static void plan_lists(BatchPlan &p)
   uint64_t ci_prev_hi = out_lo == ~0ull ? 0 : out_lo;
   for (Chunk &c : chunks) {
     c.in_lo = ~0ull; c.in_hi = 0; c.out_lo = ~0ull; c.out_hi = 0;
-    c.fm_lo = ~(size_t) 0; c.fm_n = 0; c.has_ftab = false;
+    c.fm_lo = ~(size_t) 0; c.fm_n = 0; c.has_ftab = false; c.has_lzss_ring = false;
     for (size_t i = c.a; i < c.b; i++) {
       const mspack_hip_unit &u = local[i];
       c.in_lo = std::min<uint64_t>(c.in_lo, u.in_off); c.in_hi = std::max<uint64_t>(c.in_hi, u.in_off + u.in_len);
@@ -271,6 +274,7 @@ static void plan_lists(BatchPlan &p)
         c.fm_n += unit_frames(u);
       }
       if (u.kind == MSPACK_HIP_KIND_XORSUM) continue;
+      if (unit_lzss_ring(u)) c.has_lzss_ring = true;
       c.out_lo = std::min<uint64_t>(c.out_lo, u.out_off - unit_below(u));
       c.out_hi = std::max<uint64_t>(c.out_hi, u.out_off + u.out_len + unit_above(u));
     }

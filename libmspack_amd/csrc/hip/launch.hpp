@@ -94,7 +94,7 @@ hipError_t hostcheck_launch_kind(unsigned kind, const mspack_hip_unit *d_units, 
 static hipError_t launch_kind(unsigned kind, const mspack_hip_unit *d_units, const uint32_t *d_order, size_t n,
                               const void *d_in, void *d_out, mspack_hip_result *d_results, void *d_fm, size_t n_frames_total,
                               size_t slot_lo, size_t n_slots, hipStream_t st, bool frame_tables = true, unsigned launch_ix = 0,
-                              size_t n_rec_slots = (size_t) -1, bool alone = true)
+                              size_t n_rec_slots = (size_t) -1, bool alone = true, bool lzss_ring = false)
 {
   if (n_rec_slots == (size_t) -1) n_rec_slots = n_frames_total;
   if (n == 0) return hipSuccess;
@@ -175,7 +175,10 @@ static hipError_t launch_kind(unsigned kind, const mspack_hip_unit *d_units, con
     LK(launch(mspack_decode_qtm, grid, block, st, d_units, d_order, (u32) n, in, out, d_results));
     LK(launch(mspack_decode_qtm_marks, grid, block, st, d_units, d_order, (u32) n, in, out, d_results)); break;
   case MSPACK_HIP_KIND_LZSS:
-    LK(launch(mspack_decode_lzss, grid, block, st, d_units, d_order, (u32) n, in, out, d_results)); break;
+    LK(launch(mspack_decode_lzss, grid, block, st, d_units, d_order, (u32) n, in, out, d_results));
+    // (units with MSPACK_HIP_UF_LZSS_RING: their own kernel, only when the caller says the list may hold one)
+    if (lzss_ring) LK(launch(mspack_decode_lzss_ring, grid, block, st, d_units, d_order, (u32) n, in, out, d_results));
+    break;
   case MSPACK_HIP_KIND_KWAJ_LZH:
     LK(launch(mspack_decode_kwaj_lzh, grid, block, st, d_units, d_order, (u32) n, in, out, d_results)); break;
   case MSPACK_HIP_KIND_XORSUM:
@@ -299,7 +302,7 @@ int mspack_hip_debug_frame_words(const void *d_frame_scratch, size_t n_frames_to
 }
 const char *mspack_hip_version(void) { return "mspack-hip 0.4 (gfx950; LZX/LZX-DELTA/Quantum/MSZIP batch decode)"; }
 const char *mspack_hip_last_error(void) { return g_err; }
-unsigned mspack_hip_features(void) { return MSPACK_HIP_FEAT_CRC32 | MSPACK_HIP_FEAT_MD5 | MSPACK_HIP_FEAT_SHA1 | MSPACK_HIP_FEAT_SHA256 | MSPACK_HIP_FEAT_SLOTS; }
+unsigned mspack_hip_features(void) { return MSPACK_HIP_FEAT_CRC32 | MSPACK_HIP_FEAT_MD5 | MSPACK_HIP_FEAT_SHA1 | MSPACK_HIP_FEAT_SHA256 | MSPACK_HIP_FEAT_SLOTS | MSPACK_HIP_FEAT_LZSS_RING; }
 
 int mspack_hip_device_count(void) {
   int n = 0;
@@ -326,7 +329,8 @@ int mspack_hip_decode_batch_device(const mspack_hip_unit *d_units, const uint32_
   for (unsigned k = 1; k <= MSPACK_HIP_KIND_XORSUM; k++)
     if (kind_mask & (1u << k))
       CK(launch_kind(k, d_units, d_order, n_units, d_in, d_out, d_results, d_frame_scratch, n_frames_total, 0, n_frames_total,
-                     (hipStream_t) stream, (kind_mask & MSPACK_HIP_MASK_FRAME_TABLES) != 0u));
+                     (hipStream_t) stream, (kind_mask & MSPACK_HIP_MASK_FRAME_TABLES) != 0u, 0, (size_t) -1, true,
+                     (kind_mask & MSPACK_HIP_MASK_LZSS_RING) != 0u));
   // (the flags are on the device too: the digest pass is launched only when the caller says some unit may carry MSPACK_HIP_UF_CRC32)
   if (kind_mask & MSPACK_HIP_MASK_CRC32)
     CK(launch_crc32(d_units, d_order, n_units, std::min<uint64_t>(out_bytes, 0xFFFFFFFFu), d_out, d_results, (hipStream_t) stream));
