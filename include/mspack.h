@@ -490,6 +490,43 @@ struct msoab_decompressor {
 extern struct msoab_decompressor *mspack_create_oab_decompressor(struct mspack_system *sys);
 extern void mspack_destroy_oab_decompressor(struct msoab_decompressor *self);
 
+/* extension of this library (plain functions: the decompressor struct keeps the reference's layout).
+ *
+ * Decompress MANY address-book files in as few GPU batches as their order allows.  Each job, called alone through decompress() /
+ * decompress_incremental() and in the same order, would return some value, write some bytes to its output file and say some lines
+ * through sys->message: after the call jobs[k].error holds that value, the output file holds exactly those bytes (a failing job's
+ * partial output included) and the lines are the same lines.
+ *
+ * Without it every file is a batch of its own -- planning, copies, launches and the drain for a block or two of LZX DELTA; one address
+ * list is a data file plus dozens of per-language templates, a catch-up is a chain of daily patches, a mirror serves many lists.
+ *   jobs[k]   input, output; base == NULL: a full file (decompress), else decompress_incremental's base.
+ *   steps     Each job is GATHERED (input and base opened, headers checked, the blocks' bytes and their reference slices read, both
+ *             closed again); the blocks of all gathered jobs are DECODED in one batch; the jobs are REPLAYED in order (output opened,
+ *             blocks written, CRCs compared, output closed).  No more than three files are open at any time, whatever n is.  A job
+ *             whose input, header or base fails at gather contributes nothing to the batch and its output is not created, as ever.
+ *   a batch ends, and is decoded and replayed before the next job is gathered,
+ *     order   when that job's `input` or `base` is the `output` of a job in the batch: base + patch1 -> v2, v2 + patch2 -> v3 in one
+ *             call behaves as the calls in order do.  Only IDENTICAL strings (strcmp) are recognised: two spellings of one file are
+ *             not, and such jobs belong into separate calls.  (A job whose `output` is its own `input` or `base` runs alone.)
+ *     budget  when that job would take the batch's input plus output arena past mspack_hip_cache_mb() MiB: it starts the next batch.
+ *             A job that passes the budget alone runs alone, as ever.
+ *   failure   When mspack_hip_decode_batch() fails for a batch of several jobs, each of them is decoded again in a batch of its own:
+ *             only a job whose OWN batch fails says "GPU batch decode failed: ..." and answers MSPACK_ERR_DECRUNCH.
+ *   returns   MSPACK_ERR_ARGS for self == NULL, n < 0, jobs == NULL with n > 0, or a job without input or output (no job is started
+ *             then); MSPACK_ERR_NOMEMORY when the call's own tables cannot be allocated; else MSPACK_ERR_OK, whatever the jobs'
+ *             own answers are.  n == 0 issues nothing.  MSOABD_PARAM_DECOMPBUF applies to every job.  Synchronous. */
+struct msoabd_job {
+  const char *input;    /* the .LZX file                                            */
+  const char *base;     /* NULL: a full file (decompress); else decompress_incremental's base */
+  const char *output;
+  int error;            /* out: what decompress() / decompress_incremental() returns for this job alone */
+};
+extern int mspack_oabd_decompress_many(struct msoab_decompressor *self, struct msoabd_job *jobs, int n);
+/* diagnostics: counts[0] the batch calls the OAB driver has issued in this process (a lone decompress() with a compressed block is
+ * one), counts[1] the jobs whose blocks went out in a batch built by mspack_oabd_decompress_many, counts[2] the jobs decoded again
+ * alone because their shared batch failed; counts may be NULL; reset != 0 clears them after reading */
+extern void mspack_oabd_batch_counts(unsigned long long counts[3], int reset);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,6 +8,7 @@ mspack_create_*_decompressor(sys) (MemSystem below: the same semantics as the me
 were recorded with, oracle/ref_harness.c: reads are clipped at the end, a seek beyond the end fails)."""
 import ctypes as C
 import os
+import shutil
 import tempfile
 
 from . import lib
@@ -722,6 +723,77 @@ def oab_decompress(blob, base=None, decompbuf=0, L=None):
         L.mspack_destroy_oab_decompressor(d)
         for t in tmps:
             os.unlink(t)
+
+
+class MsoabdJob(C.Structure):
+    _fields_ = [("input", C.c_char_p), ("base", C.c_char_p), ("output", C.c_char_p), ("error", C.c_int)]
+
+
+def _setup_oab(L=None):
+    """argument types of the OAB driver and its extensions (mspack.h); L as in _setup"""
+    L = L or lib()
+    L.mspack_create_oab_decompressor.restype = _P(MsoabDecompressor)
+    L.mspack_create_oab_decompressor.argtypes = [C.c_void_p]
+    L.mspack_destroy_oab_decompressor.argtypes = [_P(MsoabDecompressor)]
+    L.mspack_oabd_decompress_many.restype = C.c_int
+    L.mspack_oabd_decompress_many.argtypes = [_P(MsoabDecompressor), _P(MsoabdJob), C.c_int]
+    L.mspack_oabd_batch_counts.restype = None
+    L.mspack_oabd_batch_counts.argtypes = [C.c_void_p, C.c_int]
+    return L
+
+
+def oab_batch_counts(reset=False, L=None):
+    """mspack_oabd_batch_counts (mspack.h): (batch calls the OAB driver has issued in this process, jobs that went out in a batch of
+    mspack_oabd_decompress_many, jobs decoded again alone because their shared batch failed)"""
+    c = (C.c_ulonglong * 3)()
+    _setup_oab(L).mspack_oabd_batch_counts(c, int(reset))
+    return int(c[0]), int(c[1]), int(c[2])
+
+
+def oab_decompress_paths(jobs, decompbuf=0, L=None, sys=None):
+    """mspack_oabd_decompress_many over files that exist: jobs = [(input, base or None, output)] (bytes names; a None input or output
+    goes through as NULL) -> (the call's return value, [jobs[k].error]).  sys: a MemSystem, else the library's stdio system"""
+    L = _setup_oab(L)
+    d = L.mspack_create_oab_decompressor(sys.ptr() if sys is not None else None)
+    try:
+        if decompbuf:
+            d.contents.set_param(d, 0, decompbuf)
+        arr = (MsoabdJob * max(len(jobs), 1))()
+        for k, (pin, pbase, pout) in enumerate(jobs):
+            arr[k].input, arr[k].base, arr[k].output, arr[k].error = pin, pbase, pout, -1
+        rc = L.mspack_oabd_decompress_many(d, arr, len(jobs))
+        return rc, [int(arr[k].error) for k in range(len(jobs))]
+    finally:
+        L.mspack_destroy_oab_decompressor(d)
+
+
+def oab_decompress_many(items, decompbuf=0, L=None):
+    """mspack_oabd_decompress_many over temporary files: items = [(blob, base or None)] -> [(err, output bytes)], one call for all of
+    them.  L: as in _setup (the CPU stand-in build of the host logic: tests)"""
+    tmpdir = tempfile.mkdtemp(prefix="oab_many_")
+
+    def tmp(name, data):
+        path = os.path.join(tmpdir, name)
+        with open(path, "wb") as fh:
+            fh.write(bytes(data))
+        return os.fsencode(path)
+    try:
+        jobs = [(tmp("%d.oab" % k, blob), None if base is None else tmp("%d.base" % k, base),
+                 os.fsencode(os.path.join(tmpdir, "%d.out" % k))) for k, (blob, base) in enumerate(items)]
+        rc, errs = oab_decompress_paths(jobs, decompbuf, L)
+        if rc:
+            raise RuntimeError("mspack_oabd_decompress_many: error %d" % rc)
+        out = []
+        for (_i, _b, pout), err in zip(jobs, errs):
+            # (a job that fails before its output is opened creates none: the lone call's temporary file is then as empty)
+            data = b""
+            if os.path.exists(pout):
+                with open(pout, "rb") as fh:
+                    data = fh.read()
+            out.append((err, data))
+        return out
+    finally:
+        shutil.rmtree(tmpdir, ignore_errors=True)
 
 
 class MsszdddHeader(C.Structure):
