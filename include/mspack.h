@@ -172,6 +172,8 @@ struct mscabd_file {
                                             (MSPACK_DIGEST_MD5) of MSCABD_PARAM_HIP_DIGESTS: either one reads and writes it */
 #define MSCABD_PARAM_HIP_DIGESTS  (103)  /* a mask of MSPACK_DIGEST_*: the algorithms the batches carry digest units for, per file, for
                                             mspack_cabd_digest() (0 to 7, default 0; other values: MSPACK_ERR_ARGS) */
+#define MSCABD_PARAM_HIP_CRC32    (105)  /* 1: batches carry one CRC-32 unit per file, for mspack_cabd_crc32() (0 or 1, default 0; other
+                                            values: MSPACK_ERR_ARGS).  104 is not a parameter */
 /* digest algorithms (mspack_cabd_digest, MSCABD_PARAM_HIP_DIGESTS) */
 #define MSPACK_DIGEST_MD5     (1)        /* RFC 1321, 16 bytes */
 #define MSPACK_DIGEST_SHA1    (2)        /* FIPS 180-4, 20 bytes */
@@ -252,6 +254,22 @@ extern void mspack_cabd_md5_counts(unsigned long long counts[2], int reset);
 extern int mspack_cabd_digest(struct mscab_decompressor *self, struct mscabd_file *file, int alg, unsigned char *digest, size_t digest_cap);
 /* mspack_cabd_md5_counts() per algorithm (an unknown alg: zeros) */
 extern void mspack_cabd_digest_counts(int alg, unsigned long long counts[2], int reset);
+/* The CRC-32 of a file in zlib's convention (zlib.crc32(bytes): polynomial 0xEDB88320 reflected, started at 0xFFFFFFFF, inverted at the
+ * end; 0 for no bytes) -- the per-file checksum ZIP, gzip, 7z and PNG store, what a caller who repacks or indexes a cabinet's members
+ * needs.  The contract of mspack_cabd_digest(), word for word: the return code is the one extract(file, ...) would give now, the call
+ * COUNTS as that extract() (the sticky state, what Quantum held back, the decoder's lifetime, the lines said through sys->message), no
+ * output file is opened and sys->write is never called; *crc is the checksum of exactly the bytes extract() would have written when
+ * the call succeeds and 0 otherwise; a NULL argument is MSPACK_ERR_ARGS.  CRC-32 is not a fourth MSPACK_DIGEST_* value.
+ * With MSCABD_PARAM_HIP_CRC32 set to 1 (before the batch is built, as for MSCABD_PARAM_HIP_MD5) and a batch provider that reports
+ * MSPACK_HIP_FEAT_CRC32_RANGES, the batch carries one MSPACK_HIP_KIND_CRC32 unit per file that lies inside its folder -- at ANY
+ * length: there is no "too long for one lane" rule, the device spreads a range over the chip (mspack_hip.h) -- and the checksums are
+ * kept with the folders beside the digests.  Everything else is computed on the host by a plain-C CRC-32 with the same answers: the
+ * param off, stored folders (as they stream), failing or partial calls, what Quantum held back, a provider without the feature bit.
+ * As with the other digest units, a batch that carries CRC-32 units does not run as a job. */
+extern int mspack_cabd_crc32(struct mscab_decompressor *self, struct mscabd_file *file, unsigned int *crc);
+/* diagnostics: successful mspack_cabd_crc32() calls of this process answered from the device (counts[0]) / computed on the host
+ * (counts[1]); counts may be NULL; reset != 0 clears them after reading */
+extern void mspack_cabd_crc32_counts(unsigned long long counts[2], int reset);
 /* the value set_param() last stored for a parameter (the defaults before that); MSCABD_PARAM_HIP_MD5 answers bit 1 of
  * MSCABD_PARAM_HIP_DIGESTS.  MSPACK_ERR_ARGS for an unknown parameter or a NULL argument. */
 extern int mspack_cabd_get_param(struct mscab_decompressor *self, int param, int *value);
@@ -324,6 +342,8 @@ struct mschm_decompressor {
 /* extensions of this library (plain functions: the reference's mschm_decompressor has no set_param and keeps its layout) */
 #define MSCHMD_PARAM_HIP_DIGESTS (103)   /* a mask of MSPACK_DIGEST_*: the algorithms a chunk's batch carries digest units for, per file,
                                             for mspack_chmd_digest() (0 to 7, default 0; other values: MSPACK_ERR_ARGS) */
+#define MSCHMD_PARAM_HIP_CRC32   (105)   /* 1: a chunk's batch carries one CRC-32 unit per file, for mspack_chmd_crc32() (0 or 1, default 0;
+                                            other values: MSPACK_ERR_ARGS).  104 is not a parameter */
 /* MSPACK_ERR_ARGS for an unknown parameter or a NULL argument; get_param answers what set_param last stored (the default before that) */
 extern int mspack_chmd_set_param(struct mschm_decompressor *self, int param, int value);
 extern int mspack_chmd_get_param(struct mschm_decompressor *self, int param, int *value);
@@ -353,6 +373,16 @@ extern int mspack_chmd_digest(struct mschm_decompressor *self, struct mschmd_fil
  * on the device (counts[0]) and how many were hashed on the host (counts[1]); counts may be NULL; reset != 0 clears them after
  * reading; an unknown alg: zeros */
 extern void mspack_chmd_digest_counts(int alg, unsigned long long counts[2], int reset);
+/* The CRC-32 of a file in zlib's convention: mspack_cabd_crc32() for CHM files, under the contract of mspack_chmd_digest() word for
+ * word (return code, what the call counts as, no output file, no sys->write); *crc is zlib.crc32 of exactly the bytes extract() would
+ * have written when the call succeeds and 0 otherwise; a NULL argument is MSPACK_ERR_ARGS.
+ * With MSCHMD_PARAM_HIP_CRC32 set to 1 when a chunk is decoded (or gathered by mspack_chmd_prefetch()) and a provider that reports
+ * MSPACK_HIP_FEAT_CRC32_RANGES, the chunk's batch carries one MSPACK_HIP_KIND_CRC32 unit for every file that lies wholly inside the
+ * chunk, whatever its length; the checksums are kept with the chunk in the table of its digests.  Computed on the host, with the
+ * same answers: the param off, a provider without the feature bit, failing or partial calls, damaged (serially decoded) files,
+ * shifted E8 origins, files across a chunk boundary.  A batch that carries CRC-32 units does not run as a job. */
+extern int mspack_chmd_crc32(struct mschm_decompressor *self, struct mschmd_file *file, unsigned int *crc);
+extern void mspack_chmd_crc32_counts(unsigned long long counts[2], int reset);
 
 /* Gather the not-yet-decoded reset intervals of the given CHMs into ONE GPU batch, so that the extract() / mspack_chmd_digest()
  * calls that follow are slices of it.  Advice: what every later extract(), fast_find() + extract() and mspack_chmd_digest() returns,

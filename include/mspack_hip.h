@@ -84,6 +84,26 @@ extern "C" {
                                        entry answers MSPACK_ERR_ARGS in that unit's result and reads nothing.  A head whose range
                                        leaves out_bytes answers MSPACK_ERR_ARGS as an MD5 unit does (its tail's result is then all 0) */
 
+/* Kind 19 is not defined. */
+#define MSPACK_HIP_KIND_CRC32   20   /* a digest unit with every convention of MSPACK_HIP_KIND_MD5 (the range [out_off, out_off + out_len) of the OUTPUT
+                                       arena as it lies there behind all decoding -- E8 and resume passes included, failing units too --,
+                                       in_len 0, MSPACK_HIP_UF_CRC32 rejected and every other flag ignored, out_len 0 to 2^32-1, ranges
+                                       that may overlap each other and other digest units' ranges, the arena only read, which bytes "lie
+                                       there" per entry point as documented for MD5): the CRC-32 of the range AT ANY LENGTH -- CRC is
+                                       linear, so a range is spread over lanes and waves in 64 KiB segments, and the segments of all
+                                       ranges of a batch are one pool of work: one 2 GiB range beside 100 000 short ones fills the chip.
+                                       Result: err 0, flags 0, and the checksum in result.out_len; in_used, good_len and in_next are 0.
+                                       A range that leaves out_bytes answers MSPACK_ERR_ARGS with the other words 0 and nothing is read;
+                                       the host entry points refuse such a batch before anything touches the device
+                                       (mspack_hip_last_error() names the unit).
+                                       TWO CONVENTIONS, side by side:
+                                         MSPACK_HIP_KIND_CRC32 (this unit)    zlib's: polynomial 0xEDB88320 reflected, register started at
+                                                                              0xFFFFFFFF, INVERTED at the end -- zlib.crc32(bytes), the
+                                                                              number ZIP, gzip, 7z and PNG store; 0 for an empty range
+                                         MSPACK_HIP_UF_CRC32 (a unit's flag)  the OAB block check: the same register NOT inverted at the
+                                                                              end -- zlib.crc32(bytes) ^ 0xFFFFFFFF; 0xFFFFFFFF for no bytes
+                                       Ask mspack_hip_features() & MSPACK_HIP_FEAT_CRC32_RANGES first                          */
+
 #define MSPACK_HIP_MASK_FRAME_TABLES 0x80000000u   /* mspack_hip_decode_batch_device(kind_mask): see there */
 #define MSPACK_HIP_MASK_CRC32        0x40000000u   /* mspack_hip_decode_batch_device(kind_mask): units may carry MSPACK_HIP_UF_CRC32 */
 #define MSPACK_HIP_MASK_LZSS_RING    0x20000000u   /* mspack_hip_decode_batch_device(kind_mask): LZSS units may carry MSPACK_HIP_UF_LZSS_RING */
@@ -222,6 +242,7 @@ const char *mspack_hip_last_error(void);
 #define MSPACK_HIP_FEAT_SHA256 8u       /* MSPACK_HIP_KIND_SHA256 (and MSPACK_HIP_KIND_DIGEST_MORE) */
 #define MSPACK_HIP_FEAT_SLOTS 16u       /* mspack_hip_set_slots / _slots / _slot_stats: context slots of the host-buffer entry points */
 #define MSPACK_HIP_FEAT_LZSS_RING 32u    /* MSPACK_HIP_UF_LZSS_RING / MSPACK_HIP_MASK_LZSS_RING */
+#define MSPACK_HIP_FEAT_CRC32_RANGES 64u /* MSPACK_HIP_KIND_CRC32 */
 unsigned mspack_hip_features(void);
 
 /* ---- device-resident batch decode (the hot path proper) ---------------------------------------
@@ -253,6 +274,12 @@ unsigned mspack_hip_features(void);
  *                bit MSPACK_HIP_KIND_SHA1 (16) / MSPACK_HIP_KIND_SHA256 (17) set = heads of that algorithm (with their tails) may
  *                be present: only then is that algorithm's pass launched, one launch each, behind everything else on the stream
  *                like the MD5 pass; a mask of digest bits alone launches those passes only
+ *                bit MSPACK_HIP_KIND_CRC32 (20) set = CRC-32 range units may be present: only then is their pass launched (four launches:
+ *                results, a one-wave scan of the ranges' segment counts, the segments, tidying up), behind everything else on the
+ *                stream like the MD5 pass.  While it runs it keeps its bookkeeping in the range units' own in_used, good_len and
+ *                in_next; they are 0 when it ends.  Precondition: d_order names no range unit twice (with a unit listed twice
+ *                two places of the list would share one unit's words: the checksums would be wrong, without notice; reads stay
+ *                inside the checked ranges)
  *                MSPACK_HIP_MASK_LZSS_RING set = LZSS units may carry MSPACK_HIP_UF_LZSS_RING: only then is the kernel that takes
  *                the flagged units launched, beside the one that takes the unflagged ones (with the LZSS bit, or a mask that names no
  *                codec); without it a flagged unit is decoded by nobody and its result is not written
@@ -282,7 +309,7 @@ size_t mspack_hip_frame_scratch_bytes(size_t n_frames_total);
  * DMA that need not wait for the other streams; a buffer that cannot be registered is copied the ordinary way (MSPACK_HIP_PIN_OUT=0: always).
  * `units[i].frame_base` is filled in by the call.  Synchronous.  Bytes of the output arena
  * BETWEEN units that lie inside a copied span (alignment padding, the MSZIP slack) are unspecified afterwards.
- * Digest units (MSPACK_HIP_KIND_MD5, _SHA1, _SHA256 and their _DIGEST_MORE tails) are kept out of the chunk cutting; their passes
+ * Digest units (MSPACK_HIP_KIND_MD5, _SHA1, _SHA256 and their _DIGEST_MORE tails, MSPACK_HIP_KIND_CRC32) are kept out of the chunk cutting; their passes
  * (one per algorithm) run once per device, behind the last chunk's
  * launches and before the results go back -- over the device's copy of the output arena, which holds what this call's decoding
  * units stored (bytes of a range that no unit of the call wrote are unspecified).  mspack_hip_job_wait_unit() on a digest unit

@@ -33,6 +33,9 @@ UF_LZSS_RING = 256           # KIND_LZSS: the window in LDS, nothing owned below
 FEAT_LZSS_RING = 32
 MASK_LZSS_RING = 0x20000000  # decode_batch_device(kind_mask): launch the kernel of the units that carry UF_LZSS_RING
 MASK_SHA1, MASK_SHA256 = 1 << KIND_SHA1, 1 << KIND_SHA256     # ... the SHA-1 / the SHA-256 pass
+KIND_CRC32R = 20             # a digest unit: zlib.crc32 of out[out_off : out_off + out_len], at any length -> result.out_len
+FEAT_CRC32_RANGES = 64
+MASK_CRC32R = 1 << KIND_CRC32R   # decode_batch_device(kind_mask): launch the CRC-32 range pass
 ERR_OK, ERR_ARGS, ERR_OPEN, ERR_READ, ERR_WRITE, ERR_SEEK, ERR_NOMEMORY, ERR_SIGNATURE, \
     ERR_DATAFORMAT, ERR_CHECKSUM, ERR_CRUNCH, ERR_DECRUNCH = range(12)
 
@@ -233,6 +236,22 @@ def md5_units(ranges):
     u["out_off"] = [int(r[0]) for r in ranges]
     u["out_len"] = [int(r[1]) for r in ranges]
     return u
+
+
+def crc32r_units(ranges):
+    """digest units (KIND_CRC32R) for (out_off, out_len) ranges of the output arena"""
+    u = md5_units(ranges)
+    u["kind"] = KIND_CRC32R
+    return u
+
+
+def decode_batch_crc32r(units, in_arena, out_bytes, ranges, n_devices=1, refs=None):
+    """decode_batch with one KIND_CRC32R unit per (out_off, out_len) range appended to the batch
+    -> (out, the decoding units' results, the range units' results: the checksums are their out_len)"""
+    n = len(units)
+    both = np.concatenate([np.ascontiguousarray(units, dtype=UNIT_DTYPE), crc32r_units(ranges)])
+    out, res = decode_batch(both, in_arena, out_bytes, n_devices=n_devices, refs=refs)
+    return out, res[:n], res[n:]
 
 
 def result_digests(res):

@@ -106,6 +106,7 @@ MschmDecompressor._fields_ = [
 MSCABD_PARAM_SEARCHBUF, MSCABD_PARAM_FIXMSZIP, MSCABD_PARAM_DECOMPBUF, MSCABD_PARAM_SALVAGE = 0, 1, 2, 3
 MSCABD_PARAM_HIP_DEVICES, MSCABD_PARAM_HIP_CACHE_MB, MSCABD_PARAM_HIP_MD5, MSCABD_PARAM_HIP_DIGESTS = 100, 101, 102, 103
 MSCHMD_PARAM_HIP_DIGESTS = 103
+MSCABD_PARAM_HIP_CRC32, MSCHMD_PARAM_HIP_CRC32 = 105, 105     # 1: the batches carry one CRC-32 range unit per file (104 is no param)
 MSPACK_DIGEST_MD5, MSPACK_DIGEST_SHA1, MSPACK_DIGEST_SHA256 = 1, 2, 4
 DIGEST_BYTES = {MSPACK_DIGEST_MD5: 16, MSPACK_DIGEST_SHA1: 20, MSPACK_DIGEST_SHA256: 32}
 MSPACK_ERR_OK, MSPACK_ERR_ARGS = 0, 1
@@ -132,6 +133,13 @@ def _setup(L=None):
     L.mspack_cabd_digest.argtypes = [_P(MscabDecompressor), _P(MscabdFile), C.c_int, C.c_void_p, C.c_size_t]
     L.mspack_cabd_digest_counts.restype = None
     L.mspack_cabd_digest_counts.argtypes = [C.c_int, C.c_void_p, C.c_int]
+    L.mspack_cabd_crc32.restype = C.c_int
+    L.mspack_cabd_crc32.argtypes = [_P(MscabDecompressor), _P(MscabdFile), _P(C.c_uint)]
+    L.mspack_chmd_crc32.restype = C.c_int
+    L.mspack_chmd_crc32.argtypes = [_P(MschmDecompressor), _P(MschmdFile), _P(C.c_uint)]
+    for fn in (L.mspack_cabd_crc32_counts, L.mspack_chmd_crc32_counts):
+        fn.restype = None
+        fn.argtypes = [C.c_void_p, C.c_int]
     L.mspack_cabd_get_param.restype = C.c_int
     L.mspack_cabd_get_param.argtypes = [_P(MscabDecompressor), C.c_int, _P(C.c_int)]
     L.mspack_chmd_digest.restype = C.c_int
@@ -170,6 +178,31 @@ def chmd_digest_counts(alg, reset=False, L=None):
     c = (C.c_ulonglong * 2)()
     _setup(L).mspack_chmd_digest_counts(int(alg), c, int(reset))
     return int(c[0]), int(c[1])
+
+
+def cabd_crc32_counts(reset=False, L=None):
+    """mspack_cabd_crc32_counts (mspack.h): successful Cab.crc32() calls answered (from the device, by the host's CRC-32)"""
+    c = (C.c_ulonglong * 2)()
+    _setup(L).mspack_cabd_crc32_counts(c, int(reset))
+    return int(c[0]), int(c[1])
+
+
+def chmd_crc32_counts(reset=False, L=None):
+    """mspack_chmd_crc32_counts (mspack.h): successful Chm.crc32() calls answered (from the device, by the host's CRC-32)"""
+    c = (C.c_ulonglong * 2)()
+    _setup(L).mspack_chmd_crc32_counts(c, int(reset))
+    return int(c[0]), int(c[1])
+
+
+def crc32_counts(reset=False, L=None):
+    """both drivers' crc32 counts -> {"cab": (device, host), "chm": (device, host)}"""
+    return {"cab": cabd_crc32_counts(reset, L), "chm": chmd_crc32_counts(reset, L)}
+
+
+def _crc32(fn, d, fptr):
+    v = C.c_uint(0xDEADBEEF)
+    err = fn(d, fptr, C.byref(v))
+    return err, int(v.value)
 
 
 def chmd_batch_counts(reset=False, L=None):
@@ -344,6 +377,11 @@ class Cab:
         """mspack_cabd_get_param (mspack.h) -> (err, value)"""
         return _get_param(self.L, self.d, param)
 
+    def crc32(self, i):
+        """mspack_cabd_crc32 (mspack.h): extract(i) with the writes replaced by zlib's CRC-32 -> (err, value; 0 unless err == 0).
+        set_param(MSCABD_PARAM_HIP_CRC32, 1) before the first call lets the batch take the checksums on the device, at any length"""
+        return _crc32(self.L.mspack_cabd_crc32, self.d, self._files[i])
+
     def digest(self, i, alg, cap=None):
         """mspack_cabd_digest (mspack.h): extract(i) with the writes replaced by a hash of algorithm alg (MSPACK_DIGEST_*) -> (err, the
         16 / 20 / 32 digest bytes; zeros unless err == 0).  set_param(MSCABD_PARAM_HIP_DIGESTS, mask) before the first call lets the
@@ -444,6 +482,10 @@ class CabSet:
     def digest(self, fptr, alg, cap=None):
         """mspack_cabd_digest (mspack.h) of a file of file_ptrs() -> (err, the digest bytes)"""
         return _digest(self.L, self.d, fptr, alg, cap)
+
+    def crc32(self, fptr):
+        """mspack_cabd_crc32 (mspack.h) of a file of file_ptrs() -> (err, value)"""
+        return _crc32(self.L.mspack_cabd_crc32, self.d, fptr)
 
     def extract(self, fptr):
         if self.mem:
@@ -576,6 +618,11 @@ class Chm:
         chunks' batches take the digests on the device.  cap: the digest_cap handed over instead of the algorithm's length"""
         return _digest(self.L, self.d, self._files[i], alg, cap, fn=self.L.mspack_chmd_digest)
 
+    def crc32(self, i):
+        """mspack_chmd_crc32 (mspack.h): extract(i) with the writes replaced by zlib's CRC-32 -> (err, value; 0 unless err == 0).
+        set_param(MSCHMD_PARAM_HIP_CRC32, 1) before the first call lets the chunks' batches take the checksums on the device"""
+        return _crc32(self.L.mspack_chmd_crc32, self.d, self._files[i])
+
     def find(self, name):
         f = MschmdFile()
         err = self.d.contents.fast_find(self.d, self.chm, name, C.byref(f), C.sizeof(MschmdFile))
@@ -661,6 +708,10 @@ class ChmSet:
     def digest(self, k, i, alg, cap=None):
         """mspack_chmd_digest (mspack.h) of file i of CHM k -> (err, the digest bytes)"""
         return _digest(self.L, self.d, self._files[k][i], alg, cap, fn=self.L.mspack_chmd_digest)
+
+    def crc32(self, k, i):
+        """mspack_chmd_crc32 (mspack.h) of file i of CHM k -> (err, value)"""
+        return _crc32(self.L.mspack_chmd_crc32, self.d, self._files[k][i])
 
     def close(self, k=None):
         """close(k): CHM k alone; close(): every CHM that is still open, then the decompressor"""

@@ -628,3 +628,29 @@ void mspack_sha256(const mspack_hip_unit *units, const u32 *order, u32 n_list, u
 {
   sha_entry<MSPACK_HIP_KIND_SHA256>(units, order, n_list, n_table, out_arena, out_bytes, results);
 }
+
+// MSPACK_HIP_KIND_CRC32 (crc32_range_kernel.hpp): the CRC-32 of byte ranges of any length, launched behind everything that stores into
+// the output arena -- stream order is the only ordering, between these four launches too.  order[0 .. n) names the list's units (NULL:
+// the whole table); units of other kinds own nothing here.  init and finish: one position per lane; scan: one wave; the pass: a
+// bounded grid of waves that take chunks of segment tickets until the counter is past the end
+__global__ __launch_bounds__(64)
+void mspack_crc32r_init(const mspack_hip_unit *units, const u32 *order, u32 n, u64 out_bytes, mspack_hip_result *results)
+{
+  crc32r_init_lane(units, order, n, out_bytes, results);
+}
+__global__ __launch_bounds__(64)
+void mspack_crc32r_scan(const mspack_hip_unit *units, const u32 *order, u32 n, const u8 *out_arena, u64 out_bytes, mspack_hip_result *results)
+{
+  crc32r_scan_wave(units, order, n, out_arena, out_bytes, results);
+}
+__global__ __launch_bounds__(64)
+void mspack_crc32r_pass(const mspack_hip_unit *units, const u32 *order, u32 n, const u8 *out_arena, u64 out_bytes, mspack_hip_result *results)
+{
+  __shared__ CrcShared sh;
+  crc32r_pass_wave(units, order, n, out_arena, out_bytes, results, &sh);
+}
+__global__ __launch_bounds__(64)
+void mspack_crc32r_finish(const mspack_hip_unit *units, const u32 *order, u32 n, u64 out_bytes, mspack_hip_result *results)
+{
+  crc32r_finish_lane(units, order, n, out_bytes, results);
+}

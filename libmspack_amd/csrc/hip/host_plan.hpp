@@ -52,9 +52,9 @@ static inline bool unit_side_table(const mspack_hip_unit &u, uint64_t &lo, uint6
   }
   return false;
 }
-// digest units: the heads (MD5; SHA-1 and SHA-256, whose results go on in the next unit's) and the tails of the wide ones
+// digest units: the heads (MD5 and CRC-32 ranges; SHA-1 and SHA-256, whose results go on in the next unit's) and the tails of the wide ones
 static inline bool unit_is_wide_head(const mspack_hip_unit &u) { return u.kind == MSPACK_HIP_KIND_SHA1 || u.kind == MSPACK_HIP_KIND_SHA256; }
-static inline bool unit_is_digest_head(const mspack_hip_unit &u) { return u.kind == MSPACK_HIP_KIND_MD5 || unit_is_wide_head(u); }
+static inline bool unit_is_digest_head(const mspack_hip_unit &u) { return u.kind == MSPACK_HIP_KIND_MD5 || u.kind == MSPACK_HIP_KIND_CRC32 || unit_is_wide_head(u); }
 static inline bool unit_is_digest(const mspack_hip_unit &u) { return unit_is_digest_head(u) || u.kind == MSPACK_HIP_KIND_DIGEST_MORE; }
 static inline size_t unit_frames(const mspack_hip_unit &u) {
   if (u.kind == MSPACK_HIP_KIND_LZX || u.kind == MSPACK_HIP_KIND_LZX_DELTA) return (size_t) u.out_len / 32768u + 1u;
@@ -73,7 +73,8 @@ struct PlanKnobs {
 // stand BEHIND the chunks in local[] -- indices [n - n_dig, n), in the caller's order, so a head keeps its tail at i + 1; no chunk
 // holds them, no per-kind list, no weight in the cutting -- and order holds three consecutive lists of HEADS, one per algorithm
 // (MD5 at md5_off, SHA-1 at sha1_off, SHA-256 at sha256_off), each longest range first (one lane each: lanes of similar length next
-// to each other) for that algorithm's one pass behind the last chunk
+// to each other) for that algorithm's one pass behind the last chunk; behind them the list of the CRC-32 range units (crc32r_off), in
+// the caller's order: their pass takes segments, not units, so the order carries no weight
 struct BatchPlan {
   std::vector<uint32_t> idx;
   std::vector<mspack_hip_unit> local;
@@ -83,6 +84,7 @@ struct BatchPlan {
   size_t n_frames, n_rec_slots, n_crc;              // n_crc: units that want a digest (MSPACK_HIP_UF_CRC32)
   size_t n_md5 = 0, md5_off = 0;                    // the MD5 units: how many, their list's place in order
   size_t n_sha1 = 0, sha1_off = 0, n_sha256 = 0, sha256_off = 0;      // the SHA-1 / SHA-256 heads likewise
+  size_t n_crc32r = 0, crc32r_off = 0;              // the CRC-32 range units (MSPACK_HIP_KIND_CRC32) likewise
   size_t n_dig = 0;                                 // every digest unit, tails included: local[n - n_dig .. n)
   bool monotone, has_qtm;
 };
@@ -101,7 +103,7 @@ static int plan_units(mspack_hip_unit *units, const uint32_t *sel, size_t n_sel,
     const auto mid = std::stable_partition(idx.begin(), idx.end(), [&](uint32_t x) { return !unit_is_digest(units[x]); });
     std::sort(mid, idx.end());
     p.n_dig = (size_t)(idx.end() - mid);
-    p.n_md5 = p.n_sha1 = p.n_sha256 = 0;
+    p.n_md5 = p.n_sha1 = p.n_sha256 = p.n_crc32r = 0;
   }
   local.resize(n_sel);
   bool monotone = !per_unit_back;
@@ -139,7 +141,7 @@ static int plan_units(mspack_hip_unit *units, const uint32_t *sel, size_t n_sel,
           snprintf(errbuf, errcap, "unit %u: a wide digest unit must be followed by an MSPACK_HIP_KIND_DIGEST_MORE unit", idx[i]); return -1;
         }
       }
-      (u.kind == MSPACK_HIP_KIND_MD5 ? p.n_md5 : u.kind == MSPACK_HIP_KIND_SHA1 ? p.n_sha1 : p.n_sha256)++;
+      (u.kind == MSPACK_HIP_KIND_MD5 ? p.n_md5 : u.kind == MSPACK_HIP_KIND_SHA1 ? p.n_sha1 : u.kind == MSPACK_HIP_KIND_SHA256 ? p.n_sha256 : p.n_crc32r)++;
       u.in_off = 0; u.flags = 0;
       if (u.out_len) { out_lo = std::min<uint64_t>(out_lo, u.out_off); out_hi = std::max<uint64_t>(out_hi, u.out_off + u.out_len); }
       continue;
@@ -308,6 +310,10 @@ static void plan_lists(BatchPlan &p)
     for (size_t i = n_sel - p.n_dig; i < n_sel; i++) if (local[i].kind == dig_kind[a]) order[op++] = (uint32_t) i;
     std::stable_sort(order.begin() + *dig_off[a], order.begin() + op, [&](uint32_t x, uint32_t y) { return local[x].out_len > local[y].out_len; });
   }
+  // ... and the CRC-32 range units' list behind them
+  p.crc32r_off = op;
+  if (p.n_crc32r)
+    for (size_t i = n_sel - p.n_dig; i < n_sel; i++) if (local[i].kind == MSPACK_HIP_KIND_CRC32) order[op++] = (uint32_t) i;
 }
 
 // `sel` lists the unit indices of the batch (NULL = all n_sel units).  to_host: the outputs go back to the caller's host buffer;

@@ -1,6 +1,6 @@
 // launch.hpp -- the launch layer and the device-resident C ABI: the thread's error text, launch<> (a kernel launch whose status is
 // returned), the launch-level environment knobs, launch_kind (one codec's launches over a compact unit list), launch_crc32, launch_md5, launch_sha1 /
-// launch_sha256, the
+// launch_sha256, launch_crc32_ranges, the
 // analysis builds' debug exports, version / features / device functions, mspack_hip_decode_batch_device and _time_batch_device.
 #pragma once
 #include <mutex>
@@ -235,6 +235,40 @@ static hipError_t launch_sha256(const mspack_hip_unit *d_units, const uint32_t *
   LK(launch(mspack_sha256, dim3((unsigned)((n + 63) / 64)), dim3(64), st, d_units, d_order, (u32) n, (u32) n_table, (const u8 *) d_out, (u64) out_bytes, d_results));
   return hipSuccess;
 }
+// waves of mspack_crc32r_pass: as many as the device holds at once, eight per CU at most (nothing depends on the number being right)
+static unsigned crc32r_waves()
+{
+  static std::mutex mu;
+  static unsigned cache[MSPK_MAX_DEV_CACHE] = { 0 };
+  int dev = 0, per_cu = 0; hipDeviceProp_t pr;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MSPK_MAX_DEV_CACHE) return 2048u;
+  std::lock_guard<std::mutex> lock(mu);
+  if (!cache[dev]) {
+    if (hipGetDeviceProperties(&pr, dev) != hipSuccess) return 2048u;
+    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, mspack_crc32r_pass, 64, 0);
+    if (e != hipSuccess || per_cu < 1) per_cu = 8;
+    cache[dev] = (unsigned) pr.multiProcessorCount * (unsigned) std::min(per_cu, 8);
+  }
+  return cache[dev];
+}
+// the CRC-32 pass over the range units order[0..n) (or, order == NULL, over every unit: positions of other kinds own nothing): init, the
+// one-wave scan, the pass -- a grid no larger than the tickets the list can hold, bounded by the device's waves --, finish
+static hipError_t launch_crc32_ranges(const mspack_hip_unit *d_units, const uint32_t *d_order, size_t n, const void *d_out, size_t out_bytes,
+                                      mspack_hip_result *d_results, hipStream_t st)
+{
+  if (n == 0) return hipSuccess;
+#ifdef MSPACK_HOST_CHECK      /* tests/hostcheck runs no kernel and its stand-in for a launch computes no digest */
+  return hipErrorInvalidValue;
+#endif
+  const dim3 per_lane((unsigned)((n + 63) / 64)), block(64);
+  const uint64_t most = (uint64_t) n * (std::min<uint64_t>(out_bytes, 0xFFFFFFFFu) / CRC_SEG + 2u);      // no list of n ranges has more tickets
+  const unsigned waves = (unsigned) std::min<uint64_t>(most, crc32r_waves());
+  LK(launch(mspack_crc32r_init, per_lane, block, st, d_units, d_order, (u32) n, (u64) out_bytes, d_results));
+  LK(launch(mspack_crc32r_scan, dim3(1), block, st, d_units, d_order, (u32) n, (const u8 *) d_out, (u64) out_bytes, d_results));
+  LK(launch(mspack_crc32r_pass, dim3(waves), block, st, d_units, d_order, (u32) n, (const u8 *) d_out, (u64) out_bytes, d_results));
+  LK(launch(mspack_crc32r_finish, per_lane, block, st, d_units, d_order, (u32) n, (u64) out_bytes, d_results));
+  return hipSuccess;
+}
 #undef LK
 
 extern "C" {
@@ -302,7 +336,7 @@ int mspack_hip_debug_frame_words(const void *d_frame_scratch, size_t n_frames_to
 }
 const char *mspack_hip_version(void) { return "mspack-hip 0.4 (gfx950; LZX/LZX-DELTA/Quantum/MSZIP batch decode)"; }
 const char *mspack_hip_last_error(void) { return g_err; }
-unsigned mspack_hip_features(void) { return MSPACK_HIP_FEAT_CRC32 | MSPACK_HIP_FEAT_MD5 | MSPACK_HIP_FEAT_SHA1 | MSPACK_HIP_FEAT_SHA256 | MSPACK_HIP_FEAT_SLOTS | MSPACK_HIP_FEAT_LZSS_RING; }
+unsigned mspack_hip_features(void) { return MSPACK_HIP_FEAT_CRC32 | MSPACK_HIP_FEAT_MD5 | MSPACK_HIP_FEAT_SHA1 | MSPACK_HIP_FEAT_SHA256 | MSPACK_HIP_FEAT_SLOTS | MSPACK_HIP_FEAT_LZSS_RING | MSPACK_HIP_FEAT_CRC32_RANGES; }
 
 int mspack_hip_device_count(void) {
   int n = 0;
@@ -322,7 +356,7 @@ int mspack_hip_decode_batch_device(const mspack_hip_unit *d_units, const uint32_
 {
   (void) in_bytes;
   if (n_units == 0) return 0;
-  if ((kind_mask & 0x301FEu) == 0) kind_mask |= 0xFEu;  // bit k = units of kind k may be present; none = every codec (and no digest units)
+  if ((kind_mask & 0x1301FEu) == 0) kind_mask |= 0xFEu;  // bit k = units of kind k may be present; none = every codec (and no digest units)
   // the caller's unit table lives on the device, so the kinds cannot be compacted here: every codec in the
   // mask gets the whole grid and blocks of other kinds leave at once.  Callers with mixed batches pass one
   // order list per codec and a one-bit mask (what the host-buffer entry points below do).
@@ -342,6 +376,9 @@ int mspack_hip_decode_batch_device(const mspack_hip_unit *d_units, const uint32_
     CK(launch_sha1(d_units, d_order, n_units, n_units, d_out, out_bytes, d_results, (hipStream_t) stream));
   if (kind_mask & (1u << MSPACK_HIP_KIND_SHA256))
     CK(launch_sha256(d_units, d_order, n_units, n_units, d_out, out_bytes, d_results, (hipStream_t) stream));
+  // ... and the CRC-32 range units' pass (four launches)
+  if (kind_mask & (1u << MSPACK_HIP_KIND_CRC32))
+    CK(launch_crc32_ranges(d_units, d_order, n_units, d_out, out_bytes, d_results, (hipStream_t) stream));
   return 0;
 }
 

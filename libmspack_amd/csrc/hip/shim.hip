@@ -50,6 +50,7 @@ static_assert(sizeof(lzxp::LzxFrameRec) == sizeof(lzxn::LzxFrameRec), "one recor
 #include "lzss_kernel.hpp"
 #include "lzss_ring_kernel.hpp"
 #include "crc32_kernel.hpp"
+#include "crc32_range_kernel.hpp"
 #include "md5_kernel.hpp"
 #include "sha_kernel.hpp"
 

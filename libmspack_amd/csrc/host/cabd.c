@@ -121,6 +121,7 @@ struct cabd_p {
   struct mspack_system *system;
   int error, read_error;
   int searchbuf_size, fix_mszip, buf_size, salvage;
+  int hip_crc32;                      /* MSCABD_PARAM_HIP_CRC32: 1 = the batches carry one MSPACK_HIP_KIND_CRC32 unit per file, for mspack_cabd_crc32() */
   int devices, cache_mb, hip_digests; /* hip_digests: MSCABD_PARAM_HIP_DIGESTS, a mask of MSPACK_DIGEST_* (MSCABD_PARAM_HIP_MD5 is its bit 1) */
   struct digest_sink *sink;           /* mspack_cabd_digest is running: what extract() would write goes here instead of a file */
   const unsigned char *sink_kept;     /* ... or the call's bytes were exactly a file whose digest the batch has taken: that one */
@@ -787,6 +788,7 @@ struct gathered {
 /* diagnostics (mspack.h: mspack_cabd_md5_counts, mspack_cabd_digest_counts): per algorithm, successful digest() calls answered from a
  * digest the batch took on the device / hashed on the host, over all decompressors of the process */
 static unsigned long long g_digest_counts[3][2];
+static unsigned long long g_crc32_counts[2];            /* the same for mspack_cabd_crc32() */
 
 /* The request boundaries a Quantum folder's files imply -- cabd_extract asks its codec for the bytes in front of a file, then for
  * the file (cabd.c:1195-1218): requests end where files begin and where they end.  Ascending, without duplicates, inside
@@ -1037,7 +1039,7 @@ static int decode_cabinets(struct cabd_p *self, struct cab_p **cabs, size_t n_ca
   size_t kept = used;                                   /* what the folders this call decodes have taken of the budget */
   int err = MSPACK_ERR_OK, rc, again = 0;
   /* the algorithms the batch carries units for: asked for, the provider can (one without mspack_hip_features cannot), a ratio above 0 */
-  const int dev_algs = digest_device_algs(self->hip_digests);
+  const int dev_algs = digest_device_algs(self->hip_digests | (self->hip_crc32 ? DIGEST_ALG_CRC32 : 0));
   size_t dg_cap = 0, ndg = 0;                           /* digest units: at most digest_units_per_file per file of the gathered folders; those made */
   size_t n_qtm_files = 0;                               /* files in Quantum folders: two marks each at most (gather_marks) */
   for (c = 0; c < n_cabs; c++) {
@@ -1126,7 +1128,8 @@ static int decode_cabinets(struct cabd_p *self, struct cab_p **cabs, size_t n_ca
   }
   if (dg_cap) {
     /* the digest units (host_digest.h: digest_emit_file) of every file that lies inside what its folder's blocks hold, beside the
-     * marks gather_marks collected; the long ones are left to the host (digest_ratio, per algorithm, of the whole batch's bytes) */
+     * marks gather_marks collected; the long ones are left to the host (digest_ratio, per algorithm, of the whole batch's bytes) --
+     * for the hashes only: with DIGEST_ALG_CRC32 in dev_algs every such file gets its CRC-32 unit, whatever its length */
     double sum = 0.0, ratio[3];
     int pass;
     digest_ratios(ratio);
@@ -1511,6 +1514,25 @@ int mspack_cabd_digest(struct mscab_decompressor *base, struct mscabd_file *file
   return err;
 }
 
+/* mspack.h: extract() with the writes replaced by zlib's CRC-32 */
+int mspack_cabd_crc32(struct mscab_decompressor *base, struct mscabd_file *file, unsigned int *crc)
+{
+  struct cabd_p *self = (struct cabd_p *) base;
+  struct digest_sink k;
+  int err = crc32_call_args(file, crc);
+  if (!self) return MSPACK_ERR_ARGS;
+  if (err) return self->error = err;
+  sink_init(&k, DIGEST_ALG_CRC32);
+  self->sink = &k; self->sink_kept = NULL;
+  err = cabd_extract(base, file, NULL);
+  self->sink = NULL;
+  if (err == MSPACK_ERR_OK) crc32_call_done(&k, self->sink_kept, crc, g_crc32_counts);
+  self->sink_kept = NULL;
+  return err;
+}
+
+void mspack_cabd_crc32_counts(unsigned long long counts[2], int reset) { crc32_counts_get(g_crc32_counts, counts, reset); }
+
 int mspack_cabd_md5(struct mscab_decompressor *base, struct mscabd_file *file, unsigned char digest[16]) { return mspack_cabd_digest(base, file, MSPACK_DIGEST_MD5, digest, 16); }
 
 void mspack_cabd_digest_counts(int alg, unsigned long long counts[2], int reset) { digest_counts_get(g_digest_counts, alg, counts, reset); }
@@ -1530,6 +1552,7 @@ static int cabd_param(struct mscab_decompressor *base, int param, int value)
   case MSCABD_PARAM_HIP_CACHE_MB: if (value < 1) return MSPACK_ERR_ARGS; self->cache_mb = value; break;
   case MSCABD_PARAM_HIP_MD5:      if (value != 0 && value != 1) return MSPACK_ERR_ARGS; self->hip_digests = (self->hip_digests & ~MSPACK_DIGEST_MD5) | (value ? MSPACK_DIGEST_MD5 : 0); break;
   case MSCABD_PARAM_HIP_DIGESTS:  if (value < 0 || value > 7) return MSPACK_ERR_ARGS; self->hip_digests = value; break;
+  case MSCABD_PARAM_HIP_CRC32:    if (value != 0 && value != 1) return MSPACK_ERR_ARGS; self->hip_crc32 = value; break;
   default: return MSPACK_ERR_ARGS;
   }
   return MSPACK_ERR_OK;
@@ -1549,6 +1572,7 @@ int mspack_cabd_get_param(struct mscab_decompressor *base, int param, int *value
   case MSCABD_PARAM_HIP_CACHE_MB: *value = self->cache_mb; break;
   case MSCABD_PARAM_HIP_MD5:      *value = (self->hip_digests & MSPACK_DIGEST_MD5) ? 1 : 0; break;
   case MSCABD_PARAM_HIP_DIGESTS:  *value = self->hip_digests; break;
+  case MSCABD_PARAM_HIP_CRC32:    *value = self->hip_crc32; break;
   default: return MSPACK_ERR_ARGS;
   }
   return MSPACK_ERR_OK;
@@ -1609,7 +1633,7 @@ struct mscab_decompressor *mspack_create_cab_decompressor(struct mspack_system *
   self->system = sys;
   self->error = MSPACK_ERR_OK; self->read_error = MSPACK_ERR_OK;
   self->searchbuf_size = 32768; self->fix_mszip = 0; self->buf_size = 4096; self->salvage = 0;
-  self->devices = 1; self->cache_mb = 2048; self->list_stamp = 0; self->hip_digests = 0; self->sink = NULL; self->sink_kept = NULL;
+  self->devices = 1; self->cache_mb = 2048; self->list_stamp = 0; self->hip_digests = 0; self->hip_crc32 = 0; self->sink = NULL; self->sink_kept = NULL;
   memset(&self->st, 0, sizeof(self->st)); self->st_offset = 0; self->st_active = 0; self->last_folder = NULL;
   self->msg_folder = NULL; self->msg_offset = 0; self->msg_next = 0; self->msg_next_ck = 0;
   self->live_folder = NULL; self->live_offset = 0; self->live_failed = 0; self->live_err = MSPACK_ERR_OK;

@@ -98,6 +98,7 @@ struct chmd_p {
   int error;
   struct chm_p *v_chm; struct vdec v;
   int hip_digests;                    /* MSCHMD_PARAM_HIP_DIGESTS: a mask of MSPACK_DIGEST_* */
+  int hip_crc32;                      /* MSCHMD_PARAM_HIP_CRC32: 1 = a chunk's batch carries one MSPACK_HIP_KIND_CRC32 unit per file, for mspack_chmd_crc32() */
   struct digest_sink *sink;           /* mspack_chmd_digest is running: what extract() would write goes here instead of a file */
   int sink_whole;                     /* ... and the emit step hands over exactly the file's plain range, of a call that is good so far */
   const unsigned char *sink_kept;     /* ... and that file's digest was taken by its chunk's batch: this one */
@@ -106,6 +107,9 @@ struct chmd_p {
 };
 /* per algorithm, successful mspack_chmd_digest() calls answered from a device digest / hashed on the host (mspack.h) */
 static unsigned long long g_digest_counts[3][2];
+static unsigned long long g_crc32_counts[2];            /* the same for mspack_chmd_crc32() */
+/* the algorithms asked for, CRC-32 (host_digest.h: DIGEST_ALG_CRC32) among them */
+#define CHM_ASKED_ALGS(self) ((self)->hip_digests | ((self)->hip_crc32 ? DIGEST_ALG_CRC32 : 0))
 /* batch calls this driver has issued, and the interval units in them (mspack.h: mspack_chmd_batch_counts) */
 static unsigned long long g_batch_counts[2];
 static void count_batch(size_t n_intervals)
@@ -575,7 +579,7 @@ static void chunk_keep_digests(struct mspack_system *sys, struct chm_chunk *ch, 
 /* the algorithms a batch that decodes chunk dg_ch (from stream offset lo on) carries digest units for: asked for, not taken yet */
 static int chunk_digest_algs(const struct chmd_p *self, const struct chm_p *c, off_t lo, const struct chm_chunk *dg_ch)
 {
-  return dg_ch && c->n_dfiles && c->padded_len > lo ? digest_device_algs(self->hip_digests & ~dg_ch->dg_algs) : 0;
+  return dg_ch && c->n_dfiles && c->padded_len > lo ? digest_device_algs(CHM_ASKED_ALGS(self) & ~dg_ch->dg_algs) : 0;
 }
 /* ... and those units (chm_digest_plan) for intervals [first, first+count), their ranges counted from out_base of the batch's output;
  * units == NULL: counts only */
@@ -746,7 +750,7 @@ static int issue_batch(struct chmd_p *self, struct chm_pick *pk, size_t n, uint6
   if (!B) return MSPACK_ERR_NOMEMORY;
   memset(B, 0, sizeof(*B));
   B->owner = self; B->n = n;
-  if (self->hip_digests) digest_ratios(ratio);
+  if (CHM_ASKED_ALGS(self)) digest_ratios(ratio);
   for (k = 0; k < n; k++) {
     pk[k].out_base = out_total;
     pk[k].dg_algs = chunk_digest_algs(self, pk[k].c, (off_t) pk[k].first * pk[k].c->interval_bytes, pk[k].ch);
@@ -1361,6 +1365,25 @@ int mspack_chmd_digest(struct mschm_decompressor *base, struct mschmd_file *file
   return err;
 }
 
+/* mspack.h: extract() with the writes replaced by zlib's CRC-32 */
+int mspack_chmd_crc32(struct mschm_decompressor *base, struct mschmd_file *file, unsigned int *crc)
+{
+  struct chmd_p *self = (struct chmd_p *) base;
+  struct digest_sink k;
+  int err = crc32_call_args(file, crc);
+  if (!self) return MSPACK_ERR_ARGS;
+  if (err) return self->error = err;
+  sink_init(&k, DIGEST_ALG_CRC32);
+  self->sink = &k; self->sink_whole = 0; self->sink_kept = NULL;
+  err = chmd_extract(base, file, NULL);
+  self->sink = NULL;
+  if (err == MSPACK_ERR_OK) crc32_call_done(&k, self->sink_kept, crc, g_crc32_counts);
+  self->sink_whole = 0; self->sink_kept = NULL;
+  return err;
+}
+
+void mspack_chmd_crc32_counts(unsigned long long counts[2], int reset) { crc32_counts_get(g_crc32_counts, counts, reset); }
+
 void mspack_chmd_digest_counts(int alg, unsigned long long counts[2], int reset) { digest_counts_get(g_digest_counts, alg, counts, reset); }
 
 void mspack_chmd_batch_counts(unsigned long long counts[2], int reset)
@@ -1453,6 +1476,7 @@ int mspack_chmd_set_param(struct mschm_decompressor *base, int param, int value)
 {
   struct chmd_p *self = (struct chmd_p *) base;
   if (!self) return MSPACK_ERR_ARGS;
+  if (param == MSCHMD_PARAM_HIP_CRC32) { if (value != 0 && value != 1) return MSPACK_ERR_ARGS; self->hip_crc32 = value; return MSPACK_ERR_OK; }
   if (param != MSCHMD_PARAM_HIP_DIGESTS || value < 0 || value > 7) return MSPACK_ERR_ARGS;
   self->hip_digests = value;
   return MSPACK_ERR_OK;
@@ -1461,8 +1485,8 @@ int mspack_chmd_set_param(struct mschm_decompressor *base, int param, int value)
 int mspack_chmd_get_param(struct mschm_decompressor *base, int param, int *value)
 {
   struct chmd_p *self = (struct chmd_p *) base;
-  if (!self || !value || param != MSCHMD_PARAM_HIP_DIGESTS) return MSPACK_ERR_ARGS;
-  *value = self->hip_digests;
+  if (!self || !value || (param != MSCHMD_PARAM_HIP_DIGESTS && param != MSCHMD_PARAM_HIP_CRC32)) return MSPACK_ERR_ARGS;
+  *value = param == MSCHMD_PARAM_HIP_CRC32 ? self->hip_crc32 : self->hip_digests;
   return MSPACK_ERR_OK;
 }
 

@@ -13,18 +13,27 @@
 #include "mspack_hip.h"
 #include "md5.h"
 #include "sha.h"
+#include "crc32.h"
+
+/* CRC-32 (zlib's) rides in the drivers' masks of algorithms as a bit of its own, INTERNAL to the drivers: no MSPACK_DIGEST_* value (8 is
+ * MSPACK_ERR_ARGS in the digest() calls and in *_PARAM_HIP_DIGESTS); mspack_cabd_crc32() / mspack_chmd_crc32() and *_PARAM_HIP_CRC32 set it.
+ * Its unit is MSPACK_HIP_KIND_CRC32 -- any length: the ratio rule does not apply --, its kept record holds the checksum in d[0 .. 4),
+ * little-endian, as the unit's result.out_len lies there */
+#define DIGEST_ALG_CRC32 8
 
 /* a digest call's hash in progress: one of the three */
-struct digest_sink { int alg; struct mspack_md5 md5; struct mspack_sha sha; };
+struct digest_sink { int alg; struct mspack_md5 md5; struct mspack_sha sha; uint32_t crc; };
 static inline void sink_init(struct digest_sink *k, int alg)
 {
-  k->alg = alg;
+  k->alg = alg; k->crc = 0;
+  if (alg == DIGEST_ALG_CRC32) return;
   if (alg == MSPACK_DIGEST_MD5) mspack_md5_init(&k->md5);
   else if (alg == MSPACK_DIGEST_SHA1) mspack_sha1_init(&k->sha);
   else mspack_sha256_init(&k->sha);
 }
 static inline void sink_update(struct digest_sink *k, const void *data, size_t n)
 {
+  if (k->alg == DIGEST_ALG_CRC32) { k->crc = mspack_crc32_step(k->crc, data, n); return; }
   if (k->alg == MSPACK_DIGEST_MD5) mspack_md5_update(&k->md5, data, n); else mspack_sha_update(&k->sha, data, n);
 }
 static inline void sink_final(struct digest_sink *k, unsigned char *digest)
@@ -45,6 +54,7 @@ static inline size_t digest_units_per_file(int algs)
 {
   size_t n = 0; int alg;
   for (alg = MSPACK_DIGEST_MD5; alg <= MSPACK_DIGEST_SHA256; alg <<= 1) if (algs & alg) n += digest_units(alg);
+  if (algs & DIGEST_ALG_CRC32) n++;
   return n;
 }
 
@@ -87,6 +97,8 @@ static inline int digest_device_algs(int asked)
   int alg, algs = 0;
   for (alg = MSPACK_DIGEST_MD5; alg <= MSPACK_DIGEST_SHA256; alg <<= 1)
     if ((asked & alg) && mspack_hip_features && (mspack_hip_features() & digest_feat(alg)) && digest_ratio(alg) > 0.0) algs |= alg;
+  /* (CRC-32 range units: no ratio -- the device takes them at any length) */
+  if ((asked & DIGEST_ALG_CRC32) && mspack_hip_features && (mspack_hip_features() & MSPACK_HIP_FEAT_CRC32_RANGES)) algs |= DIGEST_ALG_CRC32;
   return algs;
 }
 static inline void digest_ratios(double ratio[3]) { int alg; for (alg = MSPACK_DIGEST_MD5; alg <= MSPACK_DIGEST_SHA256; alg <<= 1) ratio[digest_index(alg)] = digest_ratio(alg); }
@@ -112,6 +124,14 @@ static inline size_t digest_emit_file(uint64_t out_off, uint32_t len, double sum
     }
     made += need;
   }
+  if (algs & DIGEST_ALG_CRC32) {                          /* behind the hashes (the table's order), whatever the file's length */
+    if (units && n + made + 1 <= cap) {
+      memset(&units[n + made], 0, sizeof(*units));
+      units[n + made].kind = MSPACK_HIP_KIND_CRC32;
+      units[n + made].out_off = out_off; units[n + made].out_len = len;
+    }
+    made++;
+  }
   return made;
 }
 
@@ -136,7 +156,7 @@ static inline void digest_table_harvest(struct digest_table *t, const mspack_hip
 {
   size_t j; int ascending = 1;
   for (j = 0; j < n; j++) {
-    const int alg = digest_alg_of_kind(units[j].kind), wide = alg && digest_units(alg) == 2;
+    const int alg = units[j].kind == MSPACK_HIP_KIND_CRC32 ? DIGEST_ALG_CRC32 : digest_alg_of_kind(units[j].kind), wide = alg && digest_units(alg) == 2;
     struct digest_kept *e = &t->e[t->n];
     if (!alg || res[j].err != MSPACK_ERR_OK) continue;            /* (a tail is taken with its head) */
     if (wide && (j + 1 >= n || units[j + 1].kind != MSPACK_HIP_KIND_DIGEST_MORE || res[j + 1].err != MSPACK_ERR_OK)) continue;
@@ -182,6 +202,27 @@ static inline void digest_call_done(struct digest_sink *k, const unsigned char *
 {
   if (kept) memcpy(digest, kept, (size_t) digest_bytes(k->alg)); else sink_final(k, digest);
   __atomic_fetch_add(&counts[digest_index(k->alg)][kept ? 0 : 1], 1ull, __ATOMIC_RELAXED);
+}
+/* the frame of a crc32() call: the same with a checksum for a digest -- counts[0: from the device, 1: on the host] */
+static inline int crc32_call_args(const void *file, unsigned int *crc)
+{
+  if (!crc) return MSPACK_ERR_ARGS;
+  *crc = 0;
+  return file ? MSPACK_ERR_OK : MSPACK_ERR_ARGS;
+}
+static inline void crc32_call_done(const struct digest_sink *k, const unsigned char *kept, unsigned int *crc, unsigned long long counts[2])
+{
+  if (kept) *crc = (unsigned int) kept[0] | ((unsigned int) kept[1] << 8) | ((unsigned int) kept[2] << 16) | ((unsigned int) kept[3] << 24);
+  else *crc = k->crc;
+  __atomic_fetch_add(&counts[kept ? 0 : 1], 1ull, __ATOMIC_RELAXED);
+}
+static inline void crc32_counts_get(unsigned long long counts[2], unsigned long long out[2], int reset)
+{
+  int i;
+  for (i = 0; i < 2; i++) {
+    if (out) out[i] = __atomic_load_n(&counts[i], __ATOMIC_RELAXED);
+    if (reset) __atomic_store_n(&counts[i], 0ull, __ATOMIC_RELAXED);
+  }
 }
 /* the *_digest_counts calls: the pair of one algorithm (an unknown one: zeros), optionally reset */
 static inline void digest_counts_get(unsigned long long counts[3][2], int alg, unsigned long long out[2], int reset)
