@@ -174,10 +174,17 @@ struct mscabd_file {
                                             mspack_cabd_digest() (0 to 7, default 0; other values: MSPACK_ERR_ARGS) */
 #define MSCABD_PARAM_HIP_CRC32    (105)  /* 1: batches carry one CRC-32 unit per file, for mspack_cabd_crc32() (0 or 1, default 0; other
                                             values: MSPACK_ERR_ARGS).  104 is not a parameter */
-/* digest algorithms (mspack_cabd_digest, MSCABD_PARAM_HIP_DIGESTS) */
+#define MSCABD_PARAM_HIP_DIGESTS64 (106) /* a mask of MSPACK_DIGEST_SHA384 | MSPACK_DIGEST_SHA512: the 64-bit-word algorithms the batches carry
+                                            digest units for, per file, for mspack_cabd_digest() (0, 16, 32 or 48, default 0; other
+                                            values: MSPACK_ERR_ARGS).  Read where MSCABD_PARAM_HIP_DIGESTS is read; that one keeps
+                                            taking 0 to 7 only */
+/* digest algorithms (mspack_cabd_digest, MSCABD_PARAM_HIP_DIGESTS, MSCABD_PARAM_HIP_DIGESTS64) */
 #define MSPACK_DIGEST_MD5     (1)        /* RFC 1321, 16 bytes */
 #define MSPACK_DIGEST_SHA1    (2)        /* FIPS 180-4, 20 bytes */
 #define MSPACK_DIGEST_SHA256  (4)        /* FIPS 180-4, 32 bytes */
+/* (8 is no algorithm: MSPACK_ERR_ARGS) */
+#define MSPACK_DIGEST_SHA384  (16)       /* FIPS 180-4, 48 bytes; its bit belongs to MSCABD_PARAM_HIP_DIGESTS64 / MSCHMD_PARAM_HIP_DIGESTS64 */
+#define MSPACK_DIGEST_SHA512  (32)       /* FIPS 180-4, 64 bytes; likewise */
 
 struct mscab_decompressor {
   struct mscabd_cabinet * (*open) (struct mscab_decompressor *self, const char *filename);
@@ -238,8 +245,8 @@ extern void mspack_cabd_md5_counts(unsigned long long counts[2], int reset);
 /* A digest of a file, by algorithm: mspack_cabd_md5() for MD5, SHA-1 and SHA-256 -- what package verifiers of cabinets check today
  * (Authenticode catalogs, update manifests, driver packages).  Everything said of mspack_cabd_md5() holds: the return codes, what the
  * call counts as for the decompressor's sticky state, the lines said through sys->message, no output file, no sys->write.
- *   alg         MSPACK_DIGEST_MD5, _SHA1 or _SHA256 -- one of them; anything else: MSPACK_ERR_ARGS
- *   digest      with MSPACK_ERR_OK the algorithm's 16, 20 or 32 bytes in the standard's byte order; with any other code that many
+ *   alg         MSPACK_DIGEST_MD5, _SHA1, _SHA256, _SHA384 or _SHA512 -- one of them; anything else: MSPACK_ERR_ARGS
+ *   digest      with MSPACK_ERR_OK the algorithm's 16, 20, 32, 48 or 64 bytes in the standard's byte order; with any other code that many
  *               zero bytes (if they fit)
  *   digest_cap  the room at digest; below the algorithm's length: MSPACK_ERR_ARGS, nothing written
  * With the algorithm's bit set in MSCABD_PARAM_HIP_DIGESTS (before the batch is built, as for MSCABD_PARAM_HIP_MD5) and a batch provider
@@ -249,6 +256,9 @@ extern void mspack_cabd_md5_counts(unsigned long long counts[2], int reset);
  * SHA-1 / SHA-256 with identical results: the bit off, stored folders, failing or partial files, a provider without the feature bit
  * (or without mspack_hip_features() at all), and files too long for one lane of the device -- per algorithm, by that algorithm's
  * own ratio (MSPACK_HIP_SHA1_RATIO, MSPACK_HIP_SHA256_RATIO beside MSPACK_HIP_MD5_RATIO).
+ * SHA-384 and SHA-512 work the same way with their bits in MSCABD_PARAM_HIP_DIGESTS64, MSPACK_HIP_FEAT_SHA384 / _SHA512, two / three
+ * MSPACK_HIP_KIND_DIGEST_MORE units behind each head, plain-C SHA-384 / SHA-512 on the host and one ratio for both
+ * (MSPACK_HIP_SHA512_RATIO: they share a kernel).
  * As with MSCABD_PARAM_HIP_MD5, a batch that carries digest units of any algorithm does not run as a job: it is waited for as a
  * whole.  Leave the bits off for callers that extract. */
 extern int mspack_cabd_digest(struct mscab_decompressor *self, struct mscabd_file *file, int alg, unsigned char *digest, size_t digest_cap);
@@ -344,6 +354,9 @@ struct mschm_decompressor {
                                             for mspack_chmd_digest() (0 to 7, default 0; other values: MSPACK_ERR_ARGS) */
 #define MSCHMD_PARAM_HIP_CRC32   (105)   /* 1: a chunk's batch carries one CRC-32 unit per file, for mspack_chmd_crc32() (0 or 1, default 0;
                                             other values: MSPACK_ERR_ARGS).  104 is not a parameter */
+#define MSCHMD_PARAM_HIP_DIGESTS64 (106) /* a mask of MSPACK_DIGEST_SHA384 | MSPACK_DIGEST_SHA512: the 64-bit-word algorithms a chunk's batch
+                                            carries digest units for (0, 16, 32 or 48, default 0; other values: MSPACK_ERR_ARGS).  Read
+                                            where MSCHMD_PARAM_HIP_DIGESTS is read, mspack_chmd_prefetch() included */
 /* MSPACK_ERR_ARGS for an unknown parameter or a NULL argument; get_param answers what set_param last stored (the default before that) */
 extern int mspack_chmd_set_param(struct mschm_decompressor *self, int param, int value);
 extern int mspack_chmd_get_param(struct mschm_decompressor *self, int param, int *value);
@@ -353,12 +366,12 @@ extern int mspack_chmd_get_param(struct mschm_decompressor *self, int param, int
  *               extract(), the lines said through sys->message ("file is ... bytes longer than ...", the LZX reset warning) are
  *               said in this call, the cache of decoded chunks is used and aged.  It opens no output file and never calls
  *               sys->write.  last_error() answers the same.
- *   alg         MSPACK_DIGEST_MD5, _SHA1 or _SHA256 -- one of them; anything else: MSPACK_ERR_ARGS, nothing written
- *   digest      with MSPACK_ERR_OK the algorithm's 16, 20 or 32 bytes over exactly the bytes extract() would have handed to
+ *   alg         MSPACK_DIGEST_MD5, _SHA1, _SHA256, _SHA384 or _SHA512 -- one of them; anything else: MSPACK_ERR_ARGS, nothing written
+ *   digest      with MSPACK_ERR_OK the algorithm's 16, 20, 32, 48 or 64 bytes over exactly the bytes extract() would have handed to
  *               sys->write (a file of length 0: the digest of the empty message; files of section 0 are hashed as they are read);
  *               with any other code that many zero bytes (if they fit)
  *   digest_cap  the room at digest; below the algorithm's length: MSPACK_ERR_ARGS, nothing written
- * With the algorithm's bit set in MSCHMD_PARAM_HIP_DIGESTS when a chunk of the compressed section is decoded (up to 64 MiB of reset
+ * With the algorithm's bit set in MSCHMD_PARAM_HIP_DIGESTS (SHA-384, SHA-512: in MSCHMD_PARAM_HIP_DIGESTS64) when a chunk of the compressed section is decoded (up to 64 MiB of reset
  * intervals, one GPU batch) and a batch provider that reports the algorithm's feature bit, that batch carries one digest unit per
  * algorithm for every file that lies wholly inside the chunk, and the digests are kept with the chunk, also when its bytes leave
  * the cache.  A call is answered from there when it succeeds and hands over exactly the file's plain range as the chunk holds it.

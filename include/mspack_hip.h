@@ -104,6 +104,20 @@ extern "C" {
                                                                               end -- zlib.crc32(bytes) ^ 0xFFFFFFFF; 0xFFFFFFFF for no bytes
                                        Ask mspack_hip_features() & MSPACK_HIP_FEAT_CRC32_RANGES first                          */
 
+/* Kinds 21 to 23 are not defined. */
+#define MSPACK_HIP_KIND_SHA384  24   /* a wide digest unit with every convention of MSPACK_HIP_KIND_SHA256: the SHA-384 (FIPS 180-4) of the
+                                       range, 48 bytes.  64-bit words: a kernel of its own, shared with SHA-512.  A head of a digest
+                                       of n bytes at units[i] needs exactly ceil(n / 16) - 1 MSPACK_HIP_KIND_DIGEST_MORE units at
+                                       units[i + 1 ..]: 1 for SHA-1 and SHA-256, 2 for SHA-384, 3 for SHA-512.  Bytes 16 k to
+                                       16 k + 15 of the digest come back in results[i + k] from out_len on, in the standard's byte
+                                       order -- memcpy(d + 16 * k, &results[i + k].out_len, 16) --; the head's lane writes all of
+                                       them (tails: err 0, flags 0, unused words 0).  Too few tails, a tail that names bytes, a tail
+                                       with no head or more tails than its head needs are the errors described at
+                                       MSPACK_HIP_KIND_DIGEST_MORE (the device-resident entry: MSPACK_ERR_ARGS in that unit's result,
+                                       nothing read; a head whose range leaves out_bytes: all of its tails' results 0).  Ask
+                                       mspack_hip_features() & MSPACK_HIP_FEAT_SHA384 first                                    */
+#define MSPACK_HIP_KIND_SHA512  25   /* the same with SHA-512 (FIPS 180-4), 64 bytes, three tails; MSPACK_HIP_FEAT_SHA512             */
+
 #define MSPACK_HIP_MASK_FRAME_TABLES 0x80000000u   /* mspack_hip_decode_batch_device(kind_mask): see there */
 #define MSPACK_HIP_MASK_CRC32        0x40000000u   /* mspack_hip_decode_batch_device(kind_mask): units may carry MSPACK_HIP_UF_CRC32 */
 #define MSPACK_HIP_MASK_LZSS_RING    0x20000000u   /* mspack_hip_decode_batch_device(kind_mask): LZSS units may carry MSPACK_HIP_UF_LZSS_RING */
@@ -243,6 +257,8 @@ const char *mspack_hip_last_error(void);
 #define MSPACK_HIP_FEAT_SLOTS 16u       /* mspack_hip_set_slots / _slots / _slot_stats: context slots of the host-buffer entry points */
 #define MSPACK_HIP_FEAT_LZSS_RING 32u    /* MSPACK_HIP_UF_LZSS_RING / MSPACK_HIP_MASK_LZSS_RING */
 #define MSPACK_HIP_FEAT_CRC32_RANGES 64u /* MSPACK_HIP_KIND_CRC32 */
+#define MSPACK_HIP_FEAT_SHA384 128u     /* MSPACK_HIP_KIND_SHA384 (and two MSPACK_HIP_KIND_DIGEST_MORE tails per head) */
+#define MSPACK_HIP_FEAT_SHA512 256u     /* MSPACK_HIP_KIND_SHA512 (and three MSPACK_HIP_KIND_DIGEST_MORE tails per head) */
 unsigned mspack_hip_features(void);
 
 /* ---- device-resident batch decode (the hot path proper) ---------------------------------------
@@ -274,6 +290,9 @@ unsigned mspack_hip_features(void);
  *                bit MSPACK_HIP_KIND_SHA1 (16) / MSPACK_HIP_KIND_SHA256 (17) set = heads of that algorithm (with their tails) may
  *                be present: only then is that algorithm's pass launched, one launch each, behind everything else on the stream
  *                like the MD5 pass; a mask of digest bits alone launches those passes only
+ *                bit MSPACK_HIP_KIND_SHA384 (24) / MSPACK_HIP_KIND_SHA512 (25) set = SHA-384 / SHA-512 heads (with their tails) may be
+ *                present: only then is their pass launched -- ONE launch for both, the two share a kernel --, behind everything else
+ *                on the stream like the other digest passes; with one of the two bits the other algorithm's heads are left alone
  *                bit MSPACK_HIP_KIND_CRC32 (20) set = CRC-32 range units may be present: only then is their pass launched (four launches:
  *                results, a one-wave scan of the ranges' segment counts, the segments, tidying up), behind everything else on the
  *                stream like the MD5 pass.  While it runs it keeps its bookkeeping in the range units' own in_used, good_len and
@@ -309,7 +328,7 @@ size_t mspack_hip_frame_scratch_bytes(size_t n_frames_total);
  * DMA that need not wait for the other streams; a buffer that cannot be registered is copied the ordinary way (MSPACK_HIP_PIN_OUT=0: always).
  * `units[i].frame_base` is filled in by the call.  Synchronous.  Bytes of the output arena
  * BETWEEN units that lie inside a copied span (alignment padding, the MSZIP slack) are unspecified afterwards.
- * Digest units (MSPACK_HIP_KIND_MD5, _SHA1, _SHA256 and their _DIGEST_MORE tails, MSPACK_HIP_KIND_CRC32) are kept out of the chunk cutting; their passes
+ * Digest units (MSPACK_HIP_KIND_MD5, _SHA1, _SHA256, _SHA384, _SHA512 and their _DIGEST_MORE tails, MSPACK_HIP_KIND_CRC32) are kept out of the chunk cutting; their passes
  * (one per algorithm) run once per device, behind the last chunk's
  * launches and before the results go back -- over the device's copy of the output arena, which holds what this call's decoding
  * units stored (bytes of a range that no unit of the call wrote are unspecified).  mspack_hip_job_wait_unit() on a digest unit

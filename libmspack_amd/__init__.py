@@ -19,7 +19,8 @@ KIND_XORSUM = 7
 KIND_MD5 = 8                 # a digest unit: the MD5 of out[out_off : out_off + out_len] once the batch's decoding units have stored
 KIND_SHA1, KIND_SHA256 = 16, 17   # wide digest units (20 / 32 bytes): each needs a KIND_DIGEST_MORE unit right behind it in the table
 KIND_DIGEST_MORE = 18            # ... whose result takes the digest's bytes beyond sixteen
-DIGEST_BYTES = {KIND_MD5: 16, KIND_SHA1: 20, KIND_SHA256: 32}
+KIND_SHA384, KIND_SHA512 = 24, 25  # wide digest units of 48 / 64 bytes: two / three KIND_DIGEST_MORE units behind each
+DIGEST_BYTES = {KIND_MD5: 16, KIND_SHA1: 20, KIND_SHA256: 32, KIND_SHA384: 48, KIND_SHA512: 64}
 F_E8_APPLIED, F_LOOKAHEAD_READ, F_INTEL_HEADER, F_BLOCK_OPEN, F_FRAMES_ADOPTED = 1, 2, 4, 16, 32
 UF_MSZIP_REPAIR = 1
 UF_CRC32 = 128               # result.in_used = CRC-32 (OAB flavour: zlib.crc32(out[:out_len]) ^ 0xFFFFFFFF) of the decoded bytes
@@ -33,6 +34,8 @@ UF_LZSS_RING = 256           # KIND_LZSS: the window in LDS, nothing owned below
 FEAT_LZSS_RING = 32
 MASK_LZSS_RING = 0x20000000  # decode_batch_device(kind_mask): launch the kernel of the units that carry UF_LZSS_RING
 MASK_SHA1, MASK_SHA256 = 1 << KIND_SHA1, 1 << KIND_SHA256     # ... the SHA-1 / the SHA-256 pass
+FEAT_SHA384, FEAT_SHA512 = 128, 256
+MASK_SHA384, MASK_SHA512 = 1 << KIND_SHA384, 1 << KIND_SHA512     # ... the SHA-384 / SHA-512 pass (one launch for both) takes that algorithm's heads
 KIND_CRC32R = 20             # a digest unit: zlib.crc32 of out[out_off : out_off + out_len], at any length -> result.out_len
 FEAT_CRC32_RANGES = 64
 MASK_CRC32R = 1 << KIND_CRC32R   # decode_batch_device(kind_mask): launch the CRC-32 range pass
@@ -261,16 +264,16 @@ def result_digests(res):
 
 
 def digest_units(ranges, kinds):
-    """digest units for (out_off, out_len) ranges, kinds[i] = KIND_MD5 / KIND_SHA1 / KIND_SHA256 (or one kind for all): a wide head
-    is followed by its KIND_DIGEST_MORE unit -> (the units, the index of every range's head in them)"""
+    """digest units for (out_off, out_len) ranges, kinds[i] = KIND_MD5 / KIND_SHA1 / KIND_SHA256 / KIND_SHA384 / KIND_SHA512 (or one kind
+    for all): a wide head is followed by its KIND_DIGEST_MORE units, one per sixteen bytes beyond the first sixteen -> (the units, the
+    index of every range's head in them)"""
     if isinstance(kinds, int):
         kinds = [kinds] * len(ranges)
     rows, heads = [], []
     for (o, n), k in zip(ranges, kinds):
         heads.append(len(rows))
         rows.append((k, int(o), int(n)))
-        if k != KIND_MD5:
-            rows.append((KIND_DIGEST_MORE, 0, 0))
+        rows += [(KIND_DIGEST_MORE, 0, 0)] * ((DIGEST_BYTES[k] + 15) // 16 - 1)
     u = np.zeros(len(rows), dtype=UNIT_DTYPE)
     u["kind"] = [r[0] for r in rows]
     u["out_off"] = [r[1] for r in rows]
@@ -280,14 +283,16 @@ def digest_units(ranges, kinds):
 
 def result_wide_digests(res, units):
     """tail-aware unpacking: the digests of the heads among `units` out of their results `res` (same length) -> list of bytes in
-    table order: sixteen bytes of a head's result, and for a wide head the first 4 / 16 of the sixteen of the next unit's"""
+    table order: sixteen bytes of a head's result, and for a wide head what is left of the digest out of the sixteen of each of the next
+    units' (SHA-1 / SHA-256: one, SHA-384: two, SHA-512: three)"""
     raw = np.ascontiguousarray(res).view(np.uint8).reshape(len(res), RESULT_DTYPE.itemsize)
     out = []
     for i, k in enumerate(int(x) for x in units["kind"]):
         if k in DIGEST_BYTES:
             d = raw[i, 8:24].tobytes()
-            if k != KIND_MD5 and i + 1 < len(res):          # (a head without a tail is an error its result says)
-                d += raw[i + 1, 8:8 + DIGEST_BYTES[k] - 16].tobytes()
+            for t in range(1, (DIGEST_BYTES[k] + 15) // 16):
+                if i + t < len(res):                        # (a head without a tail is an error its result says)
+                    d += raw[i + t, 8:8 + min(16, DIGEST_BYTES[k] - 16 * t)].tobytes()
             out.append(d)
     return out
 

@@ -106,9 +106,11 @@ MschmDecompressor._fields_ = [
 MSCABD_PARAM_SEARCHBUF, MSCABD_PARAM_FIXMSZIP, MSCABD_PARAM_DECOMPBUF, MSCABD_PARAM_SALVAGE = 0, 1, 2, 3
 MSCABD_PARAM_HIP_DEVICES, MSCABD_PARAM_HIP_CACHE_MB, MSCABD_PARAM_HIP_MD5, MSCABD_PARAM_HIP_DIGESTS = 100, 101, 102, 103
 MSCHMD_PARAM_HIP_DIGESTS = 103
+MSCABD_PARAM_HIP_DIGESTS64 = MSCHMD_PARAM_HIP_DIGESTS64 = 106      # a mask of MSPACK_DIGEST_SHA384 | MSPACK_DIGEST_SHA512
 MSCABD_PARAM_HIP_CRC32, MSCHMD_PARAM_HIP_CRC32 = 105, 105     # 1: the batches carry one CRC-32 range unit per file (104 is no param)
 MSPACK_DIGEST_MD5, MSPACK_DIGEST_SHA1, MSPACK_DIGEST_SHA256 = 1, 2, 4
-DIGEST_BYTES = {MSPACK_DIGEST_MD5: 16, MSPACK_DIGEST_SHA1: 20, MSPACK_DIGEST_SHA256: 32}
+MSPACK_DIGEST_SHA384, MSPACK_DIGEST_SHA512 = 16, 32                  # (8 is no algorithm)
+DIGEST_BYTES = {MSPACK_DIGEST_MD5: 16, MSPACK_DIGEST_SHA1: 20, MSPACK_DIGEST_SHA256: 32, MSPACK_DIGEST_SHA384: 48, MSPACK_DIGEST_SHA512: 64}
 MSPACK_ERR_OK, MSPACK_ERR_ARGS = 0, 1
 
 
@@ -384,7 +386,7 @@ class Cab:
 
     def digest(self, i, alg, cap=None):
         """mspack_cabd_digest (mspack.h): extract(i) with the writes replaced by a hash of algorithm alg (MSPACK_DIGEST_*) -> (err, the
-        16 / 20 / 32 digest bytes; zeros unless err == 0).  set_param(MSCABD_PARAM_HIP_DIGESTS, mask) before the first call lets the
+        16 / 20 / 32 / 48 / 64 digest bytes; zeros unless err == 0).  set_param(MSCABD_PARAM_HIP_DIGESTS, mask) before the first call lets the
         batch take the digests on the device.  cap: the digest_cap handed over instead of the algorithm's length"""
         return _digest(self.L, self.d, self._files[i], alg, cap)
 
@@ -614,7 +616,7 @@ class Chm:
 
     def digest(self, i, alg, cap=None):
         """mspack_chmd_digest (mspack.h): extract(i) with the writes replaced by a hash of algorithm alg (MSPACK_DIGEST_*) -> (err, the
-        16 / 20 / 32 digest bytes; zeros unless err == 0).  set_param(MSCHMD_PARAM_HIP_DIGESTS, mask) before the first call lets the
+        16 / 20 / 32 / 48 / 64 digest bytes; zeros unless err == 0).  set_param(MSCHMD_PARAM_HIP_DIGESTS, mask) before the first call lets the
         chunks' batches take the digests on the device.  cap: the digest_cap handed over instead of the algorithm's length"""
         return _digest(self.L, self.d, self._files[i], alg, cap, fn=self.L.mspack_chmd_digest)
 

@@ -119,6 +119,24 @@ def run_cabs_digest(images, prefetch, hip_digests, alg, max_files=65536, L=None)
     return rc, [dg[32 * i:32 * i + nd].tobytes() for i in range(n)], {k: getattr(st, k) for k, _t in Stats._fields_}
 
 
+def run_cabs_digest64(images, prefetch, hip_digests64, alg, max_files=65536, L=None):
+    """run_cabs_digest for MSPACK_DIGEST_SHA384 (16) / _SHA512 (32) (mspk_api_bench_cabs_digest64), MSCABD_PARAM_HIP_DIGESTS64 =
+    hip_digests64.  -> (rc, [digest bytes per file], stats dict)"""
+    L = L or lib()
+    L.mspk_api_bench_cabs_digest64.restype = C.c_int
+    L.mspk_api_bench_cabs_digest64.argtypes = [C.c_void_p, C.c_void_p, C.c_uint, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_uint, C.POINTER(Stats)]
+    nd = {16: 48, 32: 64}[alg]
+    offs = np.zeros(len(images) + 1, dtype=np.uint64)
+    offs[1:] = np.cumsum([len(i) for i in images])
+    blob = np.frombuffer(b"".join(bytes(i) for i in images), dtype=np.uint8)
+    dg = np.zeros(64 * max_files, dtype=np.uint8)
+    st = Stats()
+    rc = L.mspk_api_bench_cabs_digest64(blob.ctypes.data, offs.ctypes.data, len(images), int(bool(prefetch)), int(hip_digests64), int(alg),
+                                        dg.ctypes.data, max_files, C.byref(st))
+    n = min(st.n_files, max_files)
+    return rc, [dg[64 * i:64 * i + nd].tobytes() for i in range(n)], {k: getattr(st, k) for k, _t in Stats._fields_}
+
+
 def run_chm_digest(image, hip_digests, alg, max_files=65536, L=None):
     """mspack_chmd_digest(alg) of every file of one CHM image in list order (mspk_api_bench_chm_digest), MSCHMD_PARAM_HIP_DIGESTS =
     hip_digests.  -> (rc, [digest bytes per file], stats dict)"""

@@ -247,6 +247,13 @@ int mspk_api_bench_cabs_digest(const unsigned char *images, const unsigned long 
 {
   return cabs_digest_run(images, offs, n_cabs, prefetch, MSCABD_PARAM_HIP_DIGESTS, hip_digests, alg, 32, digests, max_files, st);
 }
+/* ... and with MSPACK_DIGEST_SHA384 / _SHA512 (tools/sha512_digest_bench.py): hip_digests64 = the value of MSCABD_PARAM_HIP_DIGESTS64;
+ * digests receives 64 bytes per file (the algorithm's 48 or 64, then zeros) */
+int mspk_api_bench_cabs_digest64(const unsigned char *images, const unsigned long long *offs, unsigned int n_cabs, int prefetch, int hip_digests64,
+                                 int alg, unsigned char *digests, unsigned int max_files, mspk_api_stats *st)
+{
+  return cabs_digest_run(images, offs, n_cabs, prefetch, MSCABD_PARAM_HIP_DIGESTS64, hip_digests64, alg, 64, digests, max_files, st);
+}
 static int cabs_digest_run(const unsigned char *images, const unsigned long long *offs, unsigned int n_cabs, int prefetch, int param, int value,
                            int alg, unsigned int stride, unsigned char *digests, unsigned int max_files, mspk_api_stats *st)
 {
@@ -282,7 +289,7 @@ static int cabs_digest_run(const unsigned char *images, const unsigned long long
   for (k = 0; k < n_cabs && !rc; k++) {
     struct mscabd_file *f;
     for (f = cabs[k]->files; f; f = f->next) {
-      unsigned char dg[32];
+      unsigned char dg[64];
       const double e0 = now_s();
       const int err = (memset(dg, 0, sizeof(dg)), mspack_cabd_digest(d, f, alg, dg, sizeof(dg)));
       if (st->n_files == 0 && !prefetch) st->first_extract_s = now_s() - e0;

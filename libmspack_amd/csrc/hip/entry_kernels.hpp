@@ -629,6 +629,23 @@ void mspack_sha256(const mspack_hip_unit *units, const u32 *order, u32 n_list, u
   sha_entry<MSPACK_HIP_KIND_SHA256>(units, order, n_list, n_table, out_arena, out_bytes, results);
 }
 
+// MSPACK_HIP_KIND_SHA384 / _SHA512 (sha512_kernel.hpp): one head per LANE, ONE kernel for both -- they share the compression function;
+// a lane picks its initial state by its unit's kind --, launched like mspack_sha256.  `kinds`: bit MSPACK_HIP_KIND_SHA384 / _SHA512
+// set = heads of that algorithm are taken (the device-resident entry's kind_mask; the host entry points set both)
+__global__ __launch_bounds__(64)
+void mspack_sha512(const mspack_hip_unit *units, const u32 *order, u32 n_list, u32 n_table, const u8 *out_arena, u64 out_bytes, mspack_hip_result *results,
+                   u32 kinds)
+{
+  const u32 j = blockIdx.x * 64u + threadIdx.x;
+  if (j >= n_list) return;
+  const u32 ui = order ? order[j] : j;
+  if (ui >= n_table) return;
+  const mspack_hip_unit u = units[ui];
+  if (u.kind == MSPACK_HIP_KIND_DIGEST_MORE) { sha_tail_unit(units, ui, results); return; }
+  if ((u.kind != MSPACK_HIP_KIND_SHA384 && u.kind != MSPACK_HIP_KIND_SHA512) || !((kinds >> u.kind) & 1u)) return;
+  sha512_unit(units, ui, n_table, u, out_arena, out_bytes, results);
+}
+
 // MSPACK_HIP_KIND_CRC32 (crc32_range_kernel.hpp): the CRC-32 of byte ranges of any length, launched behind everything that stores into
 // the output arena -- stream order is the only ordering, between these four launches too.  order[0 .. n) names the list's units (NULL:
 // the whole table); units of other kinds own nothing here.  init and finish: one position per lane; scan: one wave; the pass: a

@@ -408,6 +408,7 @@ static int issue_chunks(PipeCall &pc, CopyBack &cb)
       TRY(launch_md5(pc.d_units, pc.d_order + plan.md5_off, plan.n_md5, d_out, pc.out_span, pc.d_res, st));
       TRY(launch_sha1(pc.d_units, pc.d_order + plan.sha1_off, plan.n_sha1, n_sel, d_out, pc.out_span, pc.d_res, st));
       TRY(launch_sha256(pc.d_units, pc.d_order + plan.sha256_off, plan.n_sha256, n_sel, d_out, pc.out_span, pc.d_res, st));
+      TRY(launch_sha512(pc.d_units, pc.d_order + plan.sha512_off, plan.n_sha512, n_sel, d_out, pc.out_span, pc.d_res, SHA512_KINDS, st));
       TRY(launch_crc32_ranges(pc.d_units, pc.d_order + plan.crc32r_off, plan.n_crc32r, d_out, pc.out_span, pc.d_res, st));
       TRY(hipMemcpyAsync(pc.h_res + m0, pc.d_res + m0, plan.n_dig * sizeof(mspack_hip_result), hipMemcpyDeviceToHost, st));
     }

@@ -52,8 +52,12 @@ static inline bool unit_side_table(const mspack_hip_unit &u, uint64_t &lo, uint6
   }
   return false;
 }
-// digest units: the heads (MD5 and CRC-32 ranges; SHA-1 and SHA-256, whose results go on in the next unit's) and the tails of the wide ones
-static inline bool unit_is_wide_head(const mspack_hip_unit &u) { return u.kind == MSPACK_HIP_KIND_SHA1 || u.kind == MSPACK_HIP_KIND_SHA256; }
+// digest units: the heads (MD5 and CRC-32 ranges; SHA-1, SHA-256, SHA-384 and SHA-512, whose results go on in the next units') and the
+// tails of the wide ones
+static inline bool unit_is_sha512(const mspack_hip_unit &u) { return u.kind == MSPACK_HIP_KIND_SHA384 || u.kind == MSPACK_HIP_KIND_SHA512; }
+static inline bool unit_is_wide_head(const mspack_hip_unit &u) { return u.kind == MSPACK_HIP_KIND_SHA1 || u.kind == MSPACK_HIP_KIND_SHA256 || unit_is_sha512(u); }
+// the tails a head needs behind it: ceil(digest bytes / 16) - 1 (mspack_hip.h)
+static inline size_t unit_wide_tails(const mspack_hip_unit &u) { return u.kind == MSPACK_HIP_KIND_SHA384 ? 2u : u.kind == MSPACK_HIP_KIND_SHA512 ? 3u : unit_is_wide_head(u) ? 1u : 0u; }
 static inline bool unit_is_digest_head(const mspack_hip_unit &u) { return u.kind == MSPACK_HIP_KIND_MD5 || u.kind == MSPACK_HIP_KIND_CRC32 || unit_is_wide_head(u); }
 static inline bool unit_is_digest(const mspack_hip_unit &u) { return unit_is_digest_head(u) || u.kind == MSPACK_HIP_KIND_DIGEST_MORE; }
 static inline size_t unit_frames(const mspack_hip_unit &u) {
@@ -69,12 +73,13 @@ struct PlanKnobs {
 };
 // what plan_batch computes.  local[i] is unit idx[i] of the caller's table, offsets relative to in_lo / out_lo; the chunks are
 // ranges of local[]; order holds every chunk's per-kind lists and its CRC list (indices into local[]).
-// Digest units (MSPACK_HIP_KIND_MD5, _SHA1, _SHA256 and the wide ones' _DIGEST_MORE tails) read no input and own no output: they
-// stand BEHIND the chunks in local[] -- indices [n - n_dig, n), in the caller's order, so a head keeps its tail at i + 1; no chunk
-// holds them, no per-kind list, no weight in the cutting -- and order holds three consecutive lists of HEADS, one per algorithm
-// (MD5 at md5_off, SHA-1 at sha1_off, SHA-256 at sha256_off), each longest range first (one lane each: lanes of similar length next
-// to each other) for that algorithm's one pass behind the last chunk; behind them the list of the CRC-32 range units (crc32r_off), in
-// the caller's order: their pass takes segments, not units, so the order carries no weight
+// Digest units (MSPACK_HIP_KIND_MD5, _SHA1, _SHA256, _SHA384, _SHA512 and the wide ones' _DIGEST_MORE tails) read no input and own no
+// output: they stand BEHIND the chunks in local[] -- indices [n - n_dig, n), in the caller's order, so a head keeps its tails at
+// i + 1 ..; no chunk holds them, no per-kind list, no weight in the cutting -- and order holds four consecutive lists of HEADS, one per
+// kernel (MD5 at md5_off, SHA-1 at sha1_off, SHA-256 at sha256_off, SHA-384 and SHA-512 together at sha512_off: they share a kernel),
+// each longest range first (one lane each: lanes of similar length next to each other) for that kernel's one pass behind the last
+// chunk; behind them the list of the CRC-32 range units (crc32r_off), in the caller's order: their pass takes segments, not units,
+// so the order carries no weight
 struct BatchPlan {
   std::vector<uint32_t> idx;
   std::vector<mspack_hip_unit> local;
@@ -84,6 +89,7 @@ struct BatchPlan {
   size_t n_frames, n_rec_slots, n_crc;              // n_crc: units that want a digest (MSPACK_HIP_UF_CRC32)
   size_t n_md5 = 0, md5_off = 0;                    // the MD5 units: how many, their list's place in order
   size_t n_sha1 = 0, sha1_off = 0, n_sha256 = 0, sha256_off = 0;      // the SHA-1 / SHA-256 heads likewise
+  size_t n_sha512 = 0, sha512_off = 0;              // the SHA-384 and SHA-512 heads, one list
   size_t n_crc32r = 0, crc32r_off = 0;              // the CRC-32 range units (MSPACK_HIP_KIND_CRC32) likewise
   size_t n_dig = 0;                                 // every digest unit, tails included: local[n - n_dig .. n)
   bool monotone, has_qtm;
@@ -103,7 +109,7 @@ static int plan_units(mspack_hip_unit *units, const uint32_t *sel, size_t n_sel,
     const auto mid = std::stable_partition(idx.begin(), idx.end(), [&](uint32_t x) { return !unit_is_digest(units[x]); });
     std::sort(mid, idx.end());
     p.n_dig = (size_t)(idx.end() - mid);
-    p.n_md5 = p.n_sha1 = p.n_sha256 = p.n_crc32r = 0;
+    p.n_md5 = p.n_sha1 = p.n_sha256 = p.n_sha512 = p.n_crc32r = 0;
   }
   local.resize(n_sel);
   bool monotone = !per_unit_back;
@@ -122,9 +128,11 @@ static int plan_units(mspack_hip_unit *units, const uint32_t *sel, size_t n_sel,
       in_lo = std::min<uint64_t>(in_lo, u.in_off); in_hi = std::max<uint64_t>(in_hi, u.in_off + u.in_len);
       continue;
     }
-    if (u.kind == MSPACK_HIP_KIND_DIGEST_MORE) {           // a wide digest's tail: names nothing, stands right behind its head
+    if (u.kind == MSPACK_HIP_KIND_DIGEST_MORE) {           // a wide digest's tail: names nothing, stands behind its head, among the tails it needs
       // (the digest units are in table order here: neighbours in the table are neighbours in this list)
-      if (i == n_sel - p.n_dig || idx[i - 1] + 1u != idx[i] || !unit_is_wide_head(local[i - 1])) {
+      size_t k = 1;                                        // the first unit in front of it that is no tail, as far back as a head reaches
+      while (k < 3 && i >= n_sel - p.n_dig + k + 1 && idx[i - k] + 1u == idx[i - k + 1] && local[i - k].kind == MSPACK_HIP_KIND_DIGEST_MORE) k++;
+      if (i < n_sel - p.n_dig + k || idx[i - k] + 1u != idx[i - k + 1] || unit_wide_tails(local[i - k]) < k) {
         snprintf(errbuf, errcap, "unit %u: an MSPACK_HIP_KIND_DIGEST_MORE unit without a SHA-1 / SHA-256 unit in front of it", idx[i]); return -1;
       }
       if (u.in_len || u.out_len) { snprintf(errbuf, errcap, "unit %u: an MSPACK_HIP_KIND_DIGEST_MORE unit names no bytes (in_len and out_len must be 0)", idx[i]); return -1; }
@@ -135,13 +143,20 @@ static int plan_units(mspack_hip_unit *units, const uint32_t *sel, size_t n_sel,
       if (u.flags & MSPACK_HIP_UF_CRC32) { snprintf(errbuf, errcap, "unit %u: a digest unit decodes nothing to take a CRC-32 of", idx[i]); return -1; }
       if (u.in_len) { snprintf(errbuf, errcap, "unit %u: a digest unit reads no input (in_len must be 0)", idx[i]); return -1; }
       if (u.out_off > out_bytes || u.out_len > out_bytes - u.out_off) { snprintf(errbuf, errcap, "unit %u: a digest unit's range leaves the output arena", idx[i]); return -1; }
-      if (unit_is_wide_head(u)) {                          // its result goes on in the next unit's
+      if (unit_is_wide_head(u)) {                          // its result goes on in the next unit's (SHA-384: next two units', SHA-512: three)
         if (!sel && (size_t) idx[i] + 1u >= n_sel) { snprintf(errbuf, errcap, "unit %u: a wide digest unit is the table's last unit (its MSPACK_HIP_KIND_DIGEST_MORE unit is missing)", idx[i]); return -1; }
         if (i + 1 >= n_sel || idx[i + 1] != idx[i] + 1u || units[idx[i + 1]].kind != MSPACK_HIP_KIND_DIGEST_MORE) {
           snprintf(errbuf, errcap, "unit %u: a wide digest unit must be followed by an MSPACK_HIP_KIND_DIGEST_MORE unit", idx[i]); return -1;
         }
+        for (size_t k = 2; k <= unit_wide_tails(u); k++)
+          if (i + k >= n_sel || idx[i + k] != idx[i] + k || units[idx[i + k]].kind != MSPACK_HIP_KIND_DIGEST_MORE) {
+            snprintf(errbuf, errcap, "unit %u: a %s unit must be followed by %u MSPACK_HIP_KIND_DIGEST_MORE units", idx[i],
+                     u.kind == MSPACK_HIP_KIND_SHA384 ? "SHA-384" : "SHA-512", (unsigned) unit_wide_tails(u));
+            return -1;
+          }
       }
-      (u.kind == MSPACK_HIP_KIND_MD5 ? p.n_md5 : u.kind == MSPACK_HIP_KIND_SHA1 ? p.n_sha1 : u.kind == MSPACK_HIP_KIND_SHA256 ? p.n_sha256 : p.n_crc32r)++;
+      (u.kind == MSPACK_HIP_KIND_MD5 ? p.n_md5 : u.kind == MSPACK_HIP_KIND_SHA1 ? p.n_sha1 : u.kind == MSPACK_HIP_KIND_SHA256 ? p.n_sha256 :
+       unit_is_sha512(u) ? p.n_sha512 : p.n_crc32r)++;
       u.in_off = 0; u.flags = 0;
       if (u.out_len) { out_lo = std::min<uint64_t>(out_lo, u.out_off); out_hi = std::max<uint64_t>(out_hi, u.out_off + u.out_len); }
       continue;
@@ -310,6 +325,12 @@ static void plan_lists(BatchPlan &p)
     for (size_t i = n_sel - p.n_dig; i < n_sel; i++) if (local[i].kind == dig_kind[a]) order[op++] = (uint32_t) i;
     std::stable_sort(order.begin() + *dig_off[a], order.begin() + op, [&](uint32_t x, uint32_t y) { return local[x].out_len > local[y].out_len; });
   }
+  // ... SHA-384 and SHA-512 heads in one list (one kernel takes both), longest first over both
+  p.sha512_off = op;
+  if (p.n_sha512) {
+    for (size_t i = n_sel - p.n_dig; i < n_sel; i++) if (unit_is_sha512(local[i])) order[op++] = (uint32_t) i;
+    std::stable_sort(order.begin() + p.sha512_off, order.begin() + op, [&](uint32_t x, uint32_t y) { return local[x].out_len > local[y].out_len; });
+  }
   // ... and the CRC-32 range units' list behind them
   p.crc32r_off = op;
   if (p.n_crc32r)
@@ -400,9 +421,11 @@ static bool plan_shards(const mspack_hip_unit *units, size_t n_units, int n_shar
       if (s + 1 < n_shards && acc * n_shards >= total * (uint64_t)(s + 1) && !barred[i]) s++;
     }
   }
-  // (a wide digest's tail goes where its head went: md5s is in table order, so the head is the entry before it)
+  // (a wide digest's tails go where their head went: md5s is in table order, so the head is the first entry before them that is no tail)
   for (size_t m = 0, at = 0; m < md5s.size(); m++) {
-    const bool tail = units[md5s[m]].kind == MSPACK_HIP_KIND_DIGEST_MORE && m && md5s[m - 1] + 1u == md5s[m] && unit_is_wide_head(units[md5s[m - 1]]);
+    size_t k = 1;
+    while (k < 3 && k < m && md5s[m - k] + 1u == md5s[m - k + 1] && units[md5s[m - k]].kind == MSPACK_HIP_KIND_DIGEST_MORE) k++;
+    const bool tail = units[md5s[m]].kind == MSPACK_HIP_KIND_DIGEST_MORE && m >= k && md5s[m - k] + 1u == md5s[m - k + 1] && unit_wide_tails(units[md5s[m - k]]) >= k;
     if (!tail) at = md5_first[m] == (size_t) -1 ? 0 : (size_t) shard_of[md5_first[m]];
     shard[at].push_back(md5s[m]);
   }

@@ -1,6 +1,6 @@
 // launch.hpp -- the launch layer and the device-resident C ABI: the thread's error text, launch<> (a kernel launch whose status is
 // returned), the launch-level environment knobs, launch_kind (one codec's launches over a compact unit list), launch_crc32, launch_md5, launch_sha1 /
-// launch_sha256, launch_crc32_ranges, the
+// launch_sha256, launch_sha512, launch_crc32_ranges, the
 // analysis builds' debug exports, version / features / device functions, mspack_hip_decode_batch_device and _time_batch_device.
 #pragma once
 #include <mutex>
@@ -235,6 +235,19 @@ static hipError_t launch_sha256(const mspack_hip_unit *d_units, const uint32_t *
   LK(launch(mspack_sha256, dim3((unsigned)((n + 63) / 64)), dim3(64), st, d_units, d_order, (u32) n, (u32) n_table, (const u8 *) d_out, (u64) out_bytes, d_results));
   return hipSuccess;
 }
+#define SHA512_KINDS ((1u << MSPACK_HIP_KIND_SHA384) | (1u << MSPACK_HIP_KIND_SHA512))
+// the SHA-384 / SHA-512 pass: one launch for the heads of both algorithms (`kinds`: which of the two are taken)
+static hipError_t launch_sha512(const mspack_hip_unit *d_units, const uint32_t *d_order, size_t n, size_t n_table, const void *d_out, size_t out_bytes,
+                                mspack_hip_result *d_results, unsigned kinds, hipStream_t st)
+{
+  if (n == 0) return hipSuccess;
+#ifdef MSPACK_HOST_CHECK
+  return hipErrorInvalidValue;
+#endif
+  LK(launch(mspack_sha512, dim3((unsigned)((n + 63) / 64)), dim3(64), st, d_units, d_order, (u32) n, (u32) n_table, (const u8 *) d_out, (u64) out_bytes, d_results,
+            (u32) kinds));
+  return hipSuccess;
+}
 // waves of mspack_crc32r_pass: as many as the device holds at once, eight per CU at most (nothing depends on the number being right)
 static unsigned crc32r_waves()
 {
@@ -336,7 +349,8 @@ int mspack_hip_debug_frame_words(const void *d_frame_scratch, size_t n_frames_to
 }
 const char *mspack_hip_version(void) { return "mspack-hip 0.4 (gfx950; LZX/LZX-DELTA/Quantum/MSZIP batch decode)"; }
 const char *mspack_hip_last_error(void) { return g_err; }
-unsigned mspack_hip_features(void) { return MSPACK_HIP_FEAT_CRC32 | MSPACK_HIP_FEAT_MD5 | MSPACK_HIP_FEAT_SHA1 | MSPACK_HIP_FEAT_SHA256 | MSPACK_HIP_FEAT_SLOTS | MSPACK_HIP_FEAT_LZSS_RING | MSPACK_HIP_FEAT_CRC32_RANGES; }
+unsigned mspack_hip_features(void) { return MSPACK_HIP_FEAT_CRC32 | MSPACK_HIP_FEAT_MD5 | MSPACK_HIP_FEAT_SHA1 | MSPACK_HIP_FEAT_SHA256 | MSPACK_HIP_FEAT_SLOTS | MSPACK_HIP_FEAT_LZSS_RING | MSPACK_HIP_FEAT_CRC32_RANGES |
+         MSPACK_HIP_FEAT_SHA384 | MSPACK_HIP_FEAT_SHA512; }
 
 int mspack_hip_device_count(void) {
   int n = 0;
@@ -356,7 +370,7 @@ int mspack_hip_decode_batch_device(const mspack_hip_unit *d_units, const uint32_
 {
   (void) in_bytes;
   if (n_units == 0) return 0;
-  if ((kind_mask & 0x1301FEu) == 0) kind_mask |= 0xFEu;  // bit k = units of kind k may be present; none = every codec (and no digest units)
+  if ((kind_mask & 0x31301FEu) == 0) kind_mask |= 0xFEu;  // bit k = units of kind k may be present; none = every codec (and no digest units)
   // the caller's unit table lives on the device, so the kinds cannot be compacted here: every codec in the
   // mask gets the whole grid and blocks of other kinds leave at once.  Callers with mixed batches pass one
   // order list per codec and a one-bit mask (what the host-buffer entry points below do).
@@ -376,6 +390,9 @@ int mspack_hip_decode_batch_device(const mspack_hip_unit *d_units, const uint32_
     CK(launch_sha1(d_units, d_order, n_units, n_units, d_out, out_bytes, d_results, (hipStream_t) stream));
   if (kind_mask & (1u << MSPACK_HIP_KIND_SHA256))
     CK(launch_sha256(d_units, d_order, n_units, n_units, d_out, out_bytes, d_results, (hipStream_t) stream));
+  // ... and the SHA-384 / SHA-512 pass, one launch for both
+  if (kind_mask & SHA512_KINDS)
+    CK(launch_sha512(d_units, d_order, n_units, n_units, d_out, out_bytes, d_results, kind_mask & SHA512_KINDS, (hipStream_t) stream));
   // ... and the CRC-32 range units' pass (four launches)
   if (kind_mask & (1u << MSPACK_HIP_KIND_CRC32))
     CK(launch_crc32_ranges(d_units, d_order, n_units, d_out, out_bytes, d_results, (hipStream_t) stream));

@@ -150,12 +150,20 @@ template <> struct ShaAlg<MSPACK_HIP_KIND_SHA256> {
 };
 
 __device__ __forceinline__ bool sha_is_head(u32 kind) { return kind == MSPACK_HIP_KIND_SHA1 || kind == MSPACK_HIP_KIND_SHA256; }
+// the tails a head of this kind needs (mspack_hip.h: ceil(digest bytes / 16) - 1); 0: no wide head
+__device__ __forceinline__ u32 sha_tails_of(u32 kind)
+{
+  return sha_is_head(kind) ? 1u : kind == MSPACK_HIP_KIND_SHA384 ? 2u : kind == MSPACK_HIP_KIND_SHA512 ? 3u : 0u;
+}
 
 // a lane that met an MSPACK_HIP_KIND_DIGEST_MORE unit (the device-resident entry only: the host entry points list heads alone): a
-// tail without a head in front of it answers MSPACK_ERR_ARGS; one behind a head is its head's lane's to write
+// tail is its head's lane's to write when the first unit in front of it that is no tail is a head that needs as many tails as
+// stand between them (itself included); every other tail -- no head, or more tails than the head needs -- answers MSPACK_ERR_ARGS
 __device__ __forceinline__ void sha_tail_unit(const mspack_hip_unit *units, const u32 ui, mspack_hip_result *results)
 {
-  if (ui != 0u && sha_is_head(units[ui - 1u].kind)) return;
+  u32 k = 1u;
+  while (k < 3u && k < ui && units[ui - k].kind == MSPACK_HIP_KIND_DIGEST_MORE) k++;
+  if (k <= ui && sha_tails_of(units[ui - k].kind) >= k) return;
   mspack_hip_result r;
   r.err = ERR_ARGS; r.flags = 0u; r.out_len = 0u; r.in_used = 0u; r.good_len = 0u; r.in_next = 0u;
   gst(&results[ui], r);

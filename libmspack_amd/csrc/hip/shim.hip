@@ -53,10 +53,11 @@ static_assert(sizeof(lzxp::LzxFrameRec) == sizeof(lzxn::LzxFrameRec), "one recor
 #include "crc32_range_kernel.hpp"
 #include "md5_kernel.hpp"
 #include "sha_kernel.hpp"
+#include "sha512_kernel.hpp"
 
 // ---- everything behind the decoders: one role header each, in this order ----
 // entry_kernels.hpp  pick_unit, the work scratch's layout (lzx_scratch), the map kernels, every __global__ entry point
-// launch.hpp         g_err / fail / CK, launch<>, the launch-level knobs, launch_kind, launch_crc32, launch_md5, launch_sha1 / _sha256; the device-resident C ABI
+// launch.hpp         g_err / fail / CK, launch<>, the launch-level knobs, launch_kind, launch_crc32, launch_md5, launch_sha1 / _sha256 / _sha512; the device-resident C ABI
 // host_plan.hpp      the host path's chunk planner: plan_batch, a pure function of the unit table (no HIP; tests include it alone)
 // host_pins.hpp      page-locked host ranges: the registry, the cut copies, a call's own locks (Pins), mspack_hip_pin / _unpin
 // host_stage.hpp     the library's own page-locked staging pool (mspack_hip_stage_alloc / _free)

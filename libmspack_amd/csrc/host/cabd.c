@@ -86,7 +86,7 @@ struct folder_p {
    * again; folder_settle() waits for the unit and takes its result over */
   struct cab_batch *job;
   size_t job_k;
-  /* MSCABD_PARAM_HIP_DIGESTS: the digests the folder's batch took of its files (mspack_hip.h: MSPACK_HIP_KIND_MD5 / _SHA1 / _SHA256),
+  /* MSCABD_PARAM_HIP_DIGESTS / _DIGESTS64: the digests the folder's batch took of its files (mspack_hip.h: MSPACK_HIP_KIND_MD5 / _SHA1 / _SHA256 / _SHA384 / _SHA512),
    * by offset in the folder (host_digest.h: struct digest_table) */
   struct digest_table dg;
 };
@@ -123,6 +123,7 @@ struct cabd_p {
   int searchbuf_size, fix_mszip, buf_size, salvage;
   int hip_crc32;                      /* MSCABD_PARAM_HIP_CRC32: 1 = the batches carry one MSPACK_HIP_KIND_CRC32 unit per file, for mspack_cabd_crc32() */
   int devices, cache_mb, hip_digests; /* hip_digests: MSCABD_PARAM_HIP_DIGESTS, a mask of MSPACK_DIGEST_* (MSCABD_PARAM_HIP_MD5 is its bit 1) */
+  int hip_digests64;                  /* MSCABD_PARAM_HIP_DIGESTS64: a mask of MSPACK_DIGEST_SHA384 | MSPACK_DIGEST_SHA512 */
   struct digest_sink *sink;           /* mspack_cabd_digest is running: what extract() would write goes here instead of a file */
   const unsigned char *sink_kept;     /* ... or the call's bytes were exactly a file whose digest the batch has taken: that one */
   unsigned int list_stamp;            /* mspack_cabd_prefetch: one number per call, to tell a folder list that is named twice */
@@ -787,7 +788,7 @@ struct gathered {
  * shared with the CHM driver; this driver's own: the walk over the gathered folders' files with one byte sum over the whole batch */
 /* diagnostics (mspack.h: mspack_cabd_md5_counts, mspack_cabd_digest_counts): per algorithm, successful digest() calls answered from a
  * digest the batch took on the device / hashed on the host, over all decompressors of the process */
-static unsigned long long g_digest_counts[3][2];
+static unsigned long long g_digest_counts[DIGEST_ALGS][2];
 static unsigned long long g_crc32_counts[2];            /* the same for mspack_cabd_crc32() */
 
 /* The request boundaries a Quantum folder's files imply -- cabd_extract asks its codec for the bytes in front of a file, then for
@@ -1039,7 +1040,7 @@ static int decode_cabinets(struct cabd_p *self, struct cab_p **cabs, size_t n_ca
   size_t kept = used;                                   /* what the folders this call decodes have taken of the budget */
   int err = MSPACK_ERR_OK, rc, again = 0;
   /* the algorithms the batch carries units for: asked for, the provider can (one without mspack_hip_features cannot), a ratio above 0 */
-  const int dev_algs = digest_device_algs(self->hip_digests | (self->hip_crc32 ? DIGEST_ALG_CRC32 : 0));
+  const int dev_algs = digest_device_algs(self->hip_digests | self->hip_digests64 | (self->hip_crc32 ? DIGEST_ALG_CRC32 : 0));
   size_t dg_cap = 0, ndg = 0;                           /* digest units: at most digest_units_per_file per file of the gathered folders; those made */
   size_t n_qtm_files = 0;                               /* files in Quantum folders: two marks each at most (gather_marks) */
   for (c = 0; c < n_cabs; c++) {
@@ -1130,7 +1131,7 @@ static int decode_cabinets(struct cabd_p *self, struct cab_p **cabs, size_t n_ca
     /* the digest units (host_digest.h: digest_emit_file) of every file that lies inside what its folder's blocks hold, beside the
      * marks gather_marks collected; the long ones are left to the host (digest_ratio, per algorithm, of the whole batch's bytes) --
      * for the hashes only: with DIGEST_ALG_CRC32 in dev_algs every such file gets its CRC-32 unit, whatever its length */
-    double sum = 0.0, ratio[3];
+    double sum = 0.0, ratio[DIGEST_ALGS];
     int pass;
     digest_ratios(ratio);
     for (pass = 0; pass < 2; pass++)
@@ -1553,6 +1554,7 @@ static int cabd_param(struct mscab_decompressor *base, int param, int value)
   case MSCABD_PARAM_HIP_MD5:      if (value != 0 && value != 1) return MSPACK_ERR_ARGS; self->hip_digests = (self->hip_digests & ~MSPACK_DIGEST_MD5) | (value ? MSPACK_DIGEST_MD5 : 0); break;
   case MSCABD_PARAM_HIP_DIGESTS:  if (value < 0 || value > 7) return MSPACK_ERR_ARGS; self->hip_digests = value; break;
   case MSCABD_PARAM_HIP_CRC32:    if (value != 0 && value != 1) return MSPACK_ERR_ARGS; self->hip_crc32 = value; break;
+  case MSCABD_PARAM_HIP_DIGESTS64: if (value & ~(MSPACK_DIGEST_SHA384 | MSPACK_DIGEST_SHA512)) return MSPACK_ERR_ARGS; self->hip_digests64 = value; break;
   default: return MSPACK_ERR_ARGS;
   }
   return MSPACK_ERR_OK;
@@ -1573,6 +1575,7 @@ int mspack_cabd_get_param(struct mscab_decompressor *base, int param, int *value
   case MSCABD_PARAM_HIP_MD5:      *value = (self->hip_digests & MSPACK_DIGEST_MD5) ? 1 : 0; break;
   case MSCABD_PARAM_HIP_DIGESTS:  *value = self->hip_digests; break;
   case MSCABD_PARAM_HIP_CRC32:    *value = self->hip_crc32; break;
+  case MSCABD_PARAM_HIP_DIGESTS64: *value = self->hip_digests64; break;
   default: return MSPACK_ERR_ARGS;
   }
   return MSPACK_ERR_OK;
@@ -1633,7 +1636,7 @@ struct mscab_decompressor *mspack_create_cab_decompressor(struct mspack_system *
   self->system = sys;
   self->error = MSPACK_ERR_OK; self->read_error = MSPACK_ERR_OK;
   self->searchbuf_size = 32768; self->fix_mszip = 0; self->buf_size = 4096; self->salvage = 0;
-  self->devices = 1; self->cache_mb = 2048; self->list_stamp = 0; self->hip_digests = 0; self->hip_crc32 = 0; self->sink = NULL; self->sink_kept = NULL;
+  self->devices = 1; self->cache_mb = 2048; self->list_stamp = 0; self->hip_digests = 0; self->hip_digests64 = 0; self->hip_crc32 = 0; self->sink = NULL; self->sink_kept = NULL;
   memset(&self->st, 0, sizeof(self->st)); self->st_offset = 0; self->st_active = 0; self->last_folder = NULL;
   self->msg_folder = NULL; self->msg_offset = 0; self->msg_next = 0; self->msg_next_ck = 0;
   self->live_folder = NULL; self->live_offset = 0; self->live_failed = 0; self->live_err = MSPACK_ERR_OK;

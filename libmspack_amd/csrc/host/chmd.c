@@ -98,6 +98,7 @@ struct chmd_p {
   int error;
   struct chm_p *v_chm; struct vdec v;
   int hip_digests;                    /* MSCHMD_PARAM_HIP_DIGESTS: a mask of MSPACK_DIGEST_* */
+  int hip_digests64;                  /* MSCHMD_PARAM_HIP_DIGESTS64: a mask of MSPACK_DIGEST_SHA384 | MSPACK_DIGEST_SHA512 */
   int hip_crc32;                      /* MSCHMD_PARAM_HIP_CRC32: 1 = a chunk's batch carries one MSPACK_HIP_KIND_CRC32 unit per file, for mspack_chmd_crc32() */
   struct digest_sink *sink;           /* mspack_chmd_digest is running: what extract() would write goes here instead of a file */
   int sink_whole;                     /* ... and the emit step hands over exactly the file's plain range, of a call that is good so far */
@@ -106,10 +107,10 @@ struct chmd_p {
   unsigned int pf_stamp;              /* mspack_chmd_prefetch: one number per call */
 };
 /* per algorithm, successful mspack_chmd_digest() calls answered from a device digest / hashed on the host (mspack.h) */
-static unsigned long long g_digest_counts[3][2];
+static unsigned long long g_digest_counts[DIGEST_ALGS][2];
 static unsigned long long g_crc32_counts[2];            /* the same for mspack_chmd_crc32() */
 /* the algorithms asked for, CRC-32 (host_digest.h: DIGEST_ALG_CRC32) among them */
-#define CHM_ASKED_ALGS(self) ((self)->hip_digests | ((self)->hip_crc32 ? DIGEST_ALG_CRC32 : 0))
+#define CHM_ASKED_ALGS(self) ((self)->hip_digests | (self)->hip_digests64 | ((self)->hip_crc32 ? DIGEST_ALG_CRC32 : 0))
 /* batch calls this driver has issued, and the interval units in them (mspack.h: mspack_chmd_batch_counts) */
 static unsigned long long g_batch_counts[2];
 static void count_batch(size_t n_intervals)
@@ -583,7 +584,7 @@ static int chunk_digest_algs(const struct chmd_p *self, const struct chm_p *c, o
 }
 /* ... and those units (chm_digest_plan) for intervals [first, first+count), their ranges counted from out_base of the batch's output;
  * units == NULL: counts only */
-static size_t chunk_digest_units(const struct chm_p *c, unsigned int first, unsigned int count, int algs, const double ratio[3],
+static size_t chunk_digest_units(const struct chm_p *c, unsigned int first, unsigned int count, int algs, const double *ratio,
                                  uint64_t out_base, mspack_hip_unit *units, size_t cap)
 {
   const off_t lo = (off_t) first * c->interval_bytes;
@@ -745,7 +746,7 @@ static int issue_batch(struct chmd_p *self, struct chm_pick *pk, size_t n, uint6
   struct chm_batch *B = (struct chm_batch *) sys->alloc(sys, sizeof(*B));
   const void *in = pk[0].c->arena;
   size_t in_bytes = pk[0].c->arena_room, n_units = 0, n_dg = 0, out_total = 0, k, u = 0, d;
-  double ratio[3] = { 0.0, 0.0, 0.0 };
+  double ratio[DIGEST_ALGS] = { 0.0, 0.0, 0.0, 0.0, 0.0 };
   int as_job;
   if (!B) return MSPACK_ERR_NOMEMORY;
   memset(B, 0, sizeof(*B));
@@ -1477,6 +1478,7 @@ int mspack_chmd_set_param(struct mschm_decompressor *base, int param, int value)
   struct chmd_p *self = (struct chmd_p *) base;
   if (!self) return MSPACK_ERR_ARGS;
   if (param == MSCHMD_PARAM_HIP_CRC32) { if (value != 0 && value != 1) return MSPACK_ERR_ARGS; self->hip_crc32 = value; return MSPACK_ERR_OK; }
+  if (param == MSCHMD_PARAM_HIP_DIGESTS64) { if (value & ~(MSPACK_DIGEST_SHA384 | MSPACK_DIGEST_SHA512)) return MSPACK_ERR_ARGS; self->hip_digests64 = value; return MSPACK_ERR_OK; }
   if (param != MSCHMD_PARAM_HIP_DIGESTS || value < 0 || value > 7) return MSPACK_ERR_ARGS;
   self->hip_digests = value;
   return MSPACK_ERR_OK;
@@ -1485,8 +1487,8 @@ int mspack_chmd_set_param(struct mschm_decompressor *base, int param, int value)
 int mspack_chmd_get_param(struct mschm_decompressor *base, int param, int *value)
 {
   struct chmd_p *self = (struct chmd_p *) base;
-  if (!self || !value || (param != MSCHMD_PARAM_HIP_DIGESTS && param != MSCHMD_PARAM_HIP_CRC32)) return MSPACK_ERR_ARGS;
-  *value = param == MSCHMD_PARAM_HIP_CRC32 ? self->hip_crc32 : self->hip_digests;
+  if (!self || !value || (param != MSCHMD_PARAM_HIP_DIGESTS && param != MSCHMD_PARAM_HIP_CRC32 && param != MSCHMD_PARAM_HIP_DIGESTS64)) return MSPACK_ERR_ARGS;
+  *value = param == MSCHMD_PARAM_HIP_CRC32 ? self->hip_crc32 : param == MSCHMD_PARAM_HIP_DIGESTS64 ? self->hip_digests64 : self->hip_digests;
   return MSPACK_ERR_OK;
 }
 

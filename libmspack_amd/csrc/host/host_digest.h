@@ -13,6 +13,7 @@
 #include "mspack_hip.h"
 #include "md5.h"
 #include "sha.h"
+#include "sha512.h"
 #include "crc32.h"
 
 /* CRC-32 (zlib's) rides in the drivers' masks of algorithms as a bit of its own, INTERNAL to the drivers: no MSPACK_DIGEST_* value (8 is
@@ -21,39 +22,66 @@
  * little-endian, as the unit's result.out_len lies there */
 #define DIGEST_ALG_CRC32 8
 
-/* a digest call's hash in progress: one of the three */
-struct digest_sink { int alg; struct mspack_md5 md5; struct mspack_sha sha; uint32_t crc; };
+/* the algorithms of the drivers' masks, in the emitter's order, and how many of them there are: digest_index(alg) counts through them */
+#define DIGEST_ALGS 5
+static const int digest_alg_list[DIGEST_ALGS] = { MSPACK_DIGEST_MD5, MSPACK_DIGEST_SHA1, MSPACK_DIGEST_SHA256, MSPACK_DIGEST_SHA384, MSPACK_DIGEST_SHA512 };
+static inline int digest_is_sha512(int alg) { return alg == MSPACK_DIGEST_SHA384 || alg == MSPACK_DIGEST_SHA512; }
+
+/* a digest call's hash in progress: one of them */
+struct digest_sink { int alg; struct mspack_md5 md5; struct mspack_sha sha; struct mspack_sha512 sha512; uint32_t crc; };
 static inline void sink_init(struct digest_sink *k, int alg)
 {
   k->alg = alg; k->crc = 0;
   if (alg == DIGEST_ALG_CRC32) return;
   if (alg == MSPACK_DIGEST_MD5) mspack_md5_init(&k->md5);
   else if (alg == MSPACK_DIGEST_SHA1) mspack_sha1_init(&k->sha);
+  else if (alg == MSPACK_DIGEST_SHA384) mspack_sha384_init(&k->sha512);
+  else if (alg == MSPACK_DIGEST_SHA512) mspack_sha512_init(&k->sha512);
   else mspack_sha256_init(&k->sha);
 }
 static inline void sink_update(struct digest_sink *k, const void *data, size_t n)
 {
   if (k->alg == DIGEST_ALG_CRC32) { k->crc = mspack_crc32_step(k->crc, data, n); return; }
-  if (k->alg == MSPACK_DIGEST_MD5) mspack_md5_update(&k->md5, data, n); else mspack_sha_update(&k->sha, data, n);
+  if (k->alg == MSPACK_DIGEST_MD5) mspack_md5_update(&k->md5, data, n);
+  else if (digest_is_sha512(k->alg)) mspack_sha512_update(&k->sha512, data, n);
+  else mspack_sha_update(&k->sha, data, n);
 }
 static inline void sink_final(struct digest_sink *k, unsigned char *digest)
 {
-  if (k->alg == MSPACK_DIGEST_MD5) mspack_md5_final(&k->md5, digest); else mspack_sha_final(&k->sha, digest);
+  if (k->alg == MSPACK_DIGEST_MD5) mspack_md5_final(&k->md5, digest);
+  else if (digest_is_sha512(k->alg)) mspack_sha512_final(&k->sha512, digest);
+  else mspack_sha_final(&k->sha, digest);
 }
-static inline int digest_bytes(int alg) { return alg == MSPACK_DIGEST_MD5 ? 16 : alg == MSPACK_DIGEST_SHA1 ? 20 : alg == MSPACK_DIGEST_SHA256 ? 32 : 0; }
-static inline int digest_index(int alg) { return alg == MSPACK_DIGEST_MD5 ? 0 : alg == MSPACK_DIGEST_SHA1 ? 1 : 2; }
+static inline int digest_bytes(int alg)
+{
+  return alg == MSPACK_DIGEST_MD5 ? 16 : alg == MSPACK_DIGEST_SHA1 ? 20 : alg == MSPACK_DIGEST_SHA256 ? 32 : alg == MSPACK_DIGEST_SHA384 ? 48 : alg == MSPACK_DIGEST_SHA512 ? 64 : 0;
+}
+static inline int digest_index(int alg) { return alg == MSPACK_DIGEST_MD5 ? 0 : alg == MSPACK_DIGEST_SHA1 ? 1 : alg == MSPACK_DIGEST_SHA384 ? 3 : alg == MSPACK_DIGEST_SHA512 ? 4 : 2; }
 /* the feature bit and the unit kind of an algorithm */
-static inline unsigned digest_feat(int alg) { return alg == MSPACK_DIGEST_MD5 ? MSPACK_HIP_FEAT_MD5 : alg == MSPACK_DIGEST_SHA1 ? MSPACK_HIP_FEAT_SHA1 : MSPACK_HIP_FEAT_SHA256; }
-static inline uint8_t digest_kind(int alg) { return (uint8_t)(alg == MSPACK_DIGEST_MD5 ? MSPACK_HIP_KIND_MD5 : alg == MSPACK_DIGEST_SHA1 ? MSPACK_HIP_KIND_SHA1 : MSPACK_HIP_KIND_SHA256); }
+static inline unsigned digest_feat(int alg)
+{
+  return alg == MSPACK_DIGEST_MD5 ? MSPACK_HIP_FEAT_MD5 : alg == MSPACK_DIGEST_SHA1 ? MSPACK_HIP_FEAT_SHA1 : alg == MSPACK_DIGEST_SHA384 ? MSPACK_HIP_FEAT_SHA384 :
+         alg == MSPACK_DIGEST_SHA512 ? MSPACK_HIP_FEAT_SHA512 : MSPACK_HIP_FEAT_SHA256;
+}
+static inline uint8_t digest_kind(int alg)
+{
+  return (uint8_t)(alg == MSPACK_DIGEST_MD5 ? MSPACK_HIP_KIND_MD5 : alg == MSPACK_DIGEST_SHA1 ? MSPACK_HIP_KIND_SHA1 : alg == MSPACK_DIGEST_SHA384 ? MSPACK_HIP_KIND_SHA384 :
+                   alg == MSPACK_DIGEST_SHA512 ? MSPACK_HIP_KIND_SHA512 : MSPACK_HIP_KIND_SHA256);
+}
 /* ... and back: the algorithm of a head's kind; 0 for every other kind (a tail's too) */
-static inline int digest_alg_of_kind(unsigned kind) { return kind == MSPACK_HIP_KIND_MD5 ? MSPACK_DIGEST_MD5 : kind == MSPACK_HIP_KIND_SHA1 ? MSPACK_DIGEST_SHA1 : kind == MSPACK_HIP_KIND_SHA256 ? MSPACK_DIGEST_SHA256 : 0; }
-/* a result has sixteen bytes to spare (mspack_hip.h): MD5 is one unit, a wide digest a head and its tail */
-static inline size_t digest_units(int alg) { return digest_bytes(alg) > 16 ? 2 : 1; }
+static inline int digest_alg_of_kind(unsigned kind)
+{
+  return kind == MSPACK_HIP_KIND_MD5 ? MSPACK_DIGEST_MD5 : kind == MSPACK_HIP_KIND_SHA1 ? MSPACK_DIGEST_SHA1 : kind == MSPACK_HIP_KIND_SHA256 ? MSPACK_DIGEST_SHA256 :
+         kind == MSPACK_HIP_KIND_SHA384 ? MSPACK_DIGEST_SHA384 : kind == MSPACK_HIP_KIND_SHA512 ? MSPACK_DIGEST_SHA512 : 0;
+}
+/* a result has sixteen bytes to spare (mspack_hip.h): MD5 is one unit, a wide digest a head and its tails -- 2 units for SHA-1 and
+ * SHA-256, 3 for SHA-384, 4 for SHA-512 */
+static inline size_t digest_units(int alg) { const int nd = digest_bytes(alg); return nd > 16 ? (size_t)(nd + 15) / 16u : 1; }
 /* the units one file needs at most for the algorithms of the mask `algs` */
 static inline size_t digest_units_per_file(int algs)
 {
-  size_t n = 0; int alg;
-  for (alg = MSPACK_DIGEST_MD5; alg <= MSPACK_DIGEST_SHA256; alg <<= 1) if (algs & alg) n += digest_units(alg);
+  size_t n = 0; int a;
+  for (a = 0; a < DIGEST_ALGS; a++) if (algs & digest_alg_list[a]) n += digest_units(digest_alg_list[a]);
   if (algs & DIGEST_ALG_CRC32) n++;
   return n;
 }
@@ -72,14 +100,19 @@ static inline size_t digest_units_per_file(int algs)
  * compiled defaults are the quotients rounded down; MSPACK_HIP_SHA1_RATIO / MSPACK_HIP_SHA256_RATIO override them in the same way. */
 #define SHA1_RATIO_DEFAULT 0.05
 #define SHA256_RATIO_DEFAULT 0.04
+/* SHA-384 and SHA-512 share one kernel and one host function, so one ratio (MSPACK_HIP_SHA512_RATIO) serves both.  Measured the same
+ * way on an MI355X box, three runs per algorithm (profiles/sha512_digest.txt; tools/sha512_digest_bench.py rates
+ * 8 3): one lane 11.0 to 14.7 MB/s, csrc/host/sha512.c on one core 539 to 553 MB/s -- SHA-384 0.0234, 0.0199, 0.0257; SHA-512 0.0236,
+ * 0.0272, 0.0239; mean 0.0240.  The compiled default is that quotient rounded down. */
+#define SHA512_RATIO_DEFAULT 0.02
 extern unsigned mspack_hip_features(void) __attribute__((weak));
 static inline double digest_ratio(int alg)
 {
   /* (read once per driver, in parts per million; plain C has no dynamic initialiser for a static: the first callers all compute
    * the same value, and it is published and read with atomic accesses, so two decompressors on two threads do not race) */
-  static long long ppm[3] = { -1, -1, -1 };
-  static const char *const name[3] = { "MSPACK_HIP_MD5_RATIO", "MSPACK_HIP_SHA1_RATIO", "MSPACK_HIP_SHA256_RATIO" };
-  static const double dflt[3] = { MD5_RATIO_DEFAULT, SHA1_RATIO_DEFAULT, SHA256_RATIO_DEFAULT };
+  static long long ppm[DIGEST_ALGS] = { -1, -1, -1, -1, -1 };
+  static const char *const name[DIGEST_ALGS] = { "MSPACK_HIP_MD5_RATIO", "MSPACK_HIP_SHA1_RATIO", "MSPACK_HIP_SHA256_RATIO", "MSPACK_HIP_SHA512_RATIO", "MSPACK_HIP_SHA512_RATIO" };
+  static const double dflt[DIGEST_ALGS] = { MD5_RATIO_DEFAULT, SHA1_RATIO_DEFAULT, SHA256_RATIO_DEFAULT, SHA512_RATIO_DEFAULT, SHA512_RATIO_DEFAULT };
   const int a = digest_index(alg);
   long long v = __atomic_load_n(&ppm[a], __ATOMIC_RELAXED);
   if (v < 0) {
@@ -94,33 +127,35 @@ static inline double digest_ratio(int alg)
  * mspack_hip_features cannot) and the ratio is above 0 */
 static inline int digest_device_algs(int asked)
 {
-  int alg, algs = 0;
-  for (alg = MSPACK_DIGEST_MD5; alg <= MSPACK_DIGEST_SHA256; alg <<= 1)
+  int a, alg, algs = 0;
+  for (a = 0; a < DIGEST_ALGS && (alg = digest_alg_list[a]) != 0; a++)
     if ((asked & alg) && mspack_hip_features && (mspack_hip_features() & digest_feat(alg)) && digest_ratio(alg) > 0.0) algs |= alg;
   /* (CRC-32 range units: no ratio -- the device takes them at any length) */
   if ((asked & DIGEST_ALG_CRC32) && mspack_hip_features && (mspack_hip_features() & MSPACK_HIP_FEAT_CRC32_RANGES)) algs |= DIGEST_ALG_CRC32;
   return algs;
 }
-static inline void digest_ratios(double ratio[3]) { int alg; for (alg = MSPACK_DIGEST_MD5; alg <= MSPACK_DIGEST_SHA256; alg <<= 1) ratio[digest_index(alg)] = digest_ratio(alg); }
+static inline void digest_ratios(double ratio[DIGEST_ALGS]) { int a; for (a = 0; a < DIGEST_ALGS; a++) ratio[a] = digest_ratio(digest_alg_list[a]); }
 
 /* ---- the digest units of one file --------------------------------------------------------------------------------------------------
  * The file's bytes lie at [out_off, out_off + len) of the batch's output arena; `sum`: the bytes of all files of the batch that may
  * get units.  Per algorithm of `algs` whose ratio[digest_index(alg)] x sum is not below len: the head (kind, out_off, out_len, every
- * other field 0) and, for a wide digest, its tail (the kind alone) behind it, MD5 / SHA-1 / SHA-256 in that order.  Written to
- * units[n ..) as far as they fit below `cap`, a head never without its tail (units == NULL: counts only).  Returns the units the
- * file needs, fitting or not. */
-static inline size_t digest_emit_file(uint64_t out_off, uint32_t len, double sum, int algs, const double ratio[3],
+ * other field 0) and, for a wide digest, its tails (the kind alone) behind it, MD5 / SHA-1 / SHA-256 / SHA-384 / SHA-512 in that order.
+ * Written to units[n ..) as far as they fit below `cap`, a head never without all its tails (units == NULL: counts only).  Returns
+ * the units the file needs, fitting or not.  (ratio[] is read at the indices of the algorithms of `algs` only: a caller that asks
+ * for the first three may pass three.) */
+static inline size_t digest_emit_file(uint64_t out_off, uint32_t len, double sum, int algs, const double *ratio,
                                       mspack_hip_unit *units, size_t n, size_t cap)
 {
-  size_t made = 0; int alg;
-  for (alg = MSPACK_DIGEST_MD5; alg <= MSPACK_DIGEST_SHA256; alg <<= 1) {
+  size_t made = 0, j; int a;
+  for (a = 0; a < DIGEST_ALGS; a++) {
+    const int alg = digest_alg_list[a];
     const size_t need = digest_units(alg), at = n + made;
-    if (!(algs & alg) || (double) len > ratio[digest_index(alg)] * sum) continue;
+    if (!(algs & alg) || (double) len > ratio[a] * sum) continue;
     if (units && at + need <= cap) {
       memset(&units[at], 0, need * sizeof(*units));
       units[at].kind = digest_kind(alg);
       units[at].out_off = out_off; units[at].out_len = len;
-      if (need == 2) units[at + 1].kind = MSPACK_HIP_KIND_DIGEST_MORE;
+      for (j = 1; j < need; j++) units[at + j].kind = MSPACK_HIP_KIND_DIGEST_MORE;
     }
     made += need;
   }
@@ -137,9 +172,9 @@ static inline size_t digest_emit_file(uint64_t out_off, uint32_t len, double sum
 
 /* ---- the digests a batch took, kept ------------------------------------------------------------------------------------------------
  * One record per head whose result -- and whose tail's -- came back MSPACK_ERR_OK, ascending by (offset, length, alg); d: the
- * algorithm's 16, 20 or 32 bytes, zeros behind them.  The owner allocates e[]; sorts: how often a harvest found its records out
+ * algorithm's 16, 20, 32, 48 or 64 bytes, zeros behind them.  The owner allocates e[]; sorts: how often a harvest found its records out
  * of order and sorted (the planners emit ascending: normally never); next: the record behind the last one found. */
-struct digest_kept { uint64_t offset; uint32_t length; int alg; unsigned char d[32]; };
+struct digest_kept { uint64_t offset; uint32_t length; int alg; unsigned char d[64]; };
 struct digest_table { struct digest_kept *e; size_t n, next; unsigned sorts; };
 static inline int digest_kept_order(const void *pa, const void *pb)
 {
@@ -150,20 +185,23 @@ static inline int digest_kept_order(const void *pa, const void *pb)
 }
 /* units[0 .. n) -- digest heads and tails -- and their results res[0 .. n) join the table, which has room for n more records; a
  * record's offset is its head's out_off - out_base + base (the owner's origin instead of the output arena's).  Bytes 0 to 15 of a digest
- * are the head's result from out_len on, bytes 16 .. of a wide one the NEXT unit's (mspack_hip.h): a wide head without one is dropped. */
+ * are the head's result from out_len on, bytes 16 k .. of a wide one those of the unit k places behind it (mspack_hip.h): a wide
+ * head whose tails are not all there and MSPACK_ERR_OK is dropped. */
 static inline void digest_table_harvest(struct digest_table *t, const mspack_hip_unit *units, const mspack_hip_result *res, size_t n,
                                         uint64_t out_base, uint64_t base)
 {
-  size_t j; int ascending = 1;
+  size_t j, k; int ascending = 1;
   for (j = 0; j < n; j++) {
-    const int alg = units[j].kind == MSPACK_HIP_KIND_CRC32 ? DIGEST_ALG_CRC32 : digest_alg_of_kind(units[j].kind), wide = alg && digest_units(alg) == 2;
+    const int alg = units[j].kind == MSPACK_HIP_KIND_CRC32 ? DIGEST_ALG_CRC32 : digest_alg_of_kind(units[j].kind);
+    const size_t tails = alg && alg != DIGEST_ALG_CRC32 ? digest_units(alg) - 1 : 0, nd = (size_t) digest_bytes(alg);
     struct digest_kept *e = &t->e[t->n];
     if (!alg || res[j].err != MSPACK_ERR_OK) continue;            /* (a tail is taken with its head) */
-    if (wide && (j + 1 >= n || units[j + 1].kind != MSPACK_HIP_KIND_DIGEST_MORE || res[j + 1].err != MSPACK_ERR_OK)) continue;
+    for (k = 1; k <= tails; k++) if (j + k >= n || units[j + k].kind != MSPACK_HIP_KIND_DIGEST_MORE || res[j + k].err != MSPACK_ERR_OK) break;
+    if (k <= tails) continue;
     e->offset = units[j].out_off - out_base + base; e->length = units[j].out_len; e->alg = alg;
     memset(e->d, 0, sizeof(e->d));
     memcpy(e->d, &res[j].out_len, 16);
-    if (wide) memcpy(e->d + 16, &res[j + 1].out_len, (size_t) digest_bytes(alg) - 16);
+    for (k = 1; k <= tails; k++) memcpy(e->d + 16 * k, &res[j + k].out_len, nd - 16 * k < 16 ? nd - 16 * k : 16);
     if (t->n && digest_kept_order(e - 1, e) > 0) ascending = 0;
     t->n++;
   }
@@ -198,7 +236,7 @@ static inline int digest_call_args(const void *file, int alg, unsigned char *dig
 }
 /* a call that succeeded: the digest the batch took of the file (`kept`) or else the one hashed on the way, and the driver's counter
  * of either -- counts[digest_index(alg)][0: from the device, 1: on the host], over all decompressors of the process */
-static inline void digest_call_done(struct digest_sink *k, const unsigned char *kept, unsigned char *digest, unsigned long long counts[3][2])
+static inline void digest_call_done(struct digest_sink *k, const unsigned char *kept, unsigned char *digest, unsigned long long counts[DIGEST_ALGS][2])
 {
   if (kept) memcpy(digest, kept, (size_t) digest_bytes(k->alg)); else sink_final(k, digest);
   __atomic_fetch_add(&counts[digest_index(k->alg)][kept ? 0 : 1], 1ull, __ATOMIC_RELAXED);
@@ -225,7 +263,7 @@ static inline void crc32_counts_get(unsigned long long counts[2], unsigned long 
   }
 }
 /* the *_digest_counts calls: the pair of one algorithm (an unknown one: zeros), optionally reset */
-static inline void digest_counts_get(unsigned long long counts[3][2], int alg, unsigned long long out[2], int reset)
+static inline void digest_counts_get(unsigned long long counts[DIGEST_ALGS][2], int alg, unsigned long long out[2], int reset)
 {
   int i;
   if (!digest_bytes(alg)) { if (out) out[0] = out[1] = 0; return; }
@@ -238,14 +276,14 @@ static inline void digest_counts_get(unsigned long long counts[3][2], int alg, u
 /* ---- CHM: the digest units of one chunk -------------------------------------------------------------------------------------------
  * files[0 .. n_files): the CHM's section-1 files with length > 0, ascending by offset.  The chunk decodes the stream's bytes
  * [chunk_lo, chunk_hi) into its output buffer from 0 on; the stream ends at padded_len.  Per algorithm of `algs` (a mask of
- * MSPACK_DIGEST_*) one unit -- a SHA head with its MSPACK_HIP_KIND_DIGEST_MORE tail behind it -- for every file that lies wholly in
+ * MSPACK_DIGEST_*) one unit -- a SHA head with its MSPACK_HIP_KIND_DIGEST_MORE tails behind it -- for every file that lies wholly in
  * [chunk_lo, min(chunk_hi, padded_len)) and is no longer than ratio[digest_index(alg)] x (the bytes of all such files), with
  * out_off = offset - chunk_lo and out_len = length (digest_emit_file); a file's algorithms next to each other, files in list order.  Files that
  * cross a chunk boundary, reach past padded_len, have length 0 or are above the ratio get none.  Returns the number of units
  * (heads and tails); writes them to units[0 .. cap) as far as they fit (units == NULL: counts only). */
 struct chm_digest_file { uint64_t offset, length; };
 static inline size_t chm_digest_plan(const struct chm_digest_file *files, size_t n_files, uint64_t chunk_lo, uint64_t chunk_hi,
-                                     uint64_t padded_len, int algs, const double ratio[3], mspack_hip_unit *units, size_t cap)
+                                     uint64_t padded_len, int algs, const double *ratio, mspack_hip_unit *units, size_t cap)
 {
   const uint64_t hi = chunk_hi < padded_len ? chunk_hi : padded_len;
   size_t lo_i = 0, hi_i = n_files, i, n = 0;
