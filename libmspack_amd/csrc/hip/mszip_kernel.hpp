@@ -13,8 +13,16 @@
 //                     into out[B_b + idx]; an index the current block has not written yet is
 //                     served from the most recent earlier block that was long enough (a short
 //                     monotonic stack of (B, length) pairs) -- bit-identical to the ring.
+//                     The stack holds ZIP_HIST levels (blocks of strictly shrinking lengths).  Where
+//                     a level more would have to be kept, the unit goes over to the reference's own
+//                     ring: the 32768 window bytes are laid out in the unit's
+//                     slack, every later block is decoded there and its bytes are copied down to
+//                     their place; what the last block produced beyond the request is moved to the
+//                     front of the slack (the in_next contract).  Parse and fold records are not
+//                     adopted from then on.  A full block (the whole window) ends the ring: the
+//                     history is linear again.  A folder of full blocks never gets there.
 // Output regions of MSZIP units need 32768 bytes of slack after out_len (a block is decoded in
-// full even when only part of it is requested, mszipd.c:442-446).
+// full even when only part of it is requested, mszipd.c:442-446; the ring above lives there too).
 #pragma once
 #include "wave_common.hpp"
 #include "spec_queue.hpp"
@@ -1055,6 +1063,24 @@ __device__ __forceinline__ int zip_inflate(ZipDec &d, u32 &bytes_output)
   return 0;
 }
 
+// The ring of mszip_decode_unit (a history deeper than the stack).  zip_ring_fill: the reference's window[32768] as it is behind
+// the current block of `hw` bytes -- this block, then the stack, 0 where nothing was ever written -- into the unit's slack.
+// zip_ring_move: n bytes of the unit's region from src down to dst < src, 64 at a time in rising order (they may overlap).
+__device__ __forceinline__ void zip_ring_fill(const ZipDec &d, const u32 ring_B, const u32 hw)
+{
+#pragma unroll 1
+  for (u32 x = d.lane; x < ZIP_FRAME; x += WAVE) d.out[ring_B + x] = (u8) d.win_byte(x, hw);
+}
+__device__ __forceinline__ void zip_ring_move(u8 *out, const u32 dst, const u32 src, const u32 n, const u32 lane)
+{
+#pragma unroll 1
+  for (u32 c = 0; c < n; c += WAVE) {
+    const u32 k = c + lane;
+    const u32 v = k < n ? out[src + k] : 0u;
+    if (k < n) out[dst + k] = (u8) v;
+  }
+}
+
 // recs / toks: the parse waves' records and tokens for this launch (NULL: none), indexed by frame slot
 __device__ __forceinline__ void mszip_decode_unit(const mspack_hip_unit &u, const u8 *in_arena, u8 *out_arena,
                                   mspack_hip_result *res, MszipShared *sh, const ZipBlockRec *recs, const uint2 *toks)
@@ -1088,6 +1114,9 @@ __device__ __forceinline__ void mszip_decode_unit(const mspack_hip_unit &u, cons
   u32 *const rlog = (u32 *)(out_arena + u.out_off + (((size_t) u.out_len + ZIP_FRAME + 15u) & ~(size_t) 15u));
   const u32 rlog_cap = logging ? (u32) u.e8_base : 0u;
   u32 n_repaired = 0;
+  // a history deeper than the stack (below, where a block is pushed): the unit's slack is the reference's ring from then on
+  bool ring = false;
+  const u32 ring_B = u.out_len;
 
   while (remaining > 0u || kwaj) {
     d.byte_align();
@@ -1128,7 +1157,7 @@ __device__ __forceinline__ void mszip_decode_unit(const mspack_hip_unit &u, cons
       const u32 st_ = rfl(rc_->status);       // (the parse kernel ran before this one)
       // (and only where the parse wave put the literals: every earlier block of the folder a full one)
       // (its matches may have been copied already, as a fold task: only usable when every block before it was taken that way)
-      const bool at = st_ == 1u && rfl(rc_->start_bit) == d.w.origin * 8u + d.cons_bits() && d.B == blk * ZIP_FRAME;
+      const bool at = st_ == 1u && rfl(rc_->start_bit) == d.w.origin * 8u + d.cons_bits() && !ring && d.B == blk * ZIP_FRAME;
       const bool folded = at && fold_chain && rfl(rc_->fold) == ZIP_FOLD_DONE;
       if (!folded) fold_chain = false;
       if (at && (folded || zip_run_tokens(d, toks, rc_->chunk, rc_->n_tokens, rc_->total_out))) {
@@ -1155,7 +1184,7 @@ __device__ __forceinline__ void mszip_decode_unit(const mspack_hip_unit &u, cons
         if (logging) {
           // (the reference's count: its bytes_output includes a flush that overflowed the frame -- the number can wrap)
           const u32 rbo = (d.ref_bo == 0u && d.wpos > 0u) ? d.wpos : d.ref_bo;
-          if (lane == 0 && n_repaired < rlog_cap) { rlog[1u + 2u * n_repaired] = d.B; rlog[2u + 2u * n_repaired] = ZIP_FRAME - rbo; }
+          if (lane == 0 && n_repaired < rlog_cap) { rlog[1u + 2u * n_repaired] = written; rlog[2u + 2u * n_repaired] = ZIP_FRAME - rbo; }
           n_repaired++;
         }
         if (r < 0) {
@@ -1187,37 +1216,72 @@ __device__ __forceinline__ void mszip_decode_unit(const mspack_hip_unit &u, cons
       else { err = (r > 0) ? r : ERR_DECRUNCH; break; }
     }
     u32 n = remaining < bytes_output ? remaining : bytes_output;
+    if (ring) {
+      // the block was decoded in the ring.  What it produced beyond the request (it is the unit's last block then) moves
+      // to the front of the slack: the in_next contract -- those bytes lie right behind out_len
+      zip_ring_move(d.out, written, ring_B, n, lane);
+      if (bytes_output > n) zip_ring_move(d.out, ring_B, ring_B + n, bytes_output - n, lane);
+    }
     written += n;
     if (r > 0 && repair) { err = r; break; }                                     // mszipd.c:449
     remaining -= n;
     leftover = bytes_output - n;
     // remember this block for later blocks' history reads; entries it shadows (not longer than
     // it) are dropped, so the stack stays strictly increasing in length towards older blocks
-    if (bytes_output) {
+    if (bytes_output && !ring) {
       u32 nh = 0, tl[ZIP_HIST - 1], tb[ZIP_HIST - 1];
+      bool deep = false;          // one more older block is still visible above this one than the stack holds
 #pragma unroll
       for (u32 k = 0; k < ZIP_HIST - 1u; k++) { tl[k] = 0; tb[k] = 0; }
 #pragma unroll
       for (u32 k = 0; k < ZIP_HIST; k++) {
         if (k < d.hist_n) {
           u32 hl = rfl(sh->hist_len[k]), hb = rfl(sh->hist_B[k]);
-          if (hl > bytes_output && nh < ZIP_HIST - 1u) {
+          if (hl > bytes_output) {
+            if (nh < ZIP_HIST - 1u) {
 #pragma unroll
-            for (u32 q = 0; q < ZIP_HIST - 1u; q++) if (q == nh) { tl[q] = hl; tb[q] = hb; }
-            nh++;
+              for (u32 q = 0; q < ZIP_HIST - 1u; q++) if (q == nh) { tl[q] = hl; tb[q] = hb; }
+              nh++;
+            }
+            else deep = true;
           }
         }
       }
-      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-      if (lane == 0) {
-        sh->hist_len[0] = bytes_output; sh->hist_B[0] = d.B;
-#pragma unroll
-        for (u32 k = 0; k < ZIP_HIST - 1u; k++) { sh->hist_len[k + 1u] = tl[k]; sh->hist_B[k + 1u] = tb[k]; }
+      if (deep && n == bytes_output && (remaining > 0u || kwaj)) {
+        // Beyond the stack's depth nothing is dropped: the unit goes over to the reference's own ring.  The 32768 window
+        // bytes as they are now (this block, then the stack; 0 where nothing was ever written) are laid out in the unit's
+        // slack; every later block is decoded THERE (window index = offset in the slack, win_byte's only entry is the
+        // ring itself) and its bytes are copied down to where they belong.  (n == bytes_output: a block that ends the
+        // request has its leftover in the slack already, and nothing is decoded after it.)
+        zip_ring_fill(d, ring_B, bytes_output);
+        ring = true;
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+        if (lane == 0) { sh->hist_len[0] = ZIP_FRAME; sh->hist_B[0] = ring_B; }
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+        d.hist_n = 1u;
       }
-      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-      d.hist_n = 1u + nh;
+      else {
+        // (`deep` with a block that ends the request: the oldest level is dropped here after all -- harmless, because nothing
+        // is decoded behind that block)
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+        if (lane == 0) {
+          sh->hist_len[0] = bytes_output; sh->hist_B[0] = d.B;
+#pragma unroll
+          for (u32 k = 0; k < ZIP_HIST - 1u; k++) { sh->hist_len[k + 1u] = tl[k]; sh->hist_B[k + 1u] = tb[k]; }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+        d.hist_n = 1u + nh;
+      }
     }
-    d.B += n;
+    else if (ring && n == ZIP_FRAME) {
+      // a full block is the whole window: the history is linear again, in the output where the block was copied to
+      ring = false;
+      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+      if (lane == 0) { sh->hist_len[0] = ZIP_FRAME; sh->hist_B[0] = written - ZIP_FRAME; }
+      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+      d.hist_n = 1u;
+    }
+    d.B = ring ? ring_B : written;
   }
   if (logging && lane == 0) rlog[0] = n_repaired;
   if (lane == 0) {

@@ -244,3 +244,44 @@ done:
   free(z);
   return err;
 }
+
+/* KWAJ framing (mszipd_decompress_kwaj, mszipd.c:462-495): per block a 16-bit length word, of which only 0 matters (end of
+ * the stream), exactly 'C','K', one inflate; every block is written whole, and a failing stream has written the blocks before
+ * the failure.  Same ring, bit reader and EOF rules as above.  `room`: the batch ABI's rule for a KWAJ-framed unit -- a block
+ * is started only with 32768 bytes of room left, else ORC_F_OUT_FULL ends the decode with what fitted (err 0). */
+int oracle_mszip_kwaj_decode(const uint8_t *in, size_t in_len, uint8_t *out, size_t out_cap,
+                             uint64_t room, oracle_result *res)
+{
+  zip_t *z = (zip_t *) calloc(1, sizeof(*z));
+  uint64_t written = 0, remaining = room;
+  int err = ORC_OK, r;
+  uint32_t flags = 0;
+  unsigned lo, hi, v;
+
+  memset(res, 0, sizeof(*res));
+  init_tables();
+  z->b.in = in; z->b.in_len = in_len; z->b.bufsz = 4096;
+  for (;;) {
+    z_restore(&z->b);                                               /* mszipd.c:468 */
+    ZDROP(&z->b, z->b.bl & 7);
+    if (z_bits(&z->b, 8, &lo) || z_bits(&z->b, 8, &hi)) { err = ORC_READ; break; }
+    if ((lo | (hi << 8)) == 0) break;
+    if (z_bits(&z->b, 8, &v)) { err = ORC_READ; break; }
+    if (v != 'C') { err = ORC_DATAFORMAT; break; }
+    if (z_bits(&z->b, 8, &v)) { err = ORC_READ; break; }
+    if (v != 'K') { err = ORC_DATAFORMAT; break; }
+    if (remaining < FRAME) { flags |= ORC_F_OUT_FULL; break; }
+    z->wpos = 0; z->bytes_output = 0;
+    z_store(&z->b);                                                 /* mszipd.c:484 */
+    r = inflate_block_stream(z);
+    if (r) { err = (r > 0) ? r : ORC_DECRUNCH; break; }
+    if (out && written < out_cap) {
+      size_t left = out_cap - (size_t) written;
+      memcpy(out + written, z->window, z->bytes_output < left ? z->bytes_output : left);
+    }
+    written += z->bytes_output; remaining -= z->bytes_output;
+  }
+  res->err = err; res->flags = flags; res->out_len = written; res->in_used = z->b.pos; res->in_next = 0;
+  free(z);
+  return err;
+}

@@ -37,6 +37,8 @@ extern "C" {
 #define ORC_F_BLOCK_OPEN     16u  /* LZX: the last decoded frame ended inside a block (block_remaining != 0;
                                      at a reset point the reference warns and goes on, lzxd.c:424-431)   */
 
+#define ORC_F_OUT_FULL        8u  /* KWAJ-framed MSZIP: the next block did not fit the room (MSPACK_HIP_F_OUT_FULL)          */
+
 typedef struct oracle_result {
   int32_t  err;       /* MSPACK_ERR_* the reference would return from the decompress call      */
   uint32_t flags;
@@ -77,6 +79,11 @@ int oracle_lzxd_decode(const uint8_t *in, size_t in_len, uint8_t *out, size_t ou
 int oracle_mszip_decode(const uint8_t *in, size_t in_len, uint8_t *out, size_t out_cap,
                         uint64_t out_bytes, int repair_mode, uint32_t *block_lens, int cap,
                         int *n_blocks, oracle_result *res);
+
+/* MSZIP as KWAJ files frame it: mszipd_init + mszipd_decompress_kwaj (mszipd.c:462-495) over the bytes behind the KWAJ header.
+ * `room`: a block is started only with 32768 bytes of it left, else ORC_F_OUT_FULL (the batch ABI's MSPACK_HIP_F_OUT_FULL). */
+int oracle_mszip_kwaj_decode(const uint8_t *in, size_t in_len, uint8_t *out, size_t out_cap,
+                             uint64_t room, oracle_result *res);
 
 /* Quantum: qtmd_init(window_bits) + one qtmd_decompress(out_bytes) over a whole folder stream
  * (CFDATA payloads, each followed by the 0xFF trailer cabd.c:1330-1332 injects). */

@@ -366,9 +366,12 @@ BL_DEFAULT = [4] * 13 + [5] * 6                      # a complete bit-length cod
 
 class Deflate:
     """MSZIP: 'CK' frames of deflate blocks, LSB-first bits, Huffman codes most significant bit first; decodes what it writes
-    with mszipd.c's 32 KiB window (window_posn back to 0 in every frame, the window's bytes kept)."""
+    with mszipd.c's 32 KiB window (window_posn back to 0 in every frame, the window's bytes kept).  kwaj: the framing of
+    mszipd_decompress_kwaj (mszipd.c:462-495) -- a 16-bit length word in front of every 'CK', end() writes the terminator.
+    The model keeps, per window index, the frame that wrote it last (owner; -1 = never written, where the reference reads
+    uninitialised memory): a match that reads such an index is counted in props["never_written_reads"]."""
 
-    def __init__(self):
+    def __init__(self, kwaj=False):
         self.out = bytearray()
         self.acc, self.n = 0, 0
         self.win, self.wpos = bytearray(FRAME), 0
@@ -376,6 +379,10 @@ class Deflate:
         self.tab = []
         self.last_kind = None                 # the kind of the frame's previous block
         self.props = {}
+        self.kwaj = kwaj
+        self.word_at = None                   # kwaj: where the current frame's length word is (filled in when the frame ends)
+        self.owner = [-1] * FRAME
+        self.blocks = []                      # bytes every frame produced
 
     def put(self, v, n):
         # (the low n bits of v, least significant first; whole bytes leave at once)
@@ -394,22 +401,57 @@ class Deflate:
         if self.n:
             self.put(0, 8 - self.n)
 
-    def frame(self, junk=b""):
-        """a new CK frame; `junk`: bytes in front of the signature, which the reference skips (mszipd.c:398-405)"""
+    def _close_word(self):
+        # kwaj: the length word says how many bytes the frame has ('CK' + deflate data), as real files do
+        if self.word_at is not None:
+            n = len(self.out) - self.word_at - 2
+            assert 0 < n < 65536
+            self.out[self.word_at:self.word_at + 2] = n.to_bytes(2, "little")
+            self.word_at = None
+
+    def frame(self, junk=b"", sig=b"CK", word=None):
+        """a new CK frame; `junk`: bytes in front of the signature, which the reference skips (mszipd.c:398-405).  kwaj: `word`
+        = a length word that lies (only 0 matters to the decoder), `sig` = what stands where 'CK' belongs"""
         self.byte_align()
+        self._close_word()
         assert b"CK" not in junk + b"C"
         self.out += junk
+        if self.kwaj:
+            if word is None:
+                self.word_at = len(self.out)
+            self.out += (0xFFFF if word is None else word).to_bytes(2, "little")
         self.tab.append(len(self.out))
-        self.out += b"CK"
+        self.out += sig
         self.wpos = 0
         self.last_kind = None
+        self.blocks.append(0)
+
+    def end(self):
+        """kwaj: the terminator, a length word of 0"""
+        self.byte_align()
+        self._close_word()
+        self.out += b"\0\0"
 
     def _emit(self, b):
         self.win[self.wpos] = b
+        self.owner[self.wpos] = len(self.blocks) - 1
         self.wpos += 1
         self.plain.append(b)
+        self.blocks[-1] += 1
         if self.wpos == FRAME:
             self.wpos = 0
+
+    def _emit_many(self, data):
+        # (whole runs at once: what _emit does byte by byte)
+        data = bytes(data)
+        while data:
+            n = min(len(data), FRAME - self.wpos)
+            self.win[self.wpos:self.wpos + n] = data[:n]
+            self.owner[self.wpos:self.wpos + n] = [len(self.blocks) - 1] * n
+            self.wpos = (self.wpos + n) % FRAME
+            self.plain += data[:n]
+            self.blocks[-1] += n
+            data = data[n:]
 
     def stored(self, data, last=0, nlen=None):
         self.put(last, 1); self.put(0, 2)
@@ -421,8 +463,7 @@ class Deflate:
         n = len(data)
         self.out += n.to_bytes(2, "little") + ((~n & 0xFFFF) if nlen is None else nlen).to_bytes(2, "little")
         self.out += bytes(data)
-        for b in data:
-            self._emit(b)
+        self._emit_many(data)
 
     def _tokens(self, toks, lc, dc):
         for t in toks:
@@ -445,7 +486,10 @@ class Deflate:
                 self.props["max_dist"] = max(self.props.get("max_dist", 0), dist)
                 for _ in range(length):
                     p = self.wpos - dist
-                    self._emit(self.win[p + FRAME if p < 0 else p])
+                    p = p + FRAME if p < 0 else p
+                    if self.owner[p] < 0:
+                        self.props["never_written_reads"] = self.props.get("never_written_reads", 0) + 1
+                    self._emit(self.win[p])
         self.code(lc[256])
 
     def fixed(self, toks, last=0):
@@ -488,6 +532,7 @@ class Deflate:
 
     def stream(self, pad=8):
         self.byte_align()
+        self._close_word()
         return bytes(self.out) + b"\0" * pad
 
 
@@ -1448,6 +1493,304 @@ def mszip_cases():
     d.frame(junk=b"xyzC" * 3 + b"Q")
     d.stored(T(235, 77), last=1)
     C.append(_mszip_case("mszip_bytes_before_the_ck_signature", d))
+    return C
+
+
+# ---- MSZIP: window history at any depth, and KWAJ framing -------------------------------------------------------------
+# mszip_kernel.hpp keeps no ring: a window index the current block has not written is served from a stack of earlier
+# blocks (ZIP_HIST entries), and beyond that depth from a ring in the unit's slack.  A chain of blocks of strictly
+# shrinking lengths L_1 > L_2 > ... makes one level per block: block k is the last writer of the indices [L_(k+1), L_k).
+# The probe block behind a chain reads, with one match per level, the last 8 bytes of every level's own range -- a lost
+# level shows up at its own offset.  Expected bytes are the Deflate model's (its own ring), never a decoder's.
+ZIP_HIST = 8                          # mszip_kernel.hpp: the stack's depth
+UF_MSZIP_REPAIR, UF_HARD_EOF, UF_MSZIP_KWAJ, UF_MSZIP_LOG, F_OUT_FULL = 1, 2, 4, 16, 8
+
+
+def _rb(seed, n):
+    return random.Random(seed).randbytes(n)
+
+
+def _levels(d, floor):
+    """[(frame, lo, hi)] of the model's window, highest index first: the runs of indices >= floor one frame wrote last"""
+    runs, hi = [], FRAME - 1
+    while hi >= floor:
+        lo = hi
+        while lo > floor and d.owner[lo - 1] == d.owner[hi]:
+            lo -= 1
+        runs.append((d.owner[hi], lo, hi))
+        hi = lo - 1
+    return runs
+
+
+def _probe(d, never=False, last=1):
+    """a frame that reads 8 bytes from the top of every level (never: also from ranges no frame ever wrote)"""
+    n_lv = len(_levels(d, 0))
+    floor = 8 + 8 * n_lv + 8
+    d.frame()
+    toks, w = [('L', b"[probe] ")], 8
+    for f, lo, hi in _levels(d, floor):
+        if hi - lo + 1 < 8 or (f < 0 and not never):
+            continue
+        toks.append(('M', 8, w + FRAME - (hi - 7))); w += 8
+    d.fixed(toks, last=last)
+    return (w - 8) // 8
+
+
+def _chain(d, lengths, seed, kinds="s"):
+    """one frame per length; kinds (cycled): s = one stored block, f = fixed Huffman literals with matches into the window as it
+    was before the frame, y = dynamic Huffman likewise, m = a stored, a fixed and a dynamic block in one frame"""
+    lit = flat_lengths(286, list(range(256)) + [256, 257 + 5, 257 + 14])
+    dst = flat_lengths(30, list(range(30)))
+    for k, n in enumerate(lengths):
+        kind = kinds[k % len(kinds)]
+        d.frame()
+        if kind == "s" or n < 1800:
+            d.stored(_rb(seed + k, n), last=1)
+            continue
+        def toks(m, s):
+            # m bytes: literals, matches of 8 and 30 bytes from far above (older frames' bytes) and from near below, literals
+            return [('L', _text(s, 200)), ('M', 8, FRAME - 100), ('M', 30, 150), ('M', 30, FRAME), ('L', _text(s + 1, m - 268))]
+        if kind == "f":
+            d.fixed(toks(n, seed + 100 * k), last=1)
+        elif kind == "y":
+            d.dynamic(toks(n, seed + 100 * k), lit, dst, last=1)
+        else:
+            a = n // 3
+            d.stored(_rb(seed + k, a), last=0)
+            d.fixed(toks(a, seed + 100 * k), last=0)
+            d.dynamic(toks(n - 2 * a, seed + 100 * k + 7), lit, dst, last=1)
+        assert d.blocks[-1] == n, (k, n, d.blocks[-1])
+
+
+def _shrinking(depth, step=None):
+    step = step or (700 if depth > 12 else 2000)
+    return [FRAME - k * step for k in range(depth)]
+
+
+def _hist_case(name, d, out_len=None, flags=0, in_chunk=0, never=False, err=ERR_OK, plain=None):
+    """CAB framing: a request of out_len bytes (default: everything).  props: in_next = what the block the request ends in
+    produced beyond it, written = bytes handed out, flags / in_chunk = the unit's"""
+    total = len(d.plain)
+    out_len = total if out_len is None else out_len
+    assert 0 < out_len <= total
+    assert never or not d.props.get("never_written_reads"), (name, "reads window bytes no frame wrote")
+    end = 0
+    for n in d.blocks:
+        end += n
+        if end >= out_len:
+            break
+    plain = bytes(d.plain[:out_len]) if plain is None else plain
+    props = dict(d.props, in_next=end - out_len if err == ERR_OK else 0, written=len(plain), uflags=flags, in_chunk=in_chunk,
+                 blocks=list(d.blocks), never=never)
+    return Case(name, "mszip", d.stream(), out_len, tab=d.tab, plain=plain, err=err, props=props)
+
+
+def _kwaj_case(name, d, room=None, err=ERR_OK, flags=0, hard_eof=False, plain=None, never=False, stream=None):
+    """KWAJ framing into `room` bytes (default: ample).  plain = the bytes written, also where the stream fails"""
+    plain = bytes(d.plain) if plain is None else bytes(plain)
+    assert never or not d.props.get("never_written_reads"), (name, "reads window bytes no frame wrote")
+    room = len(d.plain) + FRAME if room is None else room
+    props = dict(d.props, in_next=0, written=len(plain), rflags=flags, uflags=UF_MSZIP_KWAJ | (UF_HARD_EOF if hard_eof else 0),
+                 blocks=list(d.blocks), never=never)
+    return Case(name, "kwaj_mszip", d.stream(pad=0) if stream is None else stream, room, plain=plain, err=err, props=props)
+
+
+def _history_builders():
+    """name -> (build(d), never): every history stream, for either framing"""
+    B = {}
+    for depth in (2, 7, 8, 9, 12, 40):
+        def chain(d, depth=depth):
+            _chain(d, _shrinking(depth), 1000 + depth)
+            assert _probe(d) == depth
+        B["shrinking_chain_depth_%d" % depth] = (chain, False)
+
+    def equal(d):
+        # equal lengths in a row: the newer frame shadows the older one -- at depth 3 and, below a long chain, in the ring
+        _chain(d, [FRAME, 30000, 30000, 28000, 28000, 28000] + [27000 - 900 * k for k in range(8)] + [9000, 9000], 1100)
+        assert _probe(d) == 12
+    B["equal_lengths_in_a_row"] = (equal, False)
+
+    def full_after(d):
+        # a full frame clears everything: the frame behind it reads through the linear path again (distances up to 32768)
+        _chain(d, _shrinking(12), 1200)
+        _probe(d, last=1)
+        _chain(d, [FRAME], 1250)
+        d.frame()
+        d.fixed([('M', 258, FRAME), ('L', _text(1251, 300)), ('M', 100, FRAME - 7), ('M', 50, 20), ('L', _text(1252, 4000))], last=1)
+        _chain(d, [3000], 1260)
+        assert _probe(d) == 3
+    B["full_block_after_a_deep_chain"] = (full_after, False)
+
+    def zero(d):
+        # a frame of 0 bytes is no level
+        ln = _shrinking(11)
+        _chain(d, ln[:5], 1300)
+        d.frame(); d.stored(b"", last=1)
+        _chain(d, ln[5:], 1310)
+        d.frame(); d.fixed([], last=1)
+        assert _probe(d) == 11
+    B["zero_byte_blocks_in_the_chain"] = (zero, False)
+
+    def across(d):
+        # single matches whose source run crosses a level boundary, and 32767 -> 0: from the two OLDEST frames (32768 and
+        # 32748 bytes: the first a full stack gives up) below ten more levels
+        _chain(d, [FRAME, FRAME - 20] + [30000 - 700 * k for k in range(10)], 1400)
+        d.frame()
+        d.fixed([('L', b"01234"),
+                 ('M', 100, 40),                      # periodic branch (distance 40 < 64, at 5 < 40): 32733..32767, then 0..4
+                 ('L', _text(1401, 95)),
+                 ('M', 258, FRAME - 32468),           # at 200, distance 300: 32668..32767 (over 32748), 0..157
+                 ('M', 64, 458 + FRAME - 29280),      # 29280..29343 crosses 29300 = L_4 (distance >= 64)
+                 ('M', 30, 522 + FRAME - 29985),      # 29985..30014 crosses 30000 = L_3
+                 ('L', b"."), ('M', 200, 63),         # periodic, inside the frame
+                 ('M', 258, 753 + FRAME - 32700)], last=1)
+        assert _probe(d) >= 12
+    B["matches_across_level_boundaries"] = (across, False)
+
+    def mixed(d):
+        _chain(d, _shrinking(13), 1500, kinds="sfym")
+        assert _probe(d) == 13
+    B["stored_fixed_dynamic_mixed_in_a_chain"] = (mixed, False)
+
+    def parsed(d):
+        # Huffman blocks only (what the parse waves of units with block tables take apart): two full blocks, ten levels, a probe,
+        # two full blocks again, then matches through the linear path and a probe
+        lit = flat_lengths(286, list(range(256)) + [256, 257 + 5, 257 + 28])
+        dst = flat_lengths(30, list(range(30)))
+
+        def huff(n, seed, dyn):
+            d.frame()
+            toks, left = [('L', _text(seed, 200))], n - 200
+            if len(d.blocks) > 1:
+                toks.append(('M', 8, FRAME - 100)); left -= 8
+            toks += [('M', 258, 200)] * (left // 258) + [('L', _text(seed + 1, left % 258))]
+            d.dynamic(toks, lit, dst, last=1) if dyn else d.fixed(toks, last=1)
+            assert d.blocks[-1] == n
+        for k, n in enumerate([FRAME, FRAME] + [12000 - 1000 * j for j in range(10)]):
+            huff(n, 1900 + 2 * k, k % 2)
+        assert _probe(d) == 11
+        huff(FRAME, 1950, 0); huff(FRAME, 1952, 1)
+        d.frame()
+        d.fixed([('M', 258, FRAME), ('L', _text(1954, 100)), ('M', 40, FRAME - 9), ('L', _text(1955, 900))], last=1)
+        assert _probe(d) == 2
+    B["huffman_blocks_only_full_blocks_around_a_chain"] = (parsed, False)
+
+    def never1(d):
+        _chain(d, [20000, 10000], 1600)
+        assert _probe(d, never=True) == 3
+    B["never_written_index_shallow"] = (never1, True)
+
+    def never2(d):
+        _chain(d, [30000 - 1500 * k for k in range(10)], 1610)
+        assert _probe(d, never=True) == 11
+    B["never_written_index_below_a_deep_chain"] = (never2, True)
+    return B
+
+
+NEVER_WRITTEN = ("never_written_index_shallow", "never_written_index_below_a_deep_chain")
+
+
+def mszip_history_cases():
+    C = []
+    for name, (build, never) in _history_builders().items():
+        d = Deflate()
+        build(d)
+        C.append(_hist_case("mszip_history_" + name, d, never=never))
+        if name.startswith("shrinking_chain"):
+            # the same chain with a request that ends inside it, and one that ends inside the probe frame (in_next, leftover)
+            k = len(d.blocks) - 2
+            C.append(_hist_case("mszip_history_%s_request_ends_in_the_chain" % name, d, out_len=sum(d.blocks[:k]) + d.blocks[k] // 3))
+            C.append(_hist_case("mszip_history_%s_request_ends_in_the_last_block" % name, d, out_len=len(d.plain) - 5))
+    # repair mode: a damaged frame in the middle of a deep chain is a zero-filled FULL frame -- it resets the history.  The
+    # damaged frame: literals, then code 286 (mszipd.c:246).  The next frame is found from the reference's stored state, at or
+    # behind the damaged frame's 'K' whatever the feeder's buffer size (in_chunk): no 'CK' in between
+    ln = _shrinking(12)
+    for name, flags, in_chunk in (("", UF_MSZIP_REPAIR, 0), ("_in_chunk_512", UF_MSZIP_REPAIR, 512),
+                                  ("_logged", UF_MSZIP_REPAIR | UF_MSZIP_LOG, 0)):
+        d = Deflate()
+        _chain(d, ln[:10], 1700)
+        d.frame()
+        at = len(d.out)
+        d.fixed([('L', _text(1701, 700)), ('M', 8, FRAME - 50), ('C', 286)], last=1)
+        d.byte_align()
+        assert b"CK" not in bytes(d.out[at:]) + b"C"
+        d._emit_many(bytes(FRAME - d.blocks[-1]))                 # (the repair: zeros up to a full frame)
+        _chain(d, [5000, 4000], 1710)
+        assert _probe(d) == 3
+        C.append(_hist_case("mszip_history_repair_in_a_deep_chain" + name, d, flags=flags, in_chunk=in_chunk))
+        C[-1].props["repaired"] = [(sum(d.blocks[:10]), FRAME - 708)]
+    return C
+
+
+def kwaj_mszip_cases():
+    C = []
+    for name, (build, never) in _history_builders().items():
+        d = Deflate(kwaj=True)
+        build(d)
+        d.end()
+        C.append(_kwaj_case("kwaj_mszip_history_" + name, d, never=never))
+
+    def three(d):
+        # (the last frame is a stored one: it reads no bit beyond its own end, also where the feeder fails there)
+        _chain(d, [FRAME, 9000, 2000], 1800, kinds="sfy")
+        _probe(d)
+        _chain(d, [300], 1805)
+    # terminator present / missing (clean EOF: the fabricated zero bytes read as length 0) / missing with a failing feeder
+    d = Deflate(kwaj=True); three(d); d.end()
+    C.append(_kwaj_case("kwaj_mszip_terminator", d))
+    d = Deflate(kwaj=True); three(d)
+    C.append(_kwaj_case("kwaj_mszip_no_terminator_clean_eof", d))
+    C.append(_kwaj_case("kwaj_mszip_no_terminator_hard_eof", d, err=ERR_READ, hard_eof=True))
+    # the input ends inside a frame header: one byte of the length word (the fabricated 0 completes it, the second one is no
+    # 'C'), behind the word, between 'C' and 'K'; with a failing feeder all three are read errors
+    base = d.stream(pad=0)
+    for what, tail in (("after_one_byte_of_the_length_word", b"\x10"), ("after_the_length_word", b"\x10\x00"),
+                       ("between_c_and_k", b"\x10\x00C")):
+        C.append(_kwaj_case("kwaj_mszip_eof_" + what, d, err=ERR_DATAFORMAT, stream=base + tail))
+        C.append(_kwaj_case("kwaj_mszip_hard_eof_" + what, d, err=ERR_READ, hard_eof=True, stream=base + tail))
+    # wrong 'C', wrong 'K': ERR_DATAFORMAT, the frames before are kept
+    for what, sig in (("c", b"cK"), ("k", b"CX")):
+        d = Deflate(kwaj=True); three(d)
+        keep = bytes(d.plain)
+        d.frame(sig=sig); d.stored(b"never decoded", last=1); d.end()
+        C.append(_kwaj_case("kwaj_mszip_wrong_" + what, d, err=ERR_DATAFORMAT, plain=keep))
+    # length words that lie: only 0 matters
+    d = Deflate(kwaj=True)
+    for k, word in enumerate((1, 0xFFFF, 2, 0x8000)):
+        d.frame(word=word); d.stored(_rb(1810 + k, 5000 - 1000 * k), last=1)
+    _probe(d); d.end()
+    C.append(_kwaj_case("kwaj_mszip_length_words_that_lie", d))
+    # bytes behind the terminator are ignored
+    d = Deflate(kwaj=True); three(d); d.end()
+    C.append(_kwaj_case("kwaj_mszip_bytes_behind_the_terminator", d, stream=d.stream(pad=0) + b"\x05\x00CK" + _rb(1820, 40)))
+    # an inflate error in frame 3 of 5: two frames written
+    d = Deflate(kwaj=True)
+    _chain(d, [FRAME, 6000], 1830)
+    keep = bytes(d.plain)
+    d.frame(); d.fixed([('L', _text(1831, 300)), ('C', 286)], last=1)
+    _chain(d, [500, 400], 1832); d.end()
+    C.append(_kwaj_case("kwaj_mszip_inflate_error_in_frame_3_of_5", d, err=ERR_DECRUNCH, plain=keep))
+    # a frame of more than 32768 bytes
+    d = Deflate(kwaj=True)
+    _chain(d, [4000], 1840)
+    keep = bytes(d.plain)
+    d.frame(); d.stored(_rb(1841, 30000), last=0); d.fixed([('L', _text(1842, 2768)), ('M', 10, 5)], last=1); d.end()
+    C.append(_kwaj_case("kwaj_mszip_frame_of_more_than_32768_bytes", d, err=ERR_DECRUNCH, plain=keep))
+    # a frame of 0 bytes
+    d = Deflate(kwaj=True)
+    _chain(d, [7000], 1850)
+    d.frame(); d.stored(b"", last=1)
+    _chain(d, [300], 1851); _probe(d); d.end()
+    C.append(_kwaj_case("kwaj_mszip_frame_of_0_bytes", d))
+    # room: a frame is started only with 32768 bytes of room left (MSPACK_HIP_F_OUT_FULL, out_len = what fitted)
+    k = 2
+    for nb in (k, k + 1):
+        d = Deflate(kwaj=True)
+        _chain(d, [FRAME] * nb, 1860, kinds="sf"); d.end()
+        for room, fit in ((k * FRAME, k), (k * FRAME + FRAME - 1, k), (k * FRAME - 1, k - 1)):
+            full = fit < nb
+            C.append(_kwaj_case("kwaj_mszip_%d_frames_room_%d" % (nb, room), d, room=room, flags=F_OUT_FULL if full else 0,
+                                plain=d.plain[:min(fit, nb) * FRAME]))
     return C
 
 

@@ -10,7 +10,7 @@
  * (ignored: the oracle is serial), the feeder's failed read (MSPACK_HIP_UF_HARD_EOF), Quantum's good_len and marks
  * (MSPACK_HIP_UF_QTM_MARKS), LZX DELTA units (OAB
  * blocks with their reference data), LZSS and KWAJ LZH units, checksum units;
- * NOT MSZIP repair mode or KWAJ-framed MSZIP -- that makes the call fail, and the tests that need it run on the GPU.  The `-m gpu` parity tests never
+ * NOT MSZIP repair mode -- that makes the call fail, and the tests that need it run on the GPU.  The `-m gpu` parity tests never
  * see this file: they load the real library. */
 #include <stdio.h>
 #include <string.h>
@@ -48,6 +48,7 @@ int mspack_standin_decode_units(const mspack_hip_unit *units, const uint32_t *or
     }
     /* the frame table is a hint for the GPU's frame-parallel parse; results do not depend on it */
     if (u->flags & ~(MSPACK_HIP_UF_FRAME_TABLE | MSPACK_HIP_UF_HARD_EOF | (u->kind == MSPACK_HIP_KIND_LZX ? MSPACK_HIP_UF_LZX_LOG : 0u) |
+                     (u->kind == MSPACK_HIP_KIND_MSZIP ? MSPACK_HIP_UF_MSZIP_KWAJ : 0u) |
                      (u->kind == MSPACK_HIP_KIND_QUANTUM ? MSPACK_HIP_UF_QTM_MARKS : 0u))) { snprintf(g_err, sizeof(g_err), "stand-in: unit flags 0x%x unsupported", u->flags); return -1; }
     if (u->kind == 0) { r->err = 1; continue; }
     if (u->kind == MSPACK_HIP_KIND_XORSUM) {                     /* a CFDATA block's checksum (cabd.c:1462-1479) */
@@ -73,7 +74,8 @@ int mspack_standin_decode_units(const mspack_hip_unit *units, const uint32_t *or
       break;
     case MSPACK_HIP_KIND_MSZIP:
       /* (an MSZIP unit owns 32 KiB of room behind out_len: what its last block inflated to beyond the request lands there) */
-      oracle_mszip_decode(src, u->in_len, dst, (size_t) u->out_len + 32768, u->out_len, 0, NULL, 0, NULL, &o);
+      if (u->flags & MSPACK_HIP_UF_MSZIP_KWAJ) oracle_mszip_kwaj_decode(src, u->in_len, dst, (size_t) u->out_len + 32768, u->out_len, &o);   /* (out_len = room) */
+      else oracle_mszip_decode(src, u->in_len, dst, (size_t) u->out_len + 32768, u->out_len, 0, NULL, 0, NULL, &o);
       break;
     case MSPACK_HIP_KIND_QUANTUM:
       if ((u->flags & MSPACK_HIP_UF_QTM_MARKS) && u->ref_len) {  /* the unit's marks and their log (mspack_hip.h) */

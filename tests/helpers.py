@@ -174,6 +174,21 @@ def oracle_mszip(data, out_bytes, repair=0):
     return res.err, buf.raw[:min(res.out_len, out_bytes)], res, list(lens[:nb.value])
 
 
+F_OUT_FULL = 8
+
+
+def oracle_mszip_kwaj(data, room, cap=None):
+    """KWAJ-framed MSZIP (mszipd_decompress_kwaj) into `room` bytes: a block is started only with 32768 bytes of room left,
+    else F_OUT_FULL -> (err, bytes, OracleResult)"""
+    cap = int(room) if cap is None else cap
+    buf = C.create_string_buffer(max(cap, 1))
+    res = OracleResult()
+    f = oracle().oracle_mszip_kwaj_decode
+    f.argtypes = [C.c_char_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint64, C.POINTER(OracleResult)]
+    f(bytes(data), len(data), buf, cap, int(room), C.byref(res))
+    return res.err, buf.raw[:min(res.out_len, cap)], res
+
+
 def oracle_qtm(data, out_bytes, window_bits):
     buf = C.create_string_buffer(max(int(out_bytes), 1))
     res = OracleResult()

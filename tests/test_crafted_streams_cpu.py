@@ -500,3 +500,45 @@ def test_crafted_streams_on_the_wavefront_emulator(built, tmp_path):
     env = dict(os.environ, MSPACK_HIP_SO=so)
     p = subprocess.run([sys.executable, str(script)], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=3000)
     assert p.returncode == 0 and b"EMU_CRAFTED_OK" in p.stdout, p.stdout.decode()[-3000:]
+
+
+# ---- MSZIP window history at any depth, KWAJ framing (CS.mszip_history_cases, CS.kwaj_mszip_cases) ----------------------
+HISTORY = CS.mszip_history_cases()
+KWAJ_MSZIP = CS.kwaj_mszip_cases()
+
+
+def run_history_oracle(c):
+    """-> (err, bytes, result) of the oracle for a history / KWAJ case as the unit is given to the kernels"""
+    from helpers import oracle_mszip_kwaj, oracle_set_hard_eof
+    if c.codec == "kwaj_mszip":
+        oracle_set_hard_eof(bool(c.props["uflags"] & CS.UF_HARD_EOF))
+        try:
+            return oracle_mszip_kwaj(c.stream, c.out_len)
+        finally:
+            oracle_set_hard_eof(0)
+    repair = (c.props["in_chunk"] or 1) if c.props["uflags"] & CS.UF_MSZIP_REPAIR else 0
+    return oracle_mszip(c.stream, c.out_len, repair)[:3]
+
+
+def test_history_case_lists():
+    names = [c.name for c in HISTORY + KWAJ_MSZIP]
+    assert len(set(names)) == len(names) and not set(names) & {c.name for c in CASES}
+    for c in HISTORY + KWAJ_MSZIP:
+        assert len(c.props["blocks"]) <= 45 and sum(c.props["blocks"]) <= 1536 * 1024, c.name
+        # window bytes no frame wrote (the reference reads uninitialised memory there): the two named streams only
+        assert bool(c.props.get("never_written_reads")) == c.props["never"] == any(n in c.name for n in CS.NEVER_WRITTEN), c.name
+    for depth in (2, 7, 8, 9, 12, 40):
+        for head in ("mszip_history_", "kwaj_mszip_history_"):
+            c = next(c for c in HISTORY + KWAJ_MSZIP if c.name == head + "shrinking_chain_depth_%d" % depth)
+            chain = c.props["blocks"][:-1]
+            assert len(chain) == depth and all(a > b for a, b in zip(chain, chain[1:])), c.name
+    assert sum("deep" in c.name or "depth" in c.name for c in HISTORY) >= 20 and CS.ZIP_HIST == 8
+
+
+@pytest.mark.parametrize("c", HISTORY + KWAJ_MSZIP, ids=[c.name for c in HISTORY + KWAJ_MSZIP])
+def test_history_model_equals_the_oracle(built, c):
+    """error, flags, bytes written, in_next and every byte: the generator's own ring against the oracle's"""
+    e, o, r = run_history_oracle(c)
+    assert e == c.err and r.out_len == c.props["written"] == len(c.plain), (e, c.err, r.out_len, c.props["written"])
+    assert r.in_next == c.props["in_next"] and r.flags == c.props.get("rflags", 0), (r.in_next, r.flags)
+    assert o == c.plain, "differs at byte %d" % next(k for k in range(len(o)) if o[k] != c.plain[k])

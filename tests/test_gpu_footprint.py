@@ -463,3 +463,23 @@ def test_device_resident_entry(built):
     for f in ("err", "out_len", "good_len", "in_next"):
         assert np.array_equal(res[f], res2[f]), f
     assert np.array_equal(image[~mask], image2[~mask])
+
+
+def test_mszip_deep_chains_stay_in_their_regions(built):
+    """MSZIP units whose window history is deeper than the kernel's stack decode in a ring in their own slack
+    (mszip_kernel.hpp): two such CAB-framed units (one of them with a request that ends inside its last block) and a
+    KWAJ-framed one, back to back in a device buffer full of 0xA5 -- every unit's bytes are the oracle's, and outside
+    [out_off, out_off + out_len + 32768) of each unit no byte has changed."""
+    import test_gpu_mszip_history as H
+    names = ("mszip_history_shrinking_chain_depth_12", "mszip_history_shrinking_chain_depth_40_request_ends_in_the_last_block",
+             "kwaj_mszip_history_shrinking_chain_depth_12")
+    items = [(next(c for c in H.cases() if c.name == n), False) for n in names]
+    units, arena, out_bytes = H.batch(items)
+    from test_gpu_crafted import to_device
+    out, res = to_device(units, arena, out_bytes)
+    H.check(items, units, out, res, "footprint")
+    owned = np.zeros(out_bytes, dtype=bool)
+    for i, (c, _t) in enumerate(items):
+        oo = int(units["out_off"][i])
+        owned[oo:oo + c.out_len + 32768] = True
+    assert (out[~owned] == H.FILL).all(), "a byte outside the units' regions changed: %d" % int(np.flatnonzero((out != H.FILL) & ~owned)[0])

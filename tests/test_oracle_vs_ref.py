@@ -329,3 +329,48 @@ def test_lzx_open_block_at_reset_warning_vs_reference(built):
         assert (oe, ob) == (re_, rb), seed
         assert (cnt > 0) == (len(said) > 0) and len(said) <= 1, (seed, cnt, said)
         assert frames == sorted((fr // rf + 1) * rf for fr in patches), (seed, frames)
+
+
+def _history_cases():
+    import crafted_streams as CS
+    return CS.mszip_history_cases(), CS.kwaj_mszip_cases()
+
+
+def test_mszip_history_cases_oracle_vs_reference(built):
+    """the deep-history streams (CAB framing) through the real mszipd: error, bytes written, every byte.  The two streams that
+    read window bytes no frame wrote are left out: the reference reads uninitialised memory there."""
+    import crafted_streams as CS
+    left_out = 0
+    for c in _history_cases()[0]:
+        if c.props["never"]:
+            left_out += 1
+            continue
+        repair = (c.props["in_chunk"] or 1) if c.props["uflags"] & CS.UF_MSZIP_REPAIR else 0
+        e1, o1, w1 = ref_mszip(c.stream, c.out_len, repair)
+        e2, o2, r, _ = oracle_mszip(c.stream, c.out_len, repair)
+        assert (e1, w1) == (e2, r.out_len) and o1 == o2 == c.plain, (c.name, e1, w1, e2, r.out_len)
+    assert left_out == 2
+
+
+def test_mszip_kwaj_oracle_vs_reference(built):
+    """oracle_mszip_kwaj_decode against the real kwajd (method 4) on every KWAJ case: error code and every byte written -- a
+    failing stream has written the frames before the failure.  The real driver has neither a failing feeder nor a room: the
+    cases that differ only in those are the same file, compared once with ample room."""
+    from helpers import oracle_mszip_kwaj, ref_szdd_kwaj
+    import crafted_streams as CS
+    seen, left_out = set(), 0
+    for c in _history_cases()[1]:
+        if c.props["never"]:
+            left_out += 1
+            continue
+        if c.stream in seen:
+            continue
+        seen.add(c.stream)
+        total = sum(c.props["blocks"])
+        g = ref_szdd_kwaj(1, CS.kwaj_container(c.stream, 4, total))
+        e, o, r = oracle_mszip_kwaj(c.stream, total + 65536)
+        assert g["open_err"] == 0 and g["comp_type"] == 4, c.name
+        assert (g["err"], len(g["data"])) == (e, r.out_len) and g["data"] == o, (c.name, g["err"], e, len(g["data"]), r.out_len)
+        if not (c.props["uflags"] & CS.UF_HARD_EOF) and c.out_len >= total + 32768:
+            assert e == c.err and o == c.plain, c.name
+    assert left_out == 2 and len(seen) >= 25

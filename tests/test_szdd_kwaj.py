@@ -130,14 +130,14 @@ def test_files_vs_reference(built, name):
     check_file(name)
 
 
-# (KWAJ-framed MSZIP needs mszipd_decompress_kwaj, which the stand-in's oracle does not restate: those files stay on the GPU)
-CPU_FILES = [n for n in sorted(G) if n != "kwaj_m4" and "mszip" not in n]      # (KWAJ method 4 = MSZIP)
+# (KWAJ method 4 = MSZIP as mszipd_decompress_kwaj frames it: the stand-in decodes it with the oracle's KWAJ mode)
+CPU_FILES = sorted(G)
 
 
 @pytest.mark.parametrize("name", CPU_FILES)
 def test_files_vs_reference_host_logic_cpu(built, hostlogic, name):
-    """the same goldens through the same driver code (csrc/host/szdd_kwaj.c) on the CPU stand-in for the batch ABI (LZSS / LZH
-    units decoded by the oracle): header parsing, the one-unit batch, room handling -- host logic only"""
+    """the same goldens through the same driver code (csrc/host/szdd_kwaj.c) on the CPU stand-in for the batch ABI (LZSS / LZH /
+    KWAJ-framed MSZIP units decoded by the oracle): header parsing, the one-unit batch, room handling -- host logic only"""
     check_file(name, L=hostlogic)
 
 
@@ -195,3 +195,53 @@ def test_crafted_files_vs_reference(built, name):
 @pytest.mark.parametrize("name", sorted(GC))
 def test_crafted_files_vs_reference_host_logic_cpu(built, hostlogic, name):
     check_crafted_file(name, L=hostlogic)
+
+
+# ---- files around the hand-built KWAJ-framed MSZIP streams (crafted_streams.kwaj_mszip_cases) ------------------------------------
+def kwaj_mszip_file_cases():
+    """-> [(name, file bytes, err, bytes written)]: every stream of CS.kwaj_mszip_cases() as a KWAJ file of method 4 -- the deep
+    window histories and the framing's edges (terminator, ends of the input inside a frame header, wrong 'C' / 'K', length words
+    that lie, an inflate error in frame 3 of 5, frames of 0 and of more than 32768 bytes) -- once with the length it gives, once
+    with a header that states 1 byte and once with none (extract()'s own unit runs out of room: MSPACK_HIP_F_OUT_FULL, the room
+    grown and the unit run again).  Expected: the oracle's KWAJ mode, which tests/test_oracle_vs_ref.py holds against the real
+    kwajd on the same streams; a failing stream has written the frames before the failure."""
+    import crafted_streams as CS
+    from helpers import oracle_mszip_kwaj
+    seen, out = set(), []
+    for c in CS.kwaj_mszip_cases():
+        if c.stream in seen or c.props["uflags"] & CS.UF_HARD_EOF:      # (a failing feeder is the batch ABI's business, not a file's)
+            continue
+        seen.add(c.stream)
+        total = sum(c.props["blocks"])
+        e, o, _r = oracle_mszip_kwaj(c.stream, total + 65536)
+        out.append((c.name, CS.kwaj_container(c.stream, 4, total), e, o))
+        out.append((c.name + "/length_1", CS.kwaj_container(c.stream, 4, 1), e, o))
+        out.append((c.name + "/no_length", b"KWAJ\x88\xF0\x27\xD1" + (4).to_bytes(2, "little") + (14).to_bytes(2, "little") + bytes(2) + c.stream, e, o))
+    return out
+
+
+_KM = []
+
+
+def kwaj_mszip_files():
+    if not _KM:
+        _KM.extend(kwaj_mszip_file_cases())
+    return _KM
+
+
+def check_kwaj_mszip_files(L=None):
+    files = kwaj_mszip_files()
+    assert len(files) >= 75
+    for name, blob, e, o in files:
+        r = api.szdd_kwaj_extract(1, blob, L=L)
+        assert r["open_err"] == 0 and r["comp_type"] == 4, name
+        assert r["err"] == e and len(r["data"]) == len(o) and r["data"] == o, (name, r["err"], e, len(r["data"]), len(o))
+
+
+def test_kwaj_mszip_files_host_logic_cpu(built, hostlogic):
+    check_kwaj_mszip_files(hostlogic)
+
+
+@pytest.mark.gpu
+def test_kwaj_mszip_files(built):
+    check_kwaj_mszip_files()

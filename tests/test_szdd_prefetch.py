@@ -231,3 +231,59 @@ def test_a_read_that_fails(built, hostlogic, kind):
         if batchable(s, bad):
             assert COUNTS[kind](L=L)[1:] == (n_b - 1, 0)
         assert list(s.messages) == want_msgs
+
+
+def kwaj_mszip_files():
+    """the KWAJ-framed MSZIP streams of CS.kwaj_mszip_cases() as files (method 4), each once with the length it gives and once with a
+    header that states 1 byte (the member does not fit its room: MSPACK_HIP_F_OUT_FULL, decoded again alone with the room grown)
+    -> [(name, blob, err, bytes written -- also in front of a failure)] from the oracle"""
+    from helpers import oracle_mszip_kwaj
+    seen, out = set(), []
+    for c in CS.kwaj_mszip_cases():
+        if c.stream in seen or c.props["uflags"] & CS.UF_HARD_EOF:
+            continue
+        seen.add(c.stream)
+        total = sum(c.props["blocks"])
+        e, o, _r = oracle_mszip_kwaj(c.stream, total + 65536)
+        out.append((c.name, CS.kwaj_container(c.stream, 4, total), e, o))
+        out.append((c.name + "/length_1", CS.kwaj_container(c.stream, 4, 1), e, o))
+    return out
+
+
+def check_kwaj_mszip_files(L):
+    files = kwaj_mszip_files()
+    assert len(files) >= 50
+    api.kwaj_batch_counts(reset=True, L=L)
+    with api.KwajSet([f[1] for f in files], L=L) as s:
+        assert s.prefetch() == ERR_OK and s.last_error() == ERR_OK
+        assert api.kwaj_batch_counts(L=L)[0] == 1
+        for k in np.random.default_rng(11).permutation(len(files)):
+            name, _blob, e, o = files[k]
+            r = s.extract(int(k))
+            assert r["open_err"] == 0 and r["err"] == e and r["data"] == o, (name, r["err"], e, len(r["data"]), len(o))
+    _b, c1, c2 = api.kwaj_batch_counts(L=L)
+    # which members did not fit the room the batch gave them is decided by the streams: the room is the stated length in whole
+    # blocks (sk_prefetch, csrc/host/szdd_kwaj.c; the worst case where the header states more than that), and a frame is started
+    # only with 32768 bytes of it left -- the oracle says for which streams that ends in MSPACK_HIP_F_OUT_FULL.  Exactly those
+    # are decoded again alone, every other one is answered from the batch
+    from helpers import oracle_mszip_kwaj, F_OUT_FULL
+    refits = 0
+    for _name, blob, _e, _o in files:
+        stream, stated = blob[18:], int.from_bytes(blob[14:18], "little")
+        worst = (len(stream) * 8 + 65536 + 32767) & ~32767
+        room = ((stated if 0 < stated <= worst else worst) + 32767) & ~32767
+        refits += bool(oracle_mszip_kwaj(stream, room, cap=1)[2].flags & F_OUT_FULL)
+    assert refits >= len(files) // 2 and (c1, c2) == (len(files) - refits, refits), (c1, c2, refits, len(files))
+    # extract() without a prefetch: the driver's own unit, refitted the same way
+    for name, blob, e, o in files:
+        r = api.szdd_kwaj_extract(1, blob, L=L)
+        assert r["open_err"] == 0 and r["err"] == e and r["data"] == o, (name, r["err"], e)
+
+
+def test_kwaj_mszip_files_host_logic_cpu(built, hostlogic):
+    check_kwaj_mszip_files(hostlogic)
+
+
+@pytest.mark.gpu
+def test_kwaj_mszip_files_gpu(built):
+    check_kwaj_mszip_files(None)
