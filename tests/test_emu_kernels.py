@@ -215,6 +215,38 @@ def test_hand_built_folders_through_the_fold_tasks_on_the_emulator(built, tmp_pa
         assert "WORDS %s\n" % " ".join(str(f) for f in sorted(c.folds)) in s, (c.name, s[-300:])
 
 
+@pytest.mark.skipif(not os.path.exists(CLANG), reason="the emulator build needs ROCm's clang++")
+def test_uniform_launches_with_damaged_and_crafted_units_on_the_emulator(built, tmp_path):
+    """tests/test_gpu_lzx_uniform.py's twin: uniform launches of mspack_lzx_pipe -- a frame's parse and resolve tasks are tickets of
+    different waves -- over the two-frame hand-built cases (k = 1: 8 units, one of them failing; the host entry) and twelve corpus
+    units of two frames, one per damage kind (emu_batches; the device-resident entry between guard bytes), with that module's checks:
+    the oracle's err, out_len, in_next, flags and bytes, and the frame words' path evidence.  Parse waves pause behind what they
+    publish (MSPACK_EMU_PUBLISH_DELAY_US), and the launch has 32 waves (MSPACK_EMU_CUS=8): a frame's parse task runs beside the
+    parse task of the frame below, so headers are read ahead of the chain (lzx_pipe_task_spec) above frames that then fail, and the
+    crafted batch's 32 tickets all find a wave, so its resolve tasks take frames up while they are parsed -- both must be seen in
+    the trace.  Once with the environment as it is and once per MSPACK_HIP_TICKET_ORDER value, a fresh process each; every run's
+    results must equal the first's.  A child that fails or runs into its time limit fails the test, and no further child is started.
+    Wall time on 8 CPUs, both within one run of the whole suite: test_kernels_on_the_wavefront_emulator 13.7 s, this test 19.1 s
+    (alone, with the session's build checks: 15.3 s and 27 s; with k = 2 and both entries for both batches it took 42 s).
+    Mutation check (scratch copies, emulator only; nothing of it is kept): (1) lzx_pipe_resolve makes no difference between
+    LZX_ST_FAILED and LZX_ST_HDRONLY -- both end the chain --, so the mutation was applied where the difference lives, the parse
+    chain taking a FAILED frame below for one that published its code lengths: this test fails in all four environments on the frame
+    words (a frame behind a FAILED one is HDRONLY); with lzx_pipe_resolve taking a FAILED frame's record for a finished one it fails
+    on the first crafted unit's error code.  (2) the speculative header kept when the frame below fails: fails in all four
+    environments on the frame words -- with MSPACK_EMU_CUS=8 only; with the emulator's default of 4 waves no header was read ahead
+    above a failing frame and the mutant passed."""
+    import test_gpu_lzx_uniform as U
+    so = emu_so()
+    names = U.write_batches(str(tmp_path), U.emu_batches())
+    first, text = None, []
+    extra = dict(MSPACK_HIP_SO=so, MSPACK_EMU_PUBLISH_DELAY_US="3000", MSPACK_EMU_CUS="8", MSPACK_EMU_SPEC_TRACE="1", MSPACK_EMU_STREAM_TRACE="1")
+    for env_name, env in [U.ENVS[0]] + [e for e in U.ENVS if list(e[1]) == ["MSPACK_HIP_TICKET_ORDER"]]:
+        got = U.start_child(str(tmp_path), names, env_name, env, 600, extra, text)
+        first = first or got
+        assert got == first, (env_name, "differs from the first environment's run")
+    assert "header read ahead of the chain" in "".join(text) and "records in while the frame is parsed" in "".join(text)
+
+
 STREAM_WORKER = r'''
 import sys
 sys.path.insert(0, %r); sys.path.insert(0, %r + "/tests")

@@ -2,7 +2,8 @@
 with and without their frame tables -- against the oracle (error, out_len, in_next, flags without FRAMES_ADOPTED, every byte
 up to out_len) and against the helper's own plaintext; the multi-frame cases with one block per frame must really take the
 frame-parallel path.  Then every valid LZX case 600 times in one batch with its frame table, so that the pipe's tickets no
-longer all find a wave at once (the speculative header path and the other ticket orders run): ~16 000 units, ~900 MB of
+longer all find a wave at once (frame-slot order -- the cases' frame counts differ, so the launch is not uniform --, speculative
+headers, more slots than waves; the ticket orders of uniform launches are tests/test_gpu_lzx_uniform.py's): ~16 000 units, ~900 MB of
 output, 2.5 s on an MI355X.  The Quantum cases go in three times each -- in_len exact, in_len extended over 160 zero bytes
 (the lean reader), exact with a failing feeder -- and in_used and good_len are held against the oracle too; then every valid
 one 200 times in one batch, every third unit with marks (wall time of the Quantum tests on an MI355X: not measured yet).
@@ -240,7 +241,12 @@ def test_crafted_streams_vs_oracle(built):
 
 
 def test_valid_lzx_cases_600_times_in_one_batch(built):
-    """(the 600 units of a case share one copy of its stream and its table in the arena)"""
+    """(the 600 units of a case share one copy of its stream and its table in the arena)
+    What this batch runs: its cases have 1, 2, 3, 4 and 6 frames, so the launch is NOT uniform (entry_kernels.hpp: Fmin != Fmax, F == 0)
+    and the ticket order is never consulted -- frame-slot order, one ticket per frame slot, parse and resolve by the same wave, with
+    many more slots than the launch has waves, and headers read ahead of the chain (lzx_pipe_task_spec) wherever a frame's task
+    starts before the frame below has published.  The three ticket orders of uniform launches, with hand-built, damaged and
+    other-mode units in them, are tests/test_gpu_lzx_uniform.py's."""
     cases = [c for c in CS.lzx_cases() if c.err == 0]
     n = 600
     offs, toffs, pos = [], [], 0
