@@ -178,6 +178,10 @@ struct mscabd_file {
                                             digest units for, per file, for mspack_cabd_digest() (0, 16, 32 or 48, default 0; other
                                             values: MSPACK_ERR_ARGS).  Read where MSCABD_PARAM_HIP_DIGESTS is read; that one keeps
                                             taking 0 to 7 only */
+#define MSCABD_PARAM_HIP_STORED   (107)  /* 1: stored ("not compressed") folders are gathered into the batches like compressed ones -- one
+                                            MSPACK_HIP_KIND_STORED unit each, their CFDATA checksums verified on the device, their files
+                                            in the digest plan -- and served from them (0 or 1, default 0; other values:
+                                            MSPACK_ERR_ARGS).  Read when a batch is built.  See mspack_cabd_stored_counts() */
 /* digest algorithms (mspack_cabd_digest, MSCABD_PARAM_HIP_DIGESTS, MSCABD_PARAM_HIP_DIGESTS64) */
 #define MSPACK_DIGEST_MD5     (1)        /* RFC 1321, 16 bytes */
 #define MSPACK_DIGEST_SHA1    (2)        /* FIPS 180-4, 20 bytes */
@@ -207,7 +211,7 @@ struct mscab_decompressor {
  *   cabs[i]   cabinets this decompressor opened or found with search().  A member of a set joined with append() / prepend()
  *             stands for the set's folder list; an entry given twice, or two members of one set, are harmless, and so are
  *             folders that are decoded already or part of a batch that is still running.
- *   folders   stored folders are streamed as ever and are left out, as are folders continued from a cabinet that is not
+ *   folders   stored folders are streamed as ever and are left out (unless MSCABD_PARAM_HIP_STORED is 1), as are folders continued from a cabinet that is not
  *             joined; a folder whose cabinet file cannot be opened stays undecoded, and its extract() reports that.
  *             Folders are taken in argument order, then in list order, while their estimated decoded size (32 KiB per CFDATA
  *             block) fits MSCABD_PARAM_HIP_CACHE_MB; the others are decoded on demand by extract().
@@ -280,6 +284,28 @@ extern int mspack_cabd_crc32(struct mscab_decompressor *self, struct mscabd_file
 /* diagnostics: successful mspack_cabd_crc32() calls of this process answered from the device (counts[0]) / computed on the host
  * (counts[1]); counts may be NULL; reset != 0 clears them after reading */
 extern void mspack_cabd_crc32_counts(unsigned long long counts[2], int reset);
+/* Stored folders (CAB method 0) in the batches: MSCABD_PARAM_HIP_STORED.  With 0 -- or a batch provider without
+ * mspack_hip_features() / MSPACK_HIP_FEAT_STORED -- a stored folder is streamed as the reference streams it: one sys->seek + sys->read
+ * stream per extract(), its checksums verified and its files hashed on the host, no part in mspack_cabd_prefetch().  With 1 a stored
+ * folder is gathered like a compressed one by its cabinet's first extract() / md5() / digest() / crc32() and by mspack_cabd_prefetch():
+ * its CFDATA payloads are read into the batch's input arena, one MSPACK_HIP_KIND_STORED unit puts them into the folder's place in the
+ * output arena, its block parts get the checksum units compressed folders get, its files are counted into the digest plan
+ * (MSCABD_PARAM_HIP_MD5 / _DIGESTS / _DIGESTS64 / _HIP_CRC32), it counts against MSCABD_PARAM_HIP_CACHE_MB by its bytes, and the batch
+ * runs as a job under the usual conditions.
+ * The streamed state machine stays the authority on everything that is not a clean folder: a stored folder is served from the batch
+ * only if its unit answered 0, every block read succeeded, every block has cbData == cbUncomp, every checksum matched (or was 0 in the
+ * header: the reference skips those), the folder is one the gather takes (not continued from a cabinet that is not joined) and
+ * MSCABD_PARAM_SALVAGE is off.  Otherwise its bytes are dropped and every call on it is streamed as with 0 -- also a call for a file
+ * in front of the folder's only bad block -- so codes, partial writes and messages of damaged folders are those of the streamed path,
+ * not restatements of them.  A file that reaches past the folder's bytes is streamed too.  A served extract() writes the file's slice
+ * with the open / write / close calls of the compressed path (runs of 32 KiB); what it returns, what a later call returns and what
+ * last_error() says are what they are with 0.
+ * The bytes take a detour through the device: extract() of one cabinet is not faster with 1 (README: the measurements).  The param
+ * is for callers that want digests or checksums of stored files from the device, and for mspack_cabd_prefetch() over many small
+ * cabinets.
+ * diagnostics: stored folders of this process that were served from a batch (counts[0]) / that were streamed while the param was 1
+ * (counts[1]), each folder once per way; counts may be NULL; reset != 0 clears them after reading. */
+extern void mspack_cabd_stored_counts(unsigned long long counts[2], int reset);
 /* the value set_param() last stored for a parameter (the defaults before that); MSCABD_PARAM_HIP_MD5 answers bit 1 of
  * MSCABD_PARAM_HIP_DIGESTS.  MSPACK_ERR_ARGS for an unknown parameter or a NULL argument. */
 extern int mspack_cabd_get_param(struct mscab_decompressor *self, int param, int *value);

@@ -63,7 +63,31 @@ extern "C" {
                                        alone) are unspecified there, and so is a digest over them (err is still 0).  One lane per range (MD5 is one chain per message): the device wins
                                        with many ranges at once.  Ask mspack_hip_features() & MSPACK_HIP_FEAT_MD5 first       */
 
-/* Kinds 9 to 15 are not defined (an entry point that meets one answers "unknown kind"); digests other than MD5 are numbered from 16. */
+/* Kinds 9, 10 and 12 to 15 are not defined (an entry point that meets one answers "unknown kind"); digests other than MD5 are numbered from 16. */
+#define MSPACK_HIP_KIND_STORED  11   /* CAB method 0, "not compressed" (noned_decompress, cabd.c:1500-1542) -- the one CAB method whose number is not
+                                       its kind's: the unit copies min(in_len, out_len) bytes from [in_off, ...) of the input arena to
+                                       [out_off, ...) of the output arena.  in_off and out_off may have any alignment, out_len is 0 to
+                                       2^32-1.  No byte outside [out_off, out_off + min(in_len, out_len)) is written: no slack, nothing
+                                       below out_off -- neighbouring units may lie against it on both sides.  No byte outside [in_off,
+                                       in_off + in_len) is relied on (aligned reads may touch up to 7 bytes next to them: the arena's
+                                       8 bytes of slack).  window_bits, reset_frames, e8_base, ref_len, in_chunk and frame_base are
+                                       ignored.  MSPACK_HIP_UF_CRC32 is honoured as for kinds 1 to 6 (the digest of the first
+                                       result.out_len bytes in in_used); MSPACK_HIP_UF_HARD_EOF and every other flag are ignored: there
+                                       is no bit reader, so no fabricated zero bytes.  Result:
+                                         in_len >= out_len   err 0, out_len = good_len = in_used = unit.out_len, flags 0, in_next 0
+                                         in_len <  out_len   err MSPACK_ERR_READ, out_len = good_len = in_used = in_len, flags 0, in_next 0
+                                       The second case is a feeder that ran dry: every byte it had was copied.  The reference writes in
+                                       runs of its buffer size before a read fails, so how many bytes reach a file before such a
+                                       failure is the DRIVER's business, not the unit's (the cabinet driver serves only folders whose
+                                       unit answered 0).  A unit that leaves either arena answers MSPACK_ERR_ARGS with the other words 0
+                                       and nothing of it is read or written; the host entry points refuse such a batch before anything
+                                       touches the device (mspack_hip_last_error() names the unit).  In every other respect a decoding
+                                       unit: digest units may range over its region, the host entry points cut chunks through stored
+                                       units (their weight is their bytes), _multi shards them, mspack_hip_job_wait_unit() waits for
+                                       them.  A folder is 0 bytes to 2 GiB: a unit is cut into 64 KiB segments and the segments of all
+                                       stored units of a launch are one pool of work -- one 2 GiB folder spreads over the chip.
+                                       Ask mspack_hip_features() & MSPACK_HIP_FEAT_STORED first                                   */
+
 #define MSPACK_HIP_KIND_SHA1    16   /* a digest unit like MSPACK_HIP_KIND_MD5, every convention of it (the range [out_off, out_off + out_len) of the
                                        OUTPUT arena behind all decoding, in_len 0, MSPACK_HIP_UF_CRC32 rejected, overlapping ranges,
                                        the arena only read, which bytes "lie there" per entry point, err 0 and flags 0): the SHA-1
@@ -178,7 +202,7 @@ extern "C" {
                                            CFDATA block, cabd.c:1322-1324): ERR_READ at once, without the
                                            two fabricated zero bytes of a clean EOF (readbits.h:194-208) */
 
-#define MSPACK_HIP_UF_CRC32       128u  /* every decoding kind (1 to 6): result.in_used carries a digest of the first result.out_len bytes of
+#define MSPACK_HIP_UF_CRC32       128u  /* every decoding kind (1 to 6, and 11): result.in_used carries a digest of the first result.out_len bytes of
                                            the unit's output region instead of the diagnostic byte count -- CRC-32, reflected polynomial
                                            0xEDB88320, register started at 0xFFFFFFFF and NOT inverted at the end (the OAB block check,
                                            crc32.h / oabd.c:88-100): zlib's crc32(bytes) ^ 0xFFFFFFFF; 0xFFFFFFFF for out_len == 0.  Written
@@ -259,6 +283,7 @@ const char *mspack_hip_last_error(void);
 #define MSPACK_HIP_FEAT_CRC32_RANGES 64u /* MSPACK_HIP_KIND_CRC32 */
 #define MSPACK_HIP_FEAT_SHA384 128u     /* MSPACK_HIP_KIND_SHA384 (and two MSPACK_HIP_KIND_DIGEST_MORE tails per head) */
 #define MSPACK_HIP_FEAT_SHA512 256u     /* MSPACK_HIP_KIND_SHA512 (and three MSPACK_HIP_KIND_DIGEST_MORE tails per head) */
+#define MSPACK_HIP_FEAT_STORED 512u     /* MSPACK_HIP_KIND_STORED */
 unsigned mspack_hip_features(void);
 
 /* ---- device-resident batch decode (the hot path proper) ---------------------------------------
@@ -281,7 +306,7 @@ unsigned mspack_hip_features(void);
  *   kind_mask  : bit k set = units of kind k may be present; MSPACK_HIP_MASK_FRAME_TABLES set = LZX units may
  *                carry frame tables (MSPACK_HIP_UF_FRAME_TABLE): only then are the parse wavefronts launched.
  *                Was: bit k set = units of kind k may be present (one kernel per codec is launched;
- *                units of other kinds are skipped); 0 = all three codecs.
+ *                units of other kinds are skipped); 0 = all codecs (kinds 1 to 7 and 11).
  *                MSPACK_HIP_MASK_CRC32 set = units may carry MSPACK_HIP_UF_CRC32: only then is the digest pass launched
  *                behind the codecs (two more launches; flagged units of a kind the mask leaves out get no digest worth reading)
  *                bit MSPACK_HIP_KIND_MD5 set = digest units may be present: only then is the MD5 pass launched, behind everything
@@ -299,6 +324,13 @@ unsigned mspack_hip_features(void);
  *                in_next; they are 0 when it ends.  Precondition: d_order names no range unit twice (with a unit listed twice
  *                two places of the list would share one unit's words: the checksums would be wrong, without notice; reads stay
  *                inside the checked ranges)
+ *                bit MSPACK_HIP_KIND_STORED (11) set = stored units may be present: only then is their copy launched (three launches: a
+ *                one-wave scan of the units' segment counts, the segments, the results), behind the codecs and in front of every
+ *                digest pass; a mask that names no kind ("all codecs") includes it.  While it runs it keeps its bookkeeping in the
+ *                stored units' own in_used, good_len and in_next; the last launch writes their final values.  Precondition: d_order
+ *                names no stored unit twice (two places of the list would share one unit's words: bytes of those units could be
+ *                copied twice or not at all, without notice; every access stays inside the checked ranges).  Without the bit a
+ *                stored unit is copied by nobody and its result is not written
  *                MSPACK_HIP_MASK_LZSS_RING set = LZSS units may carry MSPACK_HIP_UF_LZSS_RING: only then is the kernel that takes
  *                the flagged units launched, beside the one that takes the unflagged ones (with the LZSS bit, or a mask that names no
  *                codec); without it a flagged unit is decoded by nobody and its result is not written

@@ -39,6 +39,9 @@ MASK_SHA384, MASK_SHA512 = 1 << KIND_SHA384, 1 << KIND_SHA512     # ... the SHA-
 KIND_CRC32R = 20             # a digest unit: zlib.crc32 of out[out_off : out_off + out_len], at any length -> result.out_len
 FEAT_CRC32_RANGES = 64
 MASK_CRC32R = 1 << KIND_CRC32R   # decode_batch_device(kind_mask): launch the CRC-32 range pass
+KIND_STORED = 11             # CAB method 0: min(in_len, out_len) bytes of the unit's input copied to out[out_off : ...]; no slack, any alignment
+FEAT_STORED = 512
+MASK_STORED = 1 << KIND_STORED   # decode_batch_device(kind_mask): launch the stored units' copy
 ERR_OK, ERR_ARGS, ERR_OPEN, ERR_READ, ERR_WRITE, ERR_SEEK, ERR_NOMEMORY, ERR_SIGNATURE, \
     ERR_DATAFORMAT, ERR_CHECKSUM, ERR_CRUNCH, ERR_DECRUNCH = range(12)
 

@@ -108,6 +108,7 @@ MSCABD_PARAM_HIP_DEVICES, MSCABD_PARAM_HIP_CACHE_MB, MSCABD_PARAM_HIP_MD5, MSCAB
 MSCHMD_PARAM_HIP_DIGESTS = 103
 MSCABD_PARAM_HIP_DIGESTS64 = MSCHMD_PARAM_HIP_DIGESTS64 = 106      # a mask of MSPACK_DIGEST_SHA384 | MSPACK_DIGEST_SHA512
 MSCABD_PARAM_HIP_CRC32, MSCHMD_PARAM_HIP_CRC32 = 105, 105     # 1: the batches carry one CRC-32 range unit per file (104 is no param)
+MSCABD_PARAM_HIP_STORED = 107    # 1: stored folders are gathered into the batches and served from them while clean
 MSPACK_DIGEST_MD5, MSPACK_DIGEST_SHA1, MSPACK_DIGEST_SHA256 = 1, 2, 4
 MSPACK_DIGEST_SHA384, MSPACK_DIGEST_SHA512 = 16, 32                  # (8 is no algorithm)
 DIGEST_BYTES = {MSPACK_DIGEST_MD5: 16, MSPACK_DIGEST_SHA1: 20, MSPACK_DIGEST_SHA256: 32, MSPACK_DIGEST_SHA384: 48, MSPACK_DIGEST_SHA512: 64}
@@ -142,6 +143,8 @@ def _setup(L=None):
     for fn in (L.mspack_cabd_crc32_counts, L.mspack_chmd_crc32_counts):
         fn.restype = None
         fn.argtypes = [C.c_void_p, C.c_int]
+    L.mspack_cabd_stored_counts.restype = None
+    L.mspack_cabd_stored_counts.argtypes = [C.c_void_p, C.c_int]
     L.mspack_cabd_get_param.restype = C.c_int
     L.mspack_cabd_get_param.argtypes = [_P(MscabDecompressor), C.c_int, _P(C.c_int)]
     L.mspack_chmd_digest.restype = C.c_int
@@ -186,6 +189,13 @@ def cabd_crc32_counts(reset=False, L=None):
     """mspack_cabd_crc32_counts (mspack.h): successful Cab.crc32() calls answered (from the device, by the host's CRC-32)"""
     c = (C.c_ulonglong * 2)()
     _setup(L).mspack_cabd_crc32_counts(c, int(reset))
+    return int(c[0]), int(c[1])
+
+
+def cabd_stored_counts(reset=False, L=None):
+    """mspack_cabd_stored_counts (mspack.h): stored folders (served from a batch, streamed while MSCABD_PARAM_HIP_STORED was 1)"""
+    c = (C.c_ulonglong * 2)()
+    _setup(L).mspack_cabd_stored_counts(c, int(reset))
     return int(c[0]), int(c[1])
 
 

@@ -99,7 +99,7 @@ __device__ __forceinline__ u32 crc_unit_len(const mspack_hip_unit &u, const mspa
 }
 __device__ __forceinline__ bool crc_unit_wanted(const mspack_hip_unit &u)
 {
-  return (u.flags & MSPACK_HIP_UF_CRC32) != 0u && u.kind >= MSPACK_HIP_KIND_MSZIP && u.kind <= MSPACK_HIP_KIND_KWAJ_LZH;
+  return (u.flags & MSPACK_HIP_UF_CRC32) != 0u && ((u.kind >= MSPACK_HIP_KIND_MSZIP && u.kind <= MSPACK_HIP_KIND_KWAJ_LZH) || u.kind == MSPACK_HIP_KIND_STORED);
 }
 
 // one unit per lane: in_used = 0xFFFFFFFF * x^(8n), the start value's share (all of the digest when n == 0)

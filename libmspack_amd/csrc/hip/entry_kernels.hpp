@@ -671,3 +671,24 @@ void mspack_crc32r_finish(const mspack_hip_unit *units, const u32 *order, u32 n,
 {
   crc32r_finish_lane(units, order, n, out_bytes, results);
 }
+
+// MSPACK_HIP_KIND_STORED (stored_kernel.hpp): a stored folder's bytes into the output arena -- the segments of all stored units of the
+// list one pool of work.  order[0 .. n) names the list's units (NULL: the whole table); units of other kinds own nothing here.  Stream
+// order is the only ordering between the three launches: scan: one wave; the pass: a bounded grid of waves that take chunks of segment
+// tickets until the counter is past the end; results: one position per lane, last (the pass keeps its bookkeeping in result words)
+__global__ __launch_bounds__(64)
+void mspack_stored_scan(const mspack_hip_unit *units, const u32 *order, u32 n, u64 in_bytes, const u8 *out_arena, u64 out_bytes, mspack_hip_result *results)
+{
+  stored_scan_wave(units, order, n, in_bytes, out_arena, out_bytes, results);
+}
+__global__ __launch_bounds__(64)
+void mspack_stored_pass(const mspack_hip_unit *units, const u32 *order, u32 n, const u8 *in_arena, u64 in_bytes, u8 *out_arena, u64 out_bytes,
+                        mspack_hip_result *results)
+{
+  stored_pass_wave(units, order, n, in_arena, in_bytes, out_arena, out_bytes, results);
+}
+__global__ __launch_bounds__(64)
+void mspack_stored_results(const mspack_hip_unit *units, const u32 *order, u32 n, u64 in_bytes, u64 out_bytes, mspack_hip_result *results)
+{
+  stored_result_lane(units, order, n, in_bytes, out_bytes, results);
+}

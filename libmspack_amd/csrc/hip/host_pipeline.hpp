@@ -399,6 +399,8 @@ static int issue_chunks(PipeCall &pc, CopyBack &cb)
     for (unsigned k = 1; k <= MSPACK_HIP_KIND_XORSUM; k++)
       TRY(launch_kind(k, pc.d_units, pc.d_order + c.order_off[k], c.order_n[k], d_in, d_out, pc.d_res, cx.d_fm.p, plan.n_frames, c.fm_lo, c.fm_n, st,
                       c.has_ftab, (unsigned) ci, plan.n_rec_slots, one, c.has_lzss_ring));
+    // (the stored units' copy: offsets are relative to the spans, the spans are what the device holds of the arenas)
+    TRY(launch_stored(pc.d_units, pc.d_order + c.order_off[MSPACK_HIP_KIND_STORED], c.order_n[MSPACK_HIP_KIND_STORED], d_in, pc.in_span, d_out, pc.out_span, pc.d_res, st));
     if (c.crc_n) TRY(launch_crc32(pc.d_units, pc.d_order + c.crc_off, c.crc_n, c.crc_max, d_out, pc.d_res, st));      // behind every codec's store of its results
     if (plan.n_dig && ci + 1 == plan.chunks.size()) {
       // the digest units' passes, one per algorithm: once, on the last chunk's stream, behind every chunk's launches -- the bytes

@@ -13,7 +13,7 @@
 struct Chunk {
   size_t a, b;                          // local unit range [a, b)
   uint64_t in_lo, in_hi, out_lo, out_hi;
-  size_t order_off[8], order_n[8];      // per kind: slice of the order array
+  size_t order_off[MSPACK_HIP_KIND_STORED + 1], order_n[MSPACK_HIP_KIND_STORED + 1];      // per kind (1 .. XORSUM, STORED; [MSPACK_HIP_KIND_MD5] unused: digest units have lists of their own): slice of the order array
   size_t fm_lo, fm_n;
   size_t crc_off, crc_n; uint64_t crc_max;      // the chunk's units that carry MSPACK_HIP_UF_CRC32: slice of the order array, the longest
   bool has_ftab;                        // some LZX unit of the chunk carries a frame table
@@ -120,7 +120,7 @@ static int plan_units(mspack_hip_unit *units, const uint32_t *sel, size_t n_sel,
     u = units[idx[i]];
     if (u.kind != MSPACK_HIP_KIND_LZX_DELTA && !(u.kind == MSPACK_HIP_KIND_LZX && (u.flags & MSPACK_HIP_UF_LZX_LOG)) &&
         !(u.kind == MSPACK_HIP_KIND_QUANTUM && (u.flags & MSPACK_HIP_UF_QTM_MARKS))) u.ref_len = 0;
-    if (u.kind > MSPACK_HIP_KIND_MD5 && !unit_is_digest(u)) { snprintf(errbuf, errcap, "unit %u: unknown kind %u", idx[i], u.kind); return -1; }
+    if (u.kind > MSPACK_HIP_KIND_MD5 && u.kind != MSPACK_HIP_KIND_STORED && !unit_is_digest(u)) { snprintf(errbuf, errcap, "unit %u: unknown kind %u", idx[i], u.kind); return -1; }
     if (u.kind == MSPACK_HIP_KIND_XORSUM) {                // reads its input, owns no output
       if (u.flags & MSPACK_HIP_UF_CRC32) { snprintf(errbuf, errcap, "unit %u: a checksum unit decodes nothing to take a CRC-32 of", idx[i]); return -1; }
       if (u.out_len) { snprintf(errbuf, errcap, "unit %u: a checksum unit has no output", idx[i]); return -1; }
@@ -160,6 +160,10 @@ static int plan_units(mspack_hip_unit *units, const uint32_t *sel, size_t n_sel,
       u.in_off = 0; u.flags = 0;
       if (u.out_len) { out_lo = std::min<uint64_t>(out_lo, u.out_off); out_hi = std::max<uint64_t>(out_hi, u.out_off + u.out_len); }
       continue;
+    }
+    if (u.kind == MSPACK_HIP_KIND_STORED) {                // copies its input: owns exactly [out_off, out_off + out_len), reads exactly its in_len bytes
+      if (u.in_off > in_bytes || u.in_len > in_bytes - u.in_off) { snprintf(errbuf, errcap, "unit %u: a stored unit's input leaves the input arena", idx[i]); return -1; }
+      if (u.out_off > out_bytes || u.out_len > out_bytes - u.out_off) { snprintf(errbuf, errcap, "unit %u: a stored unit's output leaves the output arena", idx[i]); return -1; }
     }
     // kind 0 = "no codec": the unit is carried along, no kernel takes it, its result says MSPACK_ERR_ARGS
     const uint64_t below = unit_below(u);
@@ -300,7 +304,7 @@ static void plan_lists(BatchPlan &p)
     ci_prev_hi = c.out_hi;
     if (c.fm_lo == ~(size_t) 0) c.fm_lo = 0;
     c.in_lo &= ~15ull;
-    for (unsigned k = 1; k <= MSPACK_HIP_KIND_XORSUM; k++) {
+    for (unsigned k = 1; k <= MSPACK_HIP_KIND_STORED; k++) {      // (the stored units' list behind the codecs' and the checksum units')
       c.order_off[k] = op;
       for (size_t i = c.a; i < c.b; i++) if (local[i].kind == k) order[op++] = (uint32_t) i;
       c.order_n[k] = op - c.order_off[k];

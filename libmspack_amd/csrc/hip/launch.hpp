@@ -1,6 +1,6 @@
 // launch.hpp -- the launch layer and the device-resident C ABI: the thread's error text, launch<> (a kernel launch whose status is
 // returned), the launch-level environment knobs, launch_kind (one codec's launches over a compact unit list), launch_crc32, launch_md5, launch_sha1 /
-// launch_sha256, launch_sha512, launch_crc32_ranges, the
+// launch_sha256, launch_sha512, launch_crc32_ranges, launch_stored, the
 // analysis builds' debug exports, version / features / device functions, mspack_hip_decode_batch_device and _time_batch_device.
 #pragma once
 #include <mutex>
@@ -282,6 +282,39 @@ static hipError_t launch_crc32_ranges(const mspack_hip_unit *d_units, const uint
   LK(launch(mspack_crc32r_finish, per_lane, block, st, d_units, d_order, (u32) n, (u64) out_bytes, d_results));
   return hipSuccess;
 }
+// waves of mspack_stored_pass: as many as the device holds at once, eight per CU at most (nothing depends on the number being right)
+static unsigned stored_waves()
+{
+  static std::mutex mu;
+  static unsigned cache[MSPK_MAX_DEV_CACHE] = { 0 };
+  int dev = 0, per_cu = 0; hipDeviceProp_t pr;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MSPK_MAX_DEV_CACHE) return 2048u;
+  std::lock_guard<std::mutex> lock(mu);
+  if (!cache[dev]) {
+    if (hipGetDeviceProperties(&pr, dev) != hipSuccess) return 2048u;
+    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, mspack_stored_pass, 64, 0);
+    if (e != hipSuccess || per_cu < 1) per_cu = 8;
+    cache[dev] = (unsigned) pr.multiProcessorCount * (unsigned) std::min(per_cu, 8);
+  }
+  return cache[dev];
+}
+// the stored units order[0..n) (or, order == NULL, every unit: positions of other kinds own nothing): the one-wave scan, the pass -- a
+// grid no larger than the tickets the list can hold, bounded by the device's waves --, the results
+static hipError_t launch_stored(const mspack_hip_unit *d_units, const uint32_t *d_order, size_t n, const void *d_in, size_t in_bytes, void *d_out,
+                                size_t out_bytes, mspack_hip_result *d_results, hipStream_t st)
+{
+  if (n == 0) return hipSuccess;
+#ifdef MSPACK_HOST_CHECK      /* tests/hostcheck runs no kernel and its stand-in for a launch copies nothing */
+  return hipErrorInvalidValue;
+#endif
+  const dim3 per_lane((unsigned)((n + 63) / 64)), block(64);
+  const uint64_t most = (uint64_t) n * (std::min<uint64_t>(out_bytes, 0xFFFFFFFFu) / STORED_SEG + 2u);      // no list of n units has more tickets
+  const unsigned waves = (unsigned) std::min<uint64_t>(most, stored_waves());
+  LK(launch(mspack_stored_scan, dim3(1), block, st, d_units, d_order, (u32) n, (u64) in_bytes, (const u8 *) d_out, (u64) out_bytes, d_results));
+  LK(launch(mspack_stored_pass, dim3(waves), block, st, d_units, d_order, (u32) n, (const u8 *) d_in, (u64) in_bytes, (u8 *) d_out, (u64) out_bytes, d_results));
+  LK(launch(mspack_stored_results, per_lane, block, st, d_units, d_order, (u32) n, (u64) in_bytes, (u64) out_bytes, d_results));
+  return hipSuccess;
+}
 #undef LK
 
 extern "C" {
@@ -350,7 +383,7 @@ int mspack_hip_debug_frame_words(const void *d_frame_scratch, size_t n_frames_to
 const char *mspack_hip_version(void) { return "mspack-hip 0.4 (gfx950; LZX/LZX-DELTA/Quantum/MSZIP batch decode)"; }
 const char *mspack_hip_last_error(void) { return g_err; }
 unsigned mspack_hip_features(void) { return MSPACK_HIP_FEAT_CRC32 | MSPACK_HIP_FEAT_MD5 | MSPACK_HIP_FEAT_SHA1 | MSPACK_HIP_FEAT_SHA256 | MSPACK_HIP_FEAT_SLOTS | MSPACK_HIP_FEAT_LZSS_RING | MSPACK_HIP_FEAT_CRC32_RANGES |
-         MSPACK_HIP_FEAT_SHA384 | MSPACK_HIP_FEAT_SHA512; }
+         MSPACK_HIP_FEAT_SHA384 | MSPACK_HIP_FEAT_SHA512 | MSPACK_HIP_FEAT_STORED; }
 
 int mspack_hip_device_count(void) {
   int n = 0;
@@ -368,9 +401,8 @@ int mspack_hip_decode_batch_device(const mspack_hip_unit *d_units, const uint32_
                                    void *d_frame_scratch, size_t n_frames_total, unsigned kind_mask,
                                    void *stream)
 {
-  (void) in_bytes;
   if (n_units == 0) return 0;
-  if ((kind_mask & 0x31301FEu) == 0) kind_mask |= 0xFEu;  // bit k = units of kind k may be present; none = every codec (and no digest units)
+  if ((kind_mask & 0x31309FEu) == 0) kind_mask |= 0x8FEu;  // bit k = units of kind k may be present; none = every codec, stored units included (and no digest units)
   // the caller's unit table lives on the device, so the kinds cannot be compacted here: every codec in the
   // mask gets the whole grid and blocks of other kinds leave at once.  Callers with mixed batches pass one
   // order list per codec and a one-bit mask (what the host-buffer entry points below do).
@@ -379,6 +411,9 @@ int mspack_hip_decode_batch_device(const mspack_hip_unit *d_units, const uint32_
       CK(launch_kind(k, d_units, d_order, n_units, d_in, d_out, d_results, d_frame_scratch, n_frames_total, 0, n_frames_total,
                      (hipStream_t) stream, (kind_mask & MSPACK_HIP_MASK_FRAME_TABLES) != 0u, 0, (size_t) -1, true,
                      (kind_mask & MSPACK_HIP_MASK_LZSS_RING) != 0u));
+  // the stored units' copy (three launches): in front of the digest passes like every kernel that stores into the arena
+  if (kind_mask & (1u << MSPACK_HIP_KIND_STORED))
+    CK(launch_stored(d_units, d_order, n_units, d_in, in_bytes, d_out, out_bytes, d_results, (hipStream_t) stream));
   // (the flags are on the device too: the digest pass is launched only when the caller says some unit may carry MSPACK_HIP_UF_CRC32)
   if (kind_mask & MSPACK_HIP_MASK_CRC32)
     CK(launch_crc32(d_units, d_order, n_units, std::min<uint64_t>(out_bytes, 0xFFFFFFFFu), d_out, d_results, (hipStream_t) stream));

@@ -51,6 +51,7 @@ static_assert(sizeof(lzxp::LzxFrameRec) == sizeof(lzxn::LzxFrameRec), "one recor
 #include "lzss_ring_kernel.hpp"
 #include "crc32_kernel.hpp"
 #include "crc32_range_kernel.hpp"
+#include "stored_kernel.hpp"
 #include "md5_kernel.hpp"
 #include "sha_kernel.hpp"
 #include "sha512_kernel.hpp"

@@ -89,6 +89,11 @@ struct folder_p {
   /* MSCABD_PARAM_HIP_DIGESTS / _DIGESTS64: the digests the folder's batch took of its files (mspack_hip.h: MSPACK_HIP_KIND_MD5 / _SHA1 / _SHA256 / _SHA384 / _SHA512),
    * by offset in the folder (host_digest.h: struct digest_table) */
   struct digest_table dg;
+  /* MSCABD_PARAM_HIP_STORED, a stored folder: st_streamed = a batch found it not clean (a failing block read, a block whose cbData is
+   * not its cbUncomp, a checksum that does not match, a unit that did not answer 0, a cabinet that would not open): it is never
+   * gathered again, the streamed state machine answers for it on every call.  st_counted: bit 1 / 2 = counted as served / as streamed
+   * (mspack_cabd_stored_counts) */
+  int st_streamed, st_counted;
 };
 struct cab_p {
   struct mscabd_cabinet base;
@@ -107,6 +112,7 @@ struct ck_list { struct ck_part *p; size_t n, cap; int failed; };
 struct blk_reader {
   struct ck_list *defer;              /* note the parts' checksums here instead of verifying them (gather only)          */
   size_t defer_base; unsigned int defer_owner;   /* arena offset of input[0]; index of the folder in the batch          */
+  int quiet_set;                      /* do not say "ran out of cabinets in set" (the gather of a stored folder: the streamed path says what is to be said) */
   int quiet_cksum, bad_cksum;          /* do not say "bad block checksum" now: the caller notes it (bad_cksum) and says it later */
   struct folder_p *folder;
   struct fseg *seg;                   /* cabinet the next block header is read from                */
@@ -121,6 +127,7 @@ struct cabd_p {
   struct mspack_system *system;
   int error, read_error;
   int searchbuf_size, fix_mszip, buf_size, salvage;
+  int hip_stored;                     /* MSCABD_PARAM_HIP_STORED: 1 = stored folders are gathered into the batches (one MSPACK_HIP_KIND_STORED unit each) and served from them while clean */
   int hip_crc32;                      /* MSCABD_PARAM_HIP_CRC32: 1 = the batches carry one MSPACK_HIP_KIND_CRC32 unit per file, for mspack_cabd_crc32() */
   int devices, cache_mb, hip_digests; /* hip_digests: MSCABD_PARAM_HIP_DIGESTS, a mask of MSPACK_DIGEST_* (MSCABD_PARAM_HIP_MD5 is its bit 1) */
   int hip_digests64;                  /* MSCABD_PARAM_HIP_DIGESTS64: a mask of MSPACK_DIGEST_SHA384 | MSPACK_DIGEST_SHA512 */
@@ -132,6 +139,8 @@ struct cabd_p {
   struct blk_reader st;
   unsigned int st_offset;             /* bytes produced so far from st.folder                      */
   int st_active;
+  struct folder_p *st_virtual;        /* MSCABD_PARAM_HIP_STORED: the stream as the streamed path would hold it now, had it answered the calls a
+                                         batch served: on this folder, at st_offset, no reader open (st_active == 0) */
   struct folder_p *last_folder;       /* folder of the previous extract()                          */
   /* the reference's ONE decompressor as far as its answers go (cabd.c:1136-1175): it lives on across extract() calls while the
    * files of a folder are asked for at ascending offsets -- also after a call that FAILED: its codec then answers every further
@@ -664,7 +673,7 @@ static int reader_block(struct cabd_p *self, struct blk_reader *r, unsigned int 
     if (ulen) { *ulen_out = ulen; return MSPACK_ERR_OK; }
     sys->close(r->fh); r->fh = NULL;
     if (!(r->seg = r->seg->next)) {
-      sys->message(NULL, "WARNING; ran out of cabinets in set. Are any missing?");
+      if (!r->quiet_set) sys->message(NULL, "WARNING; ran out of cabinets in set. Are any missing?");
       return MSPACK_ERR_DATAFORMAT;
     }
     if (!(r->fh = sys->open(sys, r->seg->cab->base.filename, MSPACK_SYS_OPEN_READ))) return MSPACK_ERR_OPEN;
@@ -675,7 +684,7 @@ static int reader_block(struct cabd_p *self, struct blk_reader *r, unsigned int 
 /* ---- stored folders: streamed (reference cabd.c:1283-1345 + noned_decompress 1530-1541) --------------- */
 static void stored_reset(struct cabd_p *self) {
   if (self->st_active) reader_close(self, &self->st);
-  self->st_active = 0; self->st_offset = 0;
+  self->st_active = 0; self->st_offset = 0; self->st_virtual = NULL;
 }
 
 /* the feeder as the "codec" sees it: returns the bytes delivered, -1 after a block error */
@@ -725,6 +734,9 @@ static int stored_extract(struct cabd_p *self, struct folder_p *fol, struct msca
   unsigned char *buf;
   if (!self->st_active || self->st.folder != fol || self->st_offset > file->offset) {
     int err;
+    /* (also where a batch served the calls before this one, st_virtual: that stream was at st_offset <= file->offset with every
+     * block read so far good and read_error OK -- starting over from the folder's first block reads the same bytes, leaves the same
+     * read_error, and ends in the state that stream would be in) */
     stored_reset(self);
     if ((err = reader_open(self, &self->st, fol, 0))) return self->error = err;
     self->st_active = 1; self->st_offset = 0;
@@ -781,6 +793,7 @@ struct gathered {
   int frames_ok;
   size_t marks_off; unsigned int n_marks;       /* Quantum: the folder's request boundaries as a table in the arena (gather_marks) */
   unsigned int *marks;
+  int st_unclean;                               /* a stored folder: some block's cbData is not its cbUncomp */
   size_t dg_lo, dg_n;                           /* MSCABD_PARAM_HIP_DIGESTS: the folder's files' digest units (heads and tails), counted from the batch's first */
 };
 
@@ -790,6 +803,21 @@ struct gathered {
  * digest the batch took on the device / hashed on the host, over all decompressors of the process */
 static unsigned long long g_digest_counts[DIGEST_ALGS][2];
 static unsigned long long g_crc32_counts[2];            /* the same for mspack_cabd_crc32() */
+/* mspack_cabd_stored_counts: stored folders a batch served / stored folders streamed while MSCABD_PARAM_HIP_STORED was 1 (each folder
+ * once per way), over all decompressors of the process */
+static unsigned long long g_stored_counts[2];
+static void stored_count(struct folder_p *fol, int streamed)
+{
+  if (fol->st_counted & (1 << streamed)) return;
+  fol->st_counted |= 1 << streamed;
+  __atomic_fetch_add(&g_stored_counts[streamed], 1ull, __ATOMIC_RELAXED);
+}
+/* MSCABD_PARAM_HIP_STORED in force: asked for, the provider can (one without mspack_hip_features cannot), salvage mode off (there the
+ * streamed state machine decides block by block what a folder gives) */
+static int stored_batches(const struct cabd_p *self)
+{
+  return self->hip_stored && !self->salvage && mspack_hip_features && (mspack_hip_features() & MSPACK_HIP_FEAT_STORED);
+}
 
 /* The request boundaries a Quantum folder's files imply -- cabd_extract asks its codec for the bytes in front of a file, then for
  * the file (cabd.c:1195-1218): requests end where files begin and where they end.  Ascending, without duplicates, inside
@@ -841,7 +869,7 @@ static int gather_folder_once(struct cabd_p *self, struct gathered *g, struct in
   /* (a folder that is gathered again -- the batch it was in failed -- starts its list afresh) */
   sys->free(fol->rep_ck); fol->rep_ck = NULL; fol->ck_n = 0;
   g->len = 0; g->total = 0; g->read_err = MSPACK_ERR_OK; g->hard_eof = 0;
-  g->nblk = 0; g->frames_ok = 1; g->tab_off = 0;
+  g->nblk = 0; g->frames_ok = 1; g->tab_off = 0; g->st_unclean = 0;
   if (!arena_room(sys, A, 16 + 64 + 32)) return MSPACK_ERR_NOMEMORY;
   while (A->len & 15) A->p[A->len++] = 0;
   g->in_off = A->len;
@@ -858,6 +886,7 @@ static int gather_folder_once(struct cabd_p *self, struct gathered *g, struct in
    * extract() call whose decoding gets there, not when this driver gathers the cabinet's folders (rep_ck below) */
   if (ignore_cksum && !g->boff) qoff = (uint32_t *) sys->alloc(sys, ((size_t) fol->base.num_blocks + 1) * sizeof(uint32_t));
   r.quiet_cksum = ignore_cksum && (g->boff != NULL || qoff != NULL);
+  r.quiet_set = method == MSCAB_COMP_NONE;
   while (r.block < fol->base.num_blocks) {
     unsigned int ulen = 0;
     r.block++;
@@ -880,6 +909,7 @@ static int gather_folder_once(struct cabd_p *self, struct gathered *g, struct in
       }
       if (bad_n < bad_cap) bad[bad_n++] = g->boff ? g->nblk : qn;
     }
+    if (method == MSCAB_COMP_NONE && r.i_end != ulen) g->st_unclean = 1;
     if (qoff) qoff[qn++] = (uint32_t)(A->len - g->in_off);
     if (g->boff) {
       if (g->total % CAB_BLOCKMAX) g->frames_ok = 0;          /* an earlier block was not a whole frame */
@@ -944,7 +974,7 @@ static int gather_folder(struct cabd_p *self, struct gathered *g, struct in_aren
 {
   const size_t ck_mark = ck ? ck->n : 0, len0 = A->len;
   int err = gather_folder_once(self, g, A, ck, owner);
-  if (!err && g->hard_eof && ck && ck->n > ck_mark) {
+  if (!err && g->hard_eof && ck && ck->n > ck_mark && (g->fol->base.comp_type & 0x0F) != MSCAB_COMP_NONE) {
     /* the chain broke behind blocks whose checksums nobody has verified yet (they were left to the device), and the input is cut
      * at the failing read: those parts no longer lie in the arena as they were read.  Once more, verifying while the blocks are
      * read -- what the reference does: a block whose checksum fails ends the chain first. */
@@ -980,10 +1010,22 @@ static void batch_take_folder(struct cab_batch *B, size_t k)
   unsigned char *const out_arena = B->out_arena;
   struct folder_p *fp = gs[k].fol;
   int method = fp->base.comp_type & 0x0F;
+  if (method == MSCAB_COMP_NONE && (res[k].err != MSPACK_ERR_OK || res[k].out_len != gs[k].total || gs[k].hard_eof || gs[k].st_unclean)) {
+    fp->st_streamed = 1;                 /* not a clean folder: its bytes are dropped, the streamed path answers for it */
+    return;
+  }
   fp->total = gs[k].total; fp->read_err = gs[k].read_err; fp->hard_eof = gs[k].hard_eof;
   fp->store = B->store; B->store->refs++;
   fp->dec = out_arena + units[k].out_off;
-  if (method >= 1 && method <= 3) {
+  if (method == MSCAB_COMP_NONE) {       /* a clean stored folder: all of it is good */
+    fp->good_len = fp->total; fp->written = fp->total; fp->dec_err = MSPACK_ERR_OK; fp->res_flags = 0;
+    sys->free(fp->dg.e); memset(&fp->dg, 0, sizeof(fp->dg));
+    if (gs[k].dg_n && (fp->dg.e = (struct digest_kept *) sys->alloc(sys, gs[k].dg_n * sizeof(*fp->dg.e)))) {
+      const size_t m0 = B->n + B->ck.n + gs[k].dg_lo;
+      digest_table_harvest(&fp->dg, units + m0, res + m0, gs[k].dg_n, units[k].out_off, 0);
+    }
+  }
+  else if (method >= 1 && method <= 3) {
     unsigned int g = res[k].good_len > gs[k].total ? gs[k].total : res[k].good_len;
     fp->good_len = g; fp->dec_err = res[k].err; fp->res_flags = res[k].flags;
     fp->written = res[k].out_len > gs[k].total ? gs[k].total : res[k].out_len;
@@ -1043,6 +1085,7 @@ static int decode_cabinets(struct cabd_p *self, struct cab_p **cabs, size_t n_ca
   const int dev_algs = digest_device_algs(self->hip_digests | self->hip_digests64 | (self->hip_crc32 ? DIGEST_ALG_CRC32 : 0));
   size_t dg_cap = 0, ndg = 0;                           /* digest units: at most digest_units_per_file per file of the gathered folders; those made */
   size_t n_qtm_files = 0;                               /* files in Quantum folders: two marks each at most (gather_marks) */
+  const int st_batches = stored_batches(self);          /* MSCABD_PARAM_HIP_STORED: stored folders are gathered too */
   for (c = 0; c < n_cabs; c++) {
     struct mscabd_file *fi;
     for (fo = cabs[c]->base.folders; fo; fo = fo->next) { n++; ((struct folder_p *) fo)->file_count = 0; ((struct folder_p *) fo)->first_file = NULL; }
@@ -1069,13 +1112,22 @@ static int decode_cabinets(struct cabd_p *self, struct cab_p **cabs, size_t n_ca
     struct folder_p *fp = (struct folder_p *) fo;
     size_t est = (size_t) fo->num_blocks * CAB_BLOCKMAX;
     if (fp->decoded || fp->job) continue;
-    if ((fo->comp_type & 0x0F) == MSCAB_COMP_NONE || fp->merge_prev) continue;   /* streamed / not extractable */
+    if (fp->merge_prev) continue;                                                /* not extractable */
+    if ((fo->comp_type & 0x0F) == MSCAB_COMP_NONE && (!st_batches || fp->st_streamed)) continue;   /* streamed */
     if (fp != want && used + est > budget) continue;
     gs[n].fol = fp;
     {
-      const size_t ck_mark = ck.n;
+      const size_t ck_mark = ck.n, len_mark = A.len;
       err = gather_folder(self, &gs[n], &A, &ck, (unsigned int) n);
       if (err) ck.n = ck_mark;                             /* (the arena was rolled back: so are the parts noted in it) */
+      if ((fo->comp_type & 0x0F) == MSCAB_COMP_NONE && (err || gs[n].hard_eof || gs[n].st_unclean)) {
+        /* a stored folder that is not clean, or could not be started: nothing of it stays in the batch -- the streamed path reports
+         * whatever there is to report, with its own reads */
+        if (!err) { sys->free(gs[n].boff); gs[n].boff = NULL; }
+        ck.n = ck_mark; A.len = len_mark; err = MSPACK_ERR_OK;
+        fp->st_streamed = 1;
+        continue;
+      }
     }
     if (err == MSPACK_ERR_OPEN && fp != want) { err = MSPACK_ERR_OK; continue; }   /* that folder stays undecoded */
     if (err) break;
@@ -1109,6 +1161,11 @@ static int decode_cabinets(struct cabd_p *self, struct cab_p **cabs, size_t n_ca
     units[k].in_off = gs[k].in_off; units[k].in_len = (uint32_t) gs[k].len;
     if (gs[k].frames_ok) units[k].in_chunk = (uint32_t)(gs[k].tab_off / 4);
     units[k].out_off = out_bytes; units[k].out_len = gs[k].total;
+    if (method == MSCAB_COMP_NONE) {                            /* copied, not decoded: no slack, no flags */
+      units[k].kind = MSPACK_HIP_KIND_STORED;
+      out_bytes += ((size_t) gs[k].total + 15) & ~(size_t) 15;
+      continue;
+    }
     out_bytes += ((size_t) gs[k].total + 32768 + 15) & ~(size_t) 15;
     if (self->fix_mszip && method == MSCAB_COMP_MSZIP) {        /* the repair log behind the unit's slack (mspack_hip.h) */
       units[k].e8_base = (int32_t)(fp->base.num_blocks + 8u);
@@ -1206,7 +1263,11 @@ static int decode_cabinets(struct cabd_p *self, struct cab_p **cabs, size_t n_ca
   if (!err) {
     /* a block part whose payload is not what its header says: that folder is gathered again, the reference's way */
     for (k = 0; k < ck.n; k++)
-      if (res[n + k].err != MSPACK_ERR_OK || res[n + k].in_next != ck.p[k].want) { gs[ck.p[k].owner].fol->cksum_on_host = 1; again = 1; }
+      if (res[n + k].err != MSPACK_ERR_OK || res[n + k].in_next != ck.p[k].want) {
+        struct folder_p *bad = gs[ck.p[k].owner].fol;
+        if ((bad->base.comp_type & 0x0F) == MSCAB_COMP_NONE) bad->st_streamed = 1;      /* (a stored folder: streamed from now on, no second gather) */
+        else { bad->cksum_on_host = 1; again = 1; }
+      }
   }
   if (!err && n) {
     /* the output arena stays: every folder's decoded bytes are where the batch put them (no copy per folder) */
@@ -1214,13 +1275,14 @@ static int decode_cabinets(struct cabd_p *self, struct cab_p **cabs, size_t n_ca
     else { B.store->base = out_arena; B.store->refs = 0; }
     for (k = 0; k < n && !err; k++) {
       struct folder_p *fp = gs[k].fol;
+      if (fp->st_streamed) continue;                       /* (a stored folder with a bad block: not kept) */
       if (fp->cksum_on_host && ck.n) {                     /* (flagged just now?  It was decoded past a bad block: not kept) */
         size_t j; int mine = 0;
         for (j = 0; j < ck.n && !mine; j++) mine = ck.p[j].owner == (unsigned int) k;
         if (mine) continue;
       }
       batch_take_folder(&B, k);
-      kept += (size_t) fp->base.num_blocks * CAB_BLOCKMAX;
+      if (fp->decoded) kept += (size_t) fp->base.num_blocks * CAB_BLOCKMAX;
     }
     if (B.store && B.store->refs) out_arena = NULL;        /* the folders own it now */
     else if (B.store) sys->free(B.store);
@@ -1285,7 +1347,8 @@ static int folder_settle(struct cabd_p *self, struct folder_p *fp)
     sys->message(NULL, "GPU batch decode failed: %s", mspack_hip_last_error());
     return MSPACK_ERR_DECRUNCH;
   }
-  if (bad) fp->cksum_on_host = 1;                          /* (decoded past a bad block: not kept) */
+  if (bad && (fp->base.comp_type & 0x0F) == MSCAB_COMP_NONE) fp->st_streamed = 1;      /* (a stored folder with a bad block: streamed) */
+  else if (bad) fp->cksum_on_host = 1;                     /* (decoded past a bad block: not kept) */
   else batch_take_folder(B, k);
   fp->job = NULL; B->gs[k].fol = NULL;
   if (--B->left == 0) batch_release(sys, B);
@@ -1354,6 +1417,52 @@ static unsigned int flushed_at_failure(struct folder_p *fp, unsigned int end)
   return f < end ? f : end;
 }
 
+/* MSCABD_PARAM_HIP_STORED: a stored folder's call answered from the bytes a batch put into the folder's place (fol->dec): the file's
+ * slice with the open / write / close calls of the compressed path, and the decompressor left as stored_extract() would leave it --
+ * error, read_error, and the stream: it starts over (read_error OK) where the streamed path would start it over, and stands behind
+ * the file afterwards (st_virtual: no reader is open; stored_extract() opens one and reads up to there when it is needed) */
+static int stored_serve(struct cabd_p *self, struct folder_p *fol, struct mscabd_file *file, unsigned int filelen, const char *filename)
+{
+  struct mspack_system *sys = self->system;
+  struct mspack_file *fh;
+  if (self->st_virtual != fol || self->st_offset > file->offset) {
+    stored_reset(self);
+    self->st_virtual = fol; self->st_offset = 0;
+    self->read_error = MSPACK_ERR_OK;
+  }
+  if (self->sink) fh = DIGEST_SINK;
+  else if (!(fh = sys->open(sys, filename, MSPACK_SYS_OPEN_WRITE))) return self->error = MSPACK_ERR_OPEN;
+  self->error = MSPACK_ERR_OK;
+  if (filelen) {
+    if (self->sink) {
+      /* (mspack_cabd_digest / _crc32: the digest the batch took of the file if it did; else these bytes are hashed) */
+      if ((self->sink_kept = digest_table_find(&fol->dg, file->offset, filelen, self->sink->alg)) == NULL)
+        sink_update(self->sink, fol->dec + file->offset, filelen);
+    }
+    else if (write_slice(sys, fh, fol->dec + file->offset, filelen) != MSPACK_ERR_OK) self->error = MSPACK_ERR_WRITE;
+    self->st_offset = file->offset + filelen;
+  }
+  if (fh != DIGEST_SINK) sys->close(fh);
+  return self->error;
+}
+
+/* can this call on a stored folder be answered from a batch?  Gathers the folder's cabinet (or waits for the folder's unit) first
+ * where that has not happened.  No: the folder is streamed, now and -- once it was found not clean -- ever */
+static int stored_from_batch(struct cabd_p *self, struct folder_p *fol, struct mscabd_file *file, unsigned int filelen)
+{
+  int tries;
+  if (!stored_batches(self)) return 0;
+  /* (a stream of the streamed path that this call would go on reading: it stays the authority -- it may be past a failure) */
+  if (self->st_active && self->st.folder == fol && self->st_offset <= file->offset) return 0;
+  for (tries = 0; !fol->decoded && !fol->st_streamed && tries < 4; tries++) {
+    const int err = fol->job ? folder_settle(self, fol) : decode_cabinet(self, (struct cab_p *) fol->data.cab, fol);
+    if (err) fol->st_streamed = 1;         /* (no batch: no memory, a device that failed -- said by whoever failed) */
+  }
+  if (!fol->decoded || fol->st_streamed) return 0;
+  /* a file that reaches past the folder's bytes is not clean either */
+  return file->offset <= fol->total && filelen <= fol->total - file->offset;
+}
+
 static int cabd_extract(struct mscab_decompressor *base, struct mscabd_file *file, const char *filename)
 {
   struct cabd_p *self = (struct cabd_p *) base;
@@ -1399,7 +1508,12 @@ static int cabd_extract(struct mscab_decompressor *base, struct mscabd_file *fil
   /* one decompression state per decompressor: another folder ends the stored folder's stream */
   if (self->last_folder != fol) stored_reset(self);
   self->last_folder = fol;
-  if ((fol->base.comp_type & 0x0F) == MSCAB_COMP_NONE) { self->live_folder = NULL; self->msg_folder = NULL; return stored_extract(self, fol, file, filelen, filename); }
+  if ((fol->base.comp_type & 0x0F) == MSCAB_COMP_NONE) {
+    self->live_folder = NULL; self->msg_folder = NULL;
+    if (stored_from_batch(self, fol, file, filelen)) { stored_count(fol, 0); return stored_serve(self, fol, file, filelen, filename); }
+    if (self->hip_stored) stored_count(fol, 1);
+    return stored_extract(self, fol, file, filelen, filename);
+  }
 
   /* (a folder whose batch is still running waits for its own unit; one that comes out of that flagged -- a block failed its
    * checksum on the device -- is gathered again, which may start the next batch) */
@@ -1534,6 +1648,16 @@ int mspack_cabd_crc32(struct mscab_decompressor *base, struct mscabd_file *file,
 
 void mspack_cabd_crc32_counts(unsigned long long counts[2], int reset) { crc32_counts_get(g_crc32_counts, counts, reset); }
 
+/* mspack.h: stored folders served from a batch / streamed while MSCABD_PARAM_HIP_STORED was 1 */
+void mspack_cabd_stored_counts(unsigned long long counts[2], int reset)
+{
+  int i;
+  for (i = 0; i < 2; i++) {
+    if (counts) counts[i] = __atomic_load_n(&g_stored_counts[i], __ATOMIC_RELAXED);
+    if (reset) __atomic_store_n(&g_stored_counts[i], 0ull, __ATOMIC_RELAXED);
+  }
+}
+
 int mspack_cabd_md5(struct mscab_decompressor *base, struct mscabd_file *file, unsigned char digest[16]) { return mspack_cabd_digest(base, file, MSPACK_DIGEST_MD5, digest, 16); }
 
 void mspack_cabd_digest_counts(int alg, unsigned long long counts[2], int reset) { digest_counts_get(g_digest_counts, alg, counts, reset); }
@@ -1555,6 +1679,7 @@ static int cabd_param(struct mscab_decompressor *base, int param, int value)
   case MSCABD_PARAM_HIP_DIGESTS:  if (value < 0 || value > 7) return MSPACK_ERR_ARGS; self->hip_digests = value; break;
   case MSCABD_PARAM_HIP_CRC32:    if (value != 0 && value != 1) return MSPACK_ERR_ARGS; self->hip_crc32 = value; break;
   case MSCABD_PARAM_HIP_DIGESTS64: if (value & ~(MSPACK_DIGEST_SHA384 | MSPACK_DIGEST_SHA512)) return MSPACK_ERR_ARGS; self->hip_digests64 = value; break;
+  case MSCABD_PARAM_HIP_STORED:   if (value != 0 && value != 1) return MSPACK_ERR_ARGS; self->hip_stored = value; break;
   default: return MSPACK_ERR_ARGS;
   }
   return MSPACK_ERR_OK;
@@ -1576,6 +1701,7 @@ int mspack_cabd_get_param(struct mscab_decompressor *base, int param, int *value
   case MSCABD_PARAM_HIP_DIGESTS:  *value = self->hip_digests; break;
   case MSCABD_PARAM_HIP_CRC32:    *value = self->hip_crc32; break;
   case MSCABD_PARAM_HIP_DIGESTS64: *value = self->hip_digests64; break;
+  case MSCABD_PARAM_HIP_STORED:   *value = self->hip_stored; break;
   default: return MSPACK_ERR_ARGS;
   }
   return MSPACK_ERR_OK;
@@ -1595,8 +1721,9 @@ int mspack_cabd_prefetch(struct mscab_decompressor *base, struct mscabd_cabinet 
   struct mspack_system *sys;
   struct cab_p **list;
   size_t n = 0;
-  int i, todo = 0, err;
+  int i, todo = 0, err, st_batches;
   if (!self) return MSPACK_ERR_ARGS;
+  st_batches = stored_batches(self);
   if (n_cabs < 0 || (n_cabs > 0 && !cabs)) return self->error = MSPACK_ERR_ARGS;
   for (i = 0; i < n_cabs; i++) if (!cabs[i]) return self->error = MSPACK_ERR_ARGS;
   if (n_cabs == 0) return self->error = MSPACK_ERR_OK;
@@ -1610,7 +1737,7 @@ int mspack_cabd_prefetch(struct mscab_decompressor *base, struct mscabd_cabinet 
     for (; fo; fo = fo->next) {
       struct folder_p *fp = (struct folder_p *) fo;
       fp->listed = self->list_stamp;
-      if (!fp->decoded && !fp->job && (fo->comp_type & 0x0F) != MSCAB_COMP_NONE && !fp->merge_prev) todo = 1;
+      if (!fp->decoded && !fp->job && !fp->merge_prev && ((fo->comp_type & 0x0F) != MSCAB_COMP_NONE || (st_batches && !fp->st_streamed))) todo = 1;
     }
     list[n++] = (struct cab_p *) cabs[i];
   }
@@ -1636,7 +1763,7 @@ struct mscab_decompressor *mspack_create_cab_decompressor(struct mspack_system *
   self->system = sys;
   self->error = MSPACK_ERR_OK; self->read_error = MSPACK_ERR_OK;
   self->searchbuf_size = 32768; self->fix_mszip = 0; self->buf_size = 4096; self->salvage = 0;
-  self->devices = 1; self->cache_mb = 2048; self->list_stamp = 0; self->hip_digests = 0; self->hip_digests64 = 0; self->hip_crc32 = 0; self->sink = NULL; self->sink_kept = NULL;
+  self->devices = 1; self->cache_mb = 2048; self->list_stamp = 0; self->hip_digests = 0; self->hip_digests64 = 0; self->hip_crc32 = 0; self->hip_stored = 0; self->st_virtual = NULL; self->sink = NULL; self->sink_kept = NULL;
   memset(&self->st, 0, sizeof(self->st)); self->st_offset = 0; self->st_active = 0; self->last_folder = NULL;
   self->msg_folder = NULL; self->msg_offset = 0; self->msg_next = 0; self->msg_next_ck = 0;
   self->live_folder = NULL; self->live_offset = 0; self->live_failed = 0; self->live_err = MSPACK_ERR_OK;
